@@ -9,10 +9,15 @@ the batch rotates over enough buffer sets that the working set is > 512 MiB (Inf
 
 Timing: W warm-up steps plus a TIME-BASED warm-up (untimed steps until the device has worked for
 `--warmup-ms`, default 40 ms: it needs ~25 ms of continuous work to settle its clocks), then the timed region of
-EXACTLY K steps -- barrier + torch.cuda.synchronize() on both sides, HIP events on the launch stream inside -- is
-run `--repeats` times back to back (default max(5, ceil(400 / K)): at least 200 timed iterations) and the MEDIAN
-region is reported (`ms_per_step` = median wall / K; every repeat is listed in `timing.repeats_ms_per_step`, with
-`timing.total_timed_steps` and the mean over all of them).  Max over ranks per repeat.
+EXACTLY K steps -- barrier + torch.cuda.synchronize() on both sides, HIP events on the launch stream inside.  A plain
+run times that region once (`ms_per_step` = its wall / K).  With `--full` it is run `--repeats` times back to back
+(default max(5, ceil(400 / K)): at least 200 timed iterations) and the MEDIAN region is reported (`ms_per_step` =
+median wall / K; every repeat is listed in `timing.repeats_ms_per_step`, with `timing.total_timed_steps` and the mean
+over all of them).  Max over ranks per repeat.
+
+`--dump-outputs DIR` writes what the last timed step computed (output_arrays: float32, at most 64 MiB) after the timed
+region.  The inputs are drawn from fixed seeds and the last timed step always converts buffer set 0, so two builds run
+with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0).  N>1: one rank per GPU, launched either by torch.distributed.run (RANK /
 WORLD_SIZE in the environment) or by this script itself when `--gpus N` is given without such an environment
@@ -20,13 +25,13 @@ WORLD_SIZE in the environment) or by this script itself when `--gpus N` is given
 scaling); the only collective is a one-off RCCL broadcast of the 8 colour coefficients, verified against the
 compiled-in defaults.  With fewer than N GPUs visible it prints a "not measured" line instead of extrapolating.
 
-Besides the timed region the default line carries (world 1): the headline's other resize types and every BASELINE configuration (`config.other_workloads`), the facade leg, the
+A plain run does nothing else: set-up, warm-up, the timed steps, the dump, the line.  Besides the timed region a `--full` line carries (world 1): the headline's other resize types and every BASELINE configuration (`config.other_workloads`), the facade leg, the
 single-frame latency leg and -- round 6 -- `config.launch_curve`: the headline, C3 and C4 at 1 .. 64 frames per launch (tensor-stream_amd/cpp/vpp_curve.cpp, its own process), the reference's
 real calling pattern.  `--workload c5 --consumers 64` makes the step ONE read_many over this rank's share of 64 named consumers of a TensorStreamConverter (C5 as BASELINE words it).
 
-The oracle (oracle/) is touched only as the checker: the parity gate (AFTER the timed region, on frames 0 / 31 / 63 of the
+The oracle (oracle/) is touched only as the checker: the parity gate (--full, AFTER the timed region, on frames 0 / 31 / 63 of the
 buffer set the last timed step wrote -- the timed launch is the checked launch), `touched_bytes`,
-and the `cpu_baseline` leg.  A failure in a side leg (cpu_baseline, other_resize_types, traffic lookup) is
+and the `cpu_baseline` leg (--full).  A failure in a side leg (cpu_baseline, other_resize_types, traffic lookup) is
 recorded as {"error": ...} inside the line and can never swallow it.
 """
 import argparse
@@ -441,7 +446,12 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=0, help="the timed region of --steps steps is run this many times and the median is reported; "
-                    "0 = max(5, ceil(400 / steps)): SURVEY.md 8(d) asks for >= 200 timed iterations and a median of 5; 400 keep the clock ramp of the first ~25 ms out of the median")
+                    "0 = one region (exactly --steps timed steps), or with --full max(5, ceil(400 / steps)): SURVEY.md 8(d) asks for >= 200 timed iterations and a median of 5; "
+                    "400 keep the clock ramp of the first ~25 ms out of the median")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: the median over --repeats regions, the oracle parity gate, the other resize "
+                    "types and BASELINE configurations, the facade / latency / launch-curve legs and the cpu_baseline.  Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, "
+                    "at most 64 MiB: the whole output, or whole frames plus a fixed seeded sample of it; see output_arrays)")
     ap.add_argument("--batch", type=int, default=None, help="frames per step (one launch per MAX_LAUNCH = 128 frames: tsvpp.h TSVPP_MAX_BATCH; with --table up to 1024 per launch).  "
                     "Default: 64 -- except the small-frame BASELINE configurations C3 (512) and C4 (256), which run out of a persistent frame table (DEFAULT_BATCH)")
     ap.add_argument("--table", action="store_true", help="register every buffer set ONCE in a persistent device-resident frame table (tsvpp_table_*) and convert it with "
@@ -468,7 +478,47 @@ def parse_args(argv=None):
     ap.add_argument("--curve-only", default=None, help="run only the launch-curve leg (1 .. 64 frames per launch, tensor-stream_amd/cpp/vpp_curve.cpp) for these workloads, "
                     "comma separated (e.g. headline,c3,c4), print its JSON and exit")
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin the rank to the CPUs local to its GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.consumers:
+        ap.error("--dump-outputs needs a C-ABI workload: with --consumers the frame a step converts follows the producer thread's clock, so two runs are not comparable")
+    return args
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: the files of one run, in all
+DUMP_SAMPLE = 4 << 20       # elements of the seeded sample of an output larger than DUMP_BYTES (16 MiB as float32)
+DUMP_SEED = 20240611
+
+
+def output_arrays(out, frames=None):
+    """What a caller of the timed path receives -- `out`, the (B, ...) output tensor of one step -- as float32 numpy arrays of at most DUMP_BYTES in all.
+    An output that fits is returned whole (`output`).  A larger one gives `output_frames` (whole frames `frames`, default first / middle / last of the
+    batch, as many as fit beside the sample; their indices in `output_frame_index`) and `output_sample` (DUMP_SAMPLE elements of the flattened
+    output at sorted indices drawn from a generator seeded with DUMP_SEED: the same positions in every run of the same arguments)."""
+    n = out.numel()
+    if n * 4 <= DUMP_BYTES:
+        return {"output": out.float().cpu().numpy()}
+    B = out.shape[0]
+    per_frame = n // B
+    room = DUMP_BYTES - DUMP_SAMPLE * 4 - (1 << 20)
+    if frames is None:
+        frames = sorted({0, B // 2 - 1 if B > 2 else 0, B - 1})
+    frames = list(frames)[: max(0, room // (per_frame * 4))]
+    arrays = {}
+    if frames:
+        arrays["output_frames"] = out[frames].float().cpu().numpy()
+        arrays["output_frame_index"] = np.array(frames, dtype=np.float64)
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=min(n, DUMP_SAMPLE), dtype=np.int64))
+    import torch
+    flat = out.reshape(-1)
+    arrays["output_sample"] = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    return arrays
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def resolve_spec(args):
@@ -556,9 +606,15 @@ class StubEngine:
         self.parity = "stub"
         self.graphs = False
         self.cur_stream = 0
+        self.n_sets = 1
 
     def step(self, i):
         time.sleep(0.0005)
+
+    def last_output(self, last_step):
+        """A stand-in for the output of a step (the stub converts nothing): deterministic, so the --dump-outputs plumbing is testable without a GPU."""
+        import torch
+        return torch.arange(self.args.batch * 3 * 16, dtype=torch.float32).reshape(self.args.batch, 3, 4, 4) / 255.0
 
     def sync(self):
         pass
@@ -610,6 +666,7 @@ class FacadeEngine:
         self.extra_streams = []
         self.cur_stream = torch.cuda.current_stream(dev).cuda_stream
         self.last = None
+        self.n_sets = 1
 
     def step(self, i):
         self.last = self.conv.read_many(self.names, **self.kw)
@@ -752,6 +809,7 @@ class GpuEngine:
         self.ws_mib = self.work.ws_mib
         self.launches_per_step = self.work.launches_per_step
         self.frames_per_launch = self.work.frames_per_launch
+        self.n_sets = len(self.work.sets)  # step i converts buffer set i % n_sets (graphs: one per set)
 
         self.parity = "skipped"  # filled in by check_parity() AFTER the timed region, on the timed launches' own output
 
@@ -790,6 +848,10 @@ class GpuEngine:
             return "tsvpp::" + str(dsc.get("kernel", "?"))
         except Exception as e:
             return f"tsvpp::? ({type(e).__name__}: {e})"
+
+    def last_output(self, last_step):
+        """The output tensor step `last_step` wrote: its buffer set's (B, ...) output, as a caller of tsvpp_convert_batch receives it."""
+        return self.work.sets[last_step % self.n_sets][2]
 
     def step(self, i):
         if self.graphs:
@@ -1068,17 +1130,30 @@ def run(args):
                 extra += 1
             eng.sync()
     reps, mine_reps = [], []
-    n_rep = args.repeats if args.repeats > 0 else max(5, -(-400 // max(1, args.steps)))
+    n_rep = args.repeats if args.repeats > 0 else (max(5, -(-400 // max(1, args.steps))) if args.full else 1)
+    # A few more untimed steps so that the last timed step converts buffer set 0 whatever the time-based warm-up ran: --dump-outputs then
+    # writes the same frames in every run of the same arguments (the sets keep rotating in order, so no timed step finds its set in cache)
+    while (first + n_rep * args.steps - 1) % eng.n_sets:
+        eng.step(first)
+        first += 1
+        extra += 1
+    eng.sync()
     for _ in range(n_rep):
         r, mine = region(args.steps, first)
         first += args.steps
         reps.append(r)
         mine_reps.append(mine)
-    # Parity gate: the output the LAST TIMED STEP left in its buffer set against the oracle (rank 0; the other ranks run the same code
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, output_arrays(eng.last_output(first - 1)))
+        log(f"--dump-outputs: {', '.join(dumped)} -> {args.dump_outputs}")
+    # Parity gate (--full): the output the LAST TIMED STEP left in its buffer set against the oracle (rank 0; the other ranks run the same code
     # on their own frames).  After the timed region, so the oracle's CPU time is never inside it.
     parity_fail = False
     if not stub and rank == 0:
-        if args.no_parity:
+        if not args.full:
+            eng.parity = "not checked (the oracle parity gate runs with --full)"
+        elif args.no_parity:
             eng.parity = "skipped (--no-parity)"
         elif args.alias:
             eng.parity = "skipped (aliased diagnostic buffers)"
@@ -1160,7 +1235,7 @@ def run(args):
             return {"error": f"{type(e).__name__}: {e}"}
 
     others, other_wl = None, None
-    if (not stub or dist is not None) and name == "headline" and not args.resize and not args.no_others and not args.consumers:
+    if args.full and (not stub or dist is not None) and name == "headline" and not args.resize and not args.no_others and not args.consumers:
         others = {}
         for rname in ("NEAREST", "BICUBIC", "AREA"):
             sp = list(spec)
@@ -1265,7 +1340,9 @@ def run(args):
         if other_wl is not None:
             res["config"]["other_workloads"] = other_wl
         # (round 6) N > 1 lines carry it too: rank 0 measures it here, after every timed region, while the other ranks wait in the final barrier
-        if not args.no_cpu_baseline:
+        if dumped is not None:
+            res["config"]["dump_outputs"] = dumped
+        if args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(spec, budget_s=(min(args.cpu_budget, 0.3) if stub else args.cpu_budget), tight_pitch=args.tight_pitch)
             except Exception as e:

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,12 +63,12 @@ FLAG_SETS = [[], ["--tight-pitch"], ["--workload", "c4"], ["--workload", "c3", "
 
 @pytest.mark.parametrize("flags", FLAG_SETS, ids=lambda f: " ".join(f) or "default")
 def test_main_flow_on_the_stub_engine(flags, capsys, monkeypatch):
-    """The default path of main() (everything but the GPU engine): one well-formed line with roofline + cpu_baseline."""
+    """The --full path of main() (everything but the GPU engine): one well-formed line with roofline + cpu_baseline."""
     monkeypatch.setenv("TSVPP_BENCH_STUB", "1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     budget = "0.05" if ("c4" in flags or "c5" in flags) else "0.2"
-    assert bench.main(["--steps", "3", "--warmup", "1", "--cpu-budget", budget] + flags) == 0
+    assert bench.main(["--full", "--steps", "3", "--warmup", "1", "--cpu-budget", budget] + flags) == 0
     res = _line(capsys.readouterr().out)
     for k in REQUIRED:
         assert k in res, k
@@ -105,7 +106,7 @@ def test_a_failing_side_leg_cannot_swallow_the_line(capsys, monkeypatch):
     monkeypatch.setattr(bench, "cpu_baseline", boom)
     monkeypatch.setattr(bench, "touched_bytes", boom)
     monkeypatch.setattr(bench, "lookup_traffic", boom)
-    assert bench.main(["--steps", "2", "--warmup", "0"]) == 0
+    assert bench.main(["--full", "--steps", "2", "--warmup", "0"]) == 0
     res = _line(capsys.readouterr().out)
     assert "NameError" in res["cpu_baseline"]["error"] and res["value"] > 0
     assert "NameError" in res["roofline"]["touched_bytes"]["error"]
@@ -116,7 +117,7 @@ def test_gpus_2_self_spawn_on_gloo():
     torch.distributed.run: rendezvous, barriers, max-over-ranks, ONE rank-0 line with n_gpus == 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["TSVPP_BENCH_STUB"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     res = _line(p.stdout)
@@ -225,7 +226,7 @@ def test_gpus_8_self_spawn_on_gloo():
     ONE line, n_gpus 8, eight per-rank entries, the 4K workloads in the line, whole-job aggregate."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["TSVPP_BENCH_STUB"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=400)
     assert p.returncode == 0, p.stderr[-2000:]
     res = _line(p.stdout)
@@ -300,3 +301,55 @@ def test_setup_times_travel_in_the_line():
     steps = [s[0] for s in res["per_rank"]["rank0_setup_steps"]]
     assert steps[:2] == ["rendezvous", "engine"] and "ready-check" in steps
     assert "set-up: rendezvous done" in p.stderr and "[bench.py rank 1/2]" in p.stderr
+
+
+def test_plain_run_times_exactly_the_given_steps_and_nothing_else(capsys, monkeypatch):
+    """Without --full: ONE timed region of exactly --steps steps, no side legs, no cpu_baseline, the parity gate left to --full."""
+    monkeypatch.setenv("TSVPP_BENCH_STUB", "1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+
+    def boom(*a, **k):
+        raise AssertionError("a plain run must not run the cpu_baseline leg")
+
+    monkeypatch.setattr(bench, "cpu_baseline", boom)
+    assert bench.main(["--steps", "7", "--warmup", "2"]) == 0
+    res = _line(capsys.readouterr().out)
+    for k in REQUIRED:
+        assert k in res, k
+    t = res["timing"]
+    assert res["steps"] == 7 and t["repeats"] == 1 and t["total_timed_steps"] == 7 and t["repeats_ms_per_step"] == [res["ms_per_step"]]
+    assert abs(res["value"] - 64 * 7 / (res["ms_per_step"] * 7e-3)) / res["value"] < 1e-3
+    assert "cpu_baseline" not in res and "other_workloads" not in res["config"] and "other_resize_types" not in res["config"]
+    assert res["metric"] == bench.METRIC and res["higher_is_better"] is True and res["unit"] == "frames/s" and res["dtype"] == "f32"
+
+
+def test_output_arrays_are_float32_within_64_mib():
+    import torch
+    small = torch.arange(2 * 3 * 8 * 8, dtype=torch.uint8).reshape(2, 3, 8, 8)
+    a = bench.output_arrays(small)
+    assert list(a) == ["output"] and a["output"].dtype == np.float32 and np.array_equal(a["output"], small.numpy().astype(np.float32))
+    big = torch.rand((64, 3, 256, 1290), generator=torch.Generator().manual_seed(0))   # the headline's shape class: 254 MiB as float32
+    a = bench.output_arrays(big)
+    assert set(a) == {"output_frames", "output_frame_index", "output_sample"}
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BYTES and all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert a["output_frame_index"].tolist() == [0, 31, 63] and np.array_equal(a["output_frames"], big[[0, 31, 63]].numpy())
+    b = bench.output_arrays(big)   # the sample's positions are fixed: the same output gives the same arrays
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    huge = torch.zeros((4, 3, 2160, 3840), dtype=torch.uint8)     # a frame larger than the room beside the sample: the sample alone
+    a = bench.output_arrays(huge)
+    assert set(a) == {"output_sample"} and sum(x.nbytes for x in a.values()) <= bench.DUMP_BYTES
+
+
+def test_dump_outputs_writes_the_last_step_the_same_way_every_run(tmp_path, capsys, monkeypatch):
+    monkeypatch.setenv("TSVPP_BENCH_STUB", "1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    for run in ("a", "b"):
+        assert bench.main(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)]) == 0
+        res = _line(capsys.readouterr().out)
+        assert res["config"]["dump_outputs"] == ["output"]
+    a, b = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "b" / "output.npy")
+    assert a.dtype == np.float32 and a.shape[0] == 64 and np.array_equal(a, b)
+    with pytest.raises(SystemExit):   # a step of --consumers reads whatever frame the producer published last: nothing to compare
+        bench.parse_args(["--workload", "c5", "--consumers", "8", "--dump-outputs", str(tmp_path / "c")])

@@ -68,7 +68,7 @@ def _check(p):
 
 def test_torchrun_world1_nccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, env=_env(OMP_NUM_THREADS="1"), capture_output=True, text=True, timeout=600)
     res = _check(p)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -77,7 +77,7 @@ def test_torchrun_world1_nccl():
 
 
 def test_force_dist_world1_nccl():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"],
                        env=_env(TSVPP_BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port())), capture_output=True, text=True, timeout=600)
     _check(p)
 
@@ -87,7 +87,7 @@ def test_force_dist_world1_nccl():
 def test_perf_floors_of_the_other_baseline_configurations(wl, key):
     """C3 (512-frame launches out of a persistent frame table on the row-segment kernel: 3.25 M frames/s, 0.72 of the roofline on moved bytes; the byte-gather
     kernel of rounds 1-4 ran 2.6 M) and C2; the headline, its three other resize types, C4 and C5 are checked on the default line above."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-others"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-others", "--full"],
                        env=_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     res = json.loads([l for l in p.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -114,7 +114,7 @@ def test_single_frame_latency_tool():
 def test_c5_named_consumers_through_the_facade_world1():
     """`--workload c5 --consumers 16` (C5 as BASELINE words it, here 16 named consumers on the one GPU of this box): the timed step is one
     TensorStreamConverter.read_many over this rank's consumers; the line names the sharding and its parity check."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--consumers", "16", "--steps", "20", "--warmup", "5", "--cpu-budget", "2"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--consumers", "16", "--steps", "20", "--warmup", "5", "--cpu-budget", "2", "--full"],
                        env=_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     res = json.loads([l for l in p.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -122,3 +122,37 @@ def test_c5_named_consumers_through_the_facade_world1():
     assert c["total"] == 16 and c["per_rank"] == 16 and res["config"]["frames_per_step"] == 16
     assert res["config"]["parity"].startswith("bit-exact") and res["value"] > 0 and res["cpu_baseline"]["value"] > 0
     print("\n" + json.dumps({k: res[k] for k in ("value", "ms_per_step", "roofline")}))
+
+
+def test_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """The plain line (no --full) on the GPU: exactly --steps timed steps in one region, and --dump-outputs writes the last timed step's output --
+    the same bits in two runs of the same arguments, whole frames of it equal to the CPU oracle's conversion of the same inputs."""
+    import numpy as np
+    import torch
+    from oracle import oracle as O
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--dump-outputs", str(d)],
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+        res = json.loads([l for l in p.stdout.splitlines() if l.startswith('{"metric"')][-1])
+        t = res["timing"]
+        assert res["value"] > 0 and res["ms_per_step"] > 0 and t["repeats"] == 1 and t["total_timed_steps"] == 8
+        assert "cpu_baseline" not in res and "other_workloads" not in res["config"]
+        files = sorted(os.listdir(d))
+        assert files == ["output_frame_index.npy", "output_frames.npy", "output_sample.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f: np.load(d / f) for f in files})
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+    # the dumped frames are buffer set 0 of the headline: the seeded inputs bench.GpuWork draws, converted by the oracle
+    import bench
+    src_w, src_h, pitch, crop, dst, rt, fcc, planes, norm = bench.WORKLOADS["headline"]
+    g = torch.Generator(device="cuda").manual_seed(1234)
+    ys = torch.randint(0, 256, (64, src_h, pitch), dtype=torch.uint8, device="cuda", generator=g)
+    uvs = torch.randint(0, 256, (64, src_h // 2, pitch), dtype=torch.uint8, device="cuda", generator=g)
+    frames = dumps[0]["output_frames.npy"]
+    for j, k in enumerate(int(x) for x in dumps[0]["output_frame_index.npy"]):
+        ref, _, _ = O.convert(ys[k].cpu().numpy(), uvs[k].cpu().numpy(), crop=crop, dst=dst, resize_type=bench.RESIZE[rt], fourcc=bench.FOURCC[fcc],
+                              planes=bench.PLANES[planes], normalization=norm, width=src_w)
+        assert np.array_equal(frames[j].ravel(), ref), k

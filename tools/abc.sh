@@ -3,7 +3,7 @@ export TSVPP_DEBUG_KNOBS=1  # the A/B knobs are honoured only under this gate (r
 # same-box A/B of environment settings over ad-hoc workloads:
 #   tools/abc.sh "SRC:DST:RESIZE:FOURCC:PLANES:NORM ..." "ENV_A" "ENV_B" ...     (an empty ENV = defaults)
 # prints one row per workload, one column per setting: frames/s, fraction of the 8 TB/s roofline, parity
-one() { env $1 python bench.py --custom "$2" --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+one() { env $1 python bench.py --full --custom "$2" --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import sys,json
 try:
     r=json.loads(sys.stdin.read()); print('%8.0f fps %.3f %s' % (r['value'], r['roofline']['frac'], 'ok' if r['config']['parity'].startswith('bit-exact') else 'PARITY-FAIL'), end='')

@@ -1,4 +1,4 @@
-one() { python bench.py --custom "$1" --steps 20 --warmup 3 --no-cpu-baseline --no-parity --alias $2 2>&1 | tail -1 | python -c "
+one() { python bench.py --full --custom "$1" --steps 20 --warmup 3 --no-cpu-baseline --no-parity --alias $2 2>&1 | tail -1 | python -c "
 export TSVPP_DEBUG_KNOBS=1  # the A/B knobs are honoured only under this gate (round 6)
 import sys,json
 r=json.loads(sys.stdin.read()); print('%8.0f fps %.3f' % (r['value'], r['roofline']['frac']), end='')"; }

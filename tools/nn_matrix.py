@@ -20,7 +20,7 @@ import pmc_lib  # noqa: E402
 
 
 def bench(custom, batch, env, extra=()):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--custom", custom, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--batch", str(batch)] + list(extra)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--custom", custom, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--batch", str(batch)] + list(extra)
     if batch > 128:
         cmd.append("--table")
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)

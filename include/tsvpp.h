@@ -239,6 +239,17 @@ int tsvpp_area_pattern(float scale, float *out, int max_floats, int *taps);
  * Returns TSVPP_OK or the status tsvpp_convert would return for the request. */
 int tsvpp_describe(const tsvpp_params *p, int in_width, int in_height, int pitch_y, int pitch_uv, int n_frames, int aligned_outputs, char *buf,
                    size_t buf_len);
+/* (describe, continued) nt= is the store variant of the launch (0 plain stores, 1 / 2 non-temporal, + 4: the 4-byte uint8
+ * stores non-temporal too), staged= says that the launch stages its source through LDS (for the colour-only kernel: that
+ * its dword-aligned fast path is taken), in4= that every plane pointer and both pitches are multiples of 4 (frame
+ * pointers assumed 256-byte aligned). */
+
+/* DEBUG ONLY (tests): what the calling thread's last tsvpp_convert / tsvpp_convert_batch / tsvpp_convert_table actually
+ * launched -- a replayed launch included -- in tsvpp_describe's format (src= / dst= are the launch's; lds= is the
+ * dynamic LDS only).  Answers only when TSVPP_DEBUG_KNOBS=1 is set now (else TSVPP_UNSUPPORTED).  TSVPP_ERROR when the
+ * thread's last conversion recorded nothing: it ran in a context created without TSVPP_DEBUG_KNOBS=1, it failed, or
+ * the thread has converted nothing.  A record of an earlier conversion is never reported. */
+int tsvpp_debug_last_launch(char *buf, size_t buf_len);
 
 /* Human-readable text for a status returned by this library. */
 const char *tsvpp_strerror(int status);

@@ -278,6 +278,7 @@ struct tsvpp_ctx {
     uint64_t id = 0;
     std::atomic<uint64_t> epoch{ 1 };
     int replay = 1; // TSVPP_REPLAY=0 (debug knob): every call runs the full selection
+    int debug = 0;  // created under TSVPP_DEBUG_KNOBS=1: every conversion keeps its launch record for tsvpp_debug_last_launch
     int color_g = 0; // TSVPP_OPT_COLOR_G_TERM
     int unsafe_coeffs = 0; // TSVPP_OPT_UNSAFE_COEFFS: tsvpp_set_coeffs accepts a block that differs from the defaults
     std::set<struct tsvpp_table *> tables; // live frame tables: released with the context if the caller destroys it first
@@ -390,6 +391,7 @@ void read_env_knobs(tsvpp_ctx *ctx, bool report = false) {
     const bool on = gate && std::atoi(gate) != 0;
     std::string seen;
     auto note = [&](const char *name, const char *val) { seen += std::string(seen.empty() ? "" : " ") + name + "=" + val; };
+    ctx->debug = on ? 1 : 0;
     for (const KnobRow &k : kKnobs)
         if (const char *e = std::getenv(k.name)) {
             note(k.name, e);
@@ -685,6 +687,12 @@ constexpr int kReplayEntries = 8;
 constexpr int kReplayMiss = -1000;
 thread_local ReplayEntry g_replay[kReplayEntries];
 thread_local uint64_t g_replay_clock = 0;
+// tsvpp_debug_last_launch: the record of this thread's last conversion, if it ran in a context created under TSVPP_DEBUG_KNOBS=1 -- a replay slot's (replayed or
+// just remembered) or a copy of a record that is not replayable (several launches, a second pass, a frame table); null otherwise.  Every conversion clears it first.
+// What that costs every conversion: two thread-local pointer stores, three int stores into the launch record, and in each launcher one thread-local load
+// (record_name) -- the record itself is only armed where the replay cache arms it anyway, or in a debug context.
+thread_local const LaunchRecord *g_last_launch = nullptr;
+thread_local LaunchRecord g_last_copy;
 struct RecordArm { // points launch_fused's launches at `rec` for the lifetime of this object
     explicit RecordArm(LaunchRecord *rec) { g_launch_rec = rec; }
     ~RecordArm() { g_launch_rec = nullptr; }
@@ -730,12 +738,13 @@ int try_replay(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *
                                    ? hipExtLaunchKernel(e.rec.fn, e.rec.grid, e.rec.block, args, e.rec.lds, (hipStream_t)stream, nullptr, nullptr, hipExtAnyOrderLaunch)
                                    : hipLaunchKernel(e.rec.fn, e.rec.grid, e.rec.block, args, e.rec.lds, (hipStream_t)stream);
         e.stamp = ++g_replay_clock;
+        if (err == hipSuccess && ctx->debug) g_last_launch = &e.rec;
         return (int)err;
     }
     return kReplayMiss;
 }
 
-void remember_launch(const tsvpp_ctx *ctx, uint64_t epoch, int n, const tsvpp_nv12 *in, const tsvpp_params *p, int py, int puv, bool aligned4, bool vec, size_t y_off,
+const LaunchRecord *remember_launch(const tsvpp_ctx *ctx, uint64_t epoch, int n, const tsvpp_nv12 *in, const tsvpp_params *p, int py, int puv, bool aligned4, bool vec, size_t y_off,
                      size_t uv_off, const LaunchRecord &rec) {
     ReplayEntry *slot = &g_replay[0];
     for (ReplayEntry &e : g_replay)
@@ -754,6 +763,7 @@ void remember_launch(const tsvpp_ctx *ctx, uint64_t epoch, int n, const tsvpp_nv
     slot->y_off = y_off;
     slot->uv_off = uv_off;
     slot->rec = rec;
+    return &slot->rec;
 }
 
 } // namespace
@@ -1022,6 +1032,7 @@ struct TableCols {
 
 // tsvpp_convert_batch and tsvpp_convert_table: `in` / `outs` are HOST arrays of the n frames (a table's pinned mirror for the latter).
 static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, void *const *outs, void *stream, const TableCols &tab) {
+    g_last_launch = nullptr; // (tsvpp_debug_last_launch: no stale record survives a conversion that records none)
     if (!ctx || !in || !p || !outs || n < 0) return TSVPP_ERROR;
     if (n == 0) return TSVPP_OK;
     const bool replayable = ctx->replay && tab.y == nullptr && n <= TSVPP_MAX_BATCH && !ctx->markers;
@@ -1160,14 +1171,37 @@ static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
                 if (((uintptr_t)outs[base + f] & 15) != 0) vec = false;
         if (!(two_pass && pl.mode == M_NONE)) {
             LaunchRecord rec;
+            rec.mode = pl.mode;
+            rec.out = out_kind;
+            rec.pass2 = two_pass ? pl.fourcc : 0;
             const bool keep = replayable && !two_pass && n <= max_launch; // one launch group, one pass
             hipError_t e;
             {
-                RecordArm arm(keep ? &rec : nullptr);
+                RecordArm arm((keep || ctx->debug) ? &rec : nullptr);
                 e = launch_fused(pl.mode, out_kind, vec, d, t, (hipStream_t)stream);
             }
-            if (e != hipSuccess) return (int)e;
-            if (keep && rec.count == 1 && rec.fn) remember_launch(ctx, epoch0, n, in, p, pitch_y, pitch_uv, aligned4, vec, y_off, uv_off, rec);
+            if (e != hipSuccess) {
+                g_last_launch = nullptr; // (an earlier launch group's record does not describe a failed conversion)
+                return (int)e;
+            }
+            if (keep && rec.count == 1 && rec.fn) {
+                const LaunchRecord *kept = remember_launch(ctx, epoch0, n, in, p, pitch_y, pitch_uv, aligned4, vec, y_off, uv_off, rec);
+                if (ctx->debug) g_last_launch = kept;
+            } else if (ctx->debug && rec.count > 0) { // (count == 0: nothing was launched, and rec.d was never written)
+                g_last_copy = rec;
+                g_last_launch = &g_last_copy;
+            } else {
+                g_last_launch = nullptr;
+            }
+        } else if (ctx->debug) { // crop + format conversion: the second pass alone
+            g_last_copy = LaunchRecord();
+            g_last_copy.name = "(none)";
+            g_last_copy.mode = pl.mode;
+            g_last_copy.out = out_kind;
+            g_last_copy.pass2 = pl.fourcc;
+            g_last_copy.d.in_aligned4 = aligned4 ? 1 : 0;
+            g_last_copy.d.n_frames = cnt;
+            g_last_launch = &g_last_copy;
         }
         if (two_pass) {
             int fpy = pitch_y, fpuv = pitch_uv;
@@ -1180,7 +1214,10 @@ static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
                 fpy = fpuv = pl.dst_w;
             }
             hipError_t e = launch_format(pl.fourcc, pl.f32, t, cnt, fpy, fpuv, pl.dst_w, pl.dst_h, (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
+            if (e != hipSuccess) {
+                g_last_launch = nullptr;
+                return (int)e;
+            }
         }
     }
     return TSVPP_OK;
@@ -1435,6 +1472,25 @@ int tsvpp_area_pattern(float scale, float *out, int max_floats, int *taps) {
     return rows;
 }
 
+} // extern "C"
+
+// The answer of tsvpp_describe / tsvpp_debug_last_launch: one line of key=value pairs.
+static void format_selection(char *buf, size_t buf_len, int mode, int out, int src_w, int src_h, int dst_w, int dst_h, const LaunchInfo &info, int frames, int pass2) {
+    static const char *const out_names[O_COUNT_ALL] = { "u8_planar", "u8_merged", "f32_planar", "f32_merged", "nv12_u8", "nv12_f32", "y800_u8", "y800_f32", "hsv_f32", "uyvy_u8", "yuv444_u8", "uyvy_f32" };
+    static const char *const mode_names[M_COUNT] = { "none", "nearest", "bilinear", "bicubic", "area_down", "area_up" };
+    char kname[128]; // the launcher's spelling without blanks: one token per key=value pair
+    size_t kn = 0;
+    for (const char *c = info.kernel ? info.kernel : "(unnamed)"; *c && kn + 1 < sizeof(kname); c++)
+        if (*c != ' ') kname[kn++] = *c;
+    kname[kn] = 0;
+    std::snprintf(buf, buf_len, "mode=%s out=%s src=%dx%d dst=%dx%d kernel=%s shape=%dx%d rpt=%d dma=%d lds=%d grid=%d tiles=%dx%d frames=%d tail=%d geo=%d nt=%d staged=%d in4=%d%s",
+                  mode_names[mode], out_names[out], src_w, src_h, dst_w, dst_h, kname, info.tx, info.ty, info.rpt, info.dma, info.lds_bytes, info.grid, info.tiles_x,
+                  info.tiles_y, frames, info.tail, info.geo, info.nt, info.staged, info.in4,
+                  pass2 ? (pass2 == TSVPP_UYVY ? " pass2=fmt_uyvy" : " pass2=fmt_yuv444") : "");
+}
+
+extern "C" {
+
 int tsvpp_describe(const tsvpp_params *p, int in_width, int in_height, int pitch_y, int pitch_uv, int n_frames, int aligned_outputs, char *buf,
                    size_t buf_len) {
     if (!p || !buf || buf_len == 0) return TSVPP_ERROR;
@@ -1489,24 +1545,44 @@ int tsvpp_describe(const tsvpp_params *p, int in_width, int in_height, int pitch
     const OutKind out_kind = single ? single_pass_kind(pl) : pl.out;
     const bool two_pass = (pl.fourcc == TSVPP_UYVY || pl.fourcc == TSVPP_YUV444) && !single;
     d.n_frames = n_frames < TSVPP_MAX_BATCH ? n_frames : TSVPP_MAX_BATCH;
-    static const char *const out_names[O_COUNT_ALL] = { "u8_planar", "u8_merged", "f32_planar", "f32_merged", "nv12_u8", "nv12_f32", "y800_u8", "y800_f32", "hsv_f32", "uyvy_u8", "yuv444_u8", "uyvy_f32" };
-    static const char *const mode_names[M_COUNT] = { "none", "nearest", "bilinear", "bicubic", "area_down", "area_up" };
+    if (two_pass && d.nt_stores < 0) d.nt_stores = 0; // (as convert_impl: the intermediate is read back at once)
     LaunchInfo info = {};
     info.kernel = "(none)";
+    info.in4 = d.in_aligned4;
     if (!(two_pass && pl.mode == M_NONE)) {
         FrameTable t = {};
         hipError_t e = launch_fused(pl.mode, out_kind, aligned_outputs != 0 || two_pass, d, t, nullptr, &info);
         if (e != hipSuccess) return (int)e;
     }
-    char kname[128]; // the launcher's spelling without blanks: one token per key=value pair
-    size_t kn = 0;
-    for (const char *c = info.kernel; *c && kn + 1 < sizeof(kname); c++)
-        if (*c != ' ') kname[kn++] = *c;
-    kname[kn] = 0;
-    std::snprintf(buf, buf_len, "mode=%s out=%s src=%dx%d dst=%dx%d kernel=%s shape=%dx%d rpt=%d dma=%d lds=%d grid=%d tiles=%dx%d frames=%d tail=%d geo=%d%s",
-                  mode_names[pl.mode], out_names[out_kind], pl.src_w, pl.src_h, pl.dst_w, pl.dst_h, kname, info.tx, info.ty, info.rpt, info.dma,
-                  info.lds_bytes, info.grid, info.tiles_x, info.tiles_y, d.n_frames, info.tail, info.geo,
-                  two_pass ? (pl.fourcc == TSVPP_UYVY ? " pass2=fmt_uyvy" : " pass2=fmt_yuv444") : "");
+    format_selection(buf, buf_len, pl.mode, out_kind, pl.src_w, pl.src_h, pl.dst_w, pl.dst_h, info, d.n_frames, two_pass ? pl.fourcc : 0);
+    return TSVPP_OK;
+}
+
+int tsvpp_debug_last_launch(char *buf, size_t buf_len) {
+    if (!buf || buf_len == 0) return TSVPP_ERROR;
+    buf[0] = 0;
+    const char *gate = std::getenv("TSVPP_DEBUG_KNOBS");
+    if (!gate || std::atoi(gate) == 0) return TSVPP_UNSUPPORTED;
+    const LaunchRecord *r = g_last_launch;
+    if (!r) return TSVPP_ERROR;
+    // the fields tsvpp_describe reports, read off the launch as it went out: the FINAL descriptor of the first launch; a second launch is the row tail
+    const LaunchDesc &d = r->d;
+    LaunchInfo info = {};
+    info.kernel = r->name;
+    info.tx = d.tx;
+    info.ty = d.ty;
+    info.rpt = d.rpt;
+    info.dma = d.dma;
+    info.staged = r->staged;
+    info.lds_bytes = (int)r->lds; // (dynamic LDS only: tsvpp_describe adds the static exchange slabs of some kernels)
+    info.grid = (int)r->grid.x;
+    info.tiles_x = d.tiles_x;
+    info.tiles_y = d.tiles_y;
+    info.tail = d.last_col0 > 0 ? 2 : (r->count > 1 ? 1 : 0);
+    info.geo = d.geo;
+    info.nt = d.nt_stores;
+    info.in4 = d.in_aligned4;
+    format_selection(buf, buf_len, r->mode, r->out, d.src_w, d.src_h, d.dst_w, d.dst_h, info, d.n_frames, r->pass2);
     return TSVPP_OK;
 }
 

@@ -296,14 +296,15 @@ static hipError_t launch_area_stream_nk(OutKind out, const LaunchDesc &d, const 
 // zero-fills the weights past the table's 4 * d.nkx).
 hipError_t launch_area_stream(OutKind out, const LaunchDesc &d, const FrameTable &t, size_t lds_bytes, hipStream_t stream, LaunchInfo *info) {
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD));
+    static const char *const names[9] = { "", "vpp_area_stream_kernel<1,OUT>", "vpp_area_stream_kernel<2,OUT>", "vpp_area_stream_kernel<3,OUT>", "vpp_area_stream_kernel<4,OUT>",
+                                          "", "vpp_area_stream_kernel<6,OUT>", "", "vpp_area_stream_kernel<8,OUT>" };
     if (info) {
-        static const char *const names[9] = { "", "vpp_area_stream_kernel<1,OUT>", "vpp_area_stream_kernel<2,OUT>", "vpp_area_stream_kernel<3,OUT>", "vpp_area_stream_kernel<4,OUT>",
-                                              "", "vpp_area_stream_kernel<6,OUT>", "", "vpp_area_stream_kernel<8,OUT>" };
         info->kernel = (d.as_nk >= 1 && d.as_nk <= 8) ? names[d.as_nk] : "";
         info->grid = (int)grid.x;
         info->lds_bytes = (int)lds_bytes;
         return hipSuccess;
     }
+    if (d.as_nk >= 1 && d.as_nk <= 8) record_name(names[d.as_nk]);
     switch (d.as_nk) {
     case 1: return launch_area_stream_nk<1>(out, d, t, grid, lds_bytes, stream);
     case 2: return launch_area_stream_nk<2>(out, d, t, grid, lds_bytes, stream);

@@ -580,14 +580,16 @@ const BcEntry *bicubic_cols_tables(const LaunchDesc &d, hipStream_t stream, bool
 hipError_t launch_bicubic_cols(OutKind out, bool exact, const LaunchDesc &d, const FrameTable &t, size_t lds_bytes, hipStream_t stream, LaunchInfo *info) {
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block(MAX_THREADS);
     const bool sparse = d.bc_sparse != 0;
-    if (info) {
-        info->kernel = exact ? (sparse ? "vpp_bicubic_cols_kernel<OUT, exact, sparse>" : "vpp_bicubic_cols_kernel<OUT, exact, dense>")
+    const char *name = exact ? (sparse ? "vpp_bicubic_cols_kernel<OUT, exact, sparse>" : "vpp_bicubic_cols_kernel<OUT, exact, dense>")
                              : (sparse ? "vpp_bicubic_cols_kernel<OUT, tie, sparse>" : "vpp_bicubic_cols_kernel<OUT, tie, dense>");
+    if (info) {
+        info->kernel = name;
         info->grid = (int)grid.x;
         info->lds_bytes = (int)lds_bytes + (out == O_U8_MERGED ? MAX_THREADS * 24 : 0); // + the static exchange slab of the uint8 merged output side
         return hipSuccess;
     }
     if (!d.bc_tab) return hipErrorInvalidValue;
+    record_name(name);
     switch (out) {
 #define TSVPP_BC(O)                                                                                                               \
     case O:                                                                                                                       \

@@ -263,6 +263,7 @@ hipError_t launch_bicubic_int(OutKind out, const LaunchDesc &d, const FrameTable
         info->lds_bytes = (int)lds_bytes;
         return hipSuccess;
     }
+    record_name("vpp_bicubic_int_kernel<OUT>");
     switch (out) {
 #define TSVPP_BI(O) case O: TSVPP_LAUNCH((vpp_bicubic_int_kernel<O>), grid, block, lds_bytes, stream, d, t); break;
         TSVPP_BI(O_U8_PLANAR) TSVPP_BI(O_U8_MERGED) TSVPP_BI(O_F32_PLANAR) TSVPP_BI(O_F32_MERGED) TSVPP_BI(O_NV12_U8)

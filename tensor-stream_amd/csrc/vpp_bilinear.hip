@@ -745,13 +745,15 @@ hipError_t launch_bilinear(bool areaup, OutKind out, const LaunchDesc &din, cons
         const size_t cols = (size_t)d.tx * PXW, rows = (size_t)d.ty * PXH * d.rpt;
         lds_bytes -= (cols + cols / 2) * sizeof(XEntry) + (rows + rows / 2) * sizeof(YEntry);
     }
+    const char *name = areaup ? "vpp_bilinear_kernel<areaup,OUT>" : d.tap22 ? "vpp_bilinear_kernel<bilinear,OUT>[area-weights]" : "vpp_bilinear_kernel<bilinear,OUT>";
     if (info) {
-        info->kernel = areaup ? "vpp_bilinear_kernel<areaup,OUT>" : d.tap22 ? "vpp_bilinear_kernel<bilinear,OUT>[area-weights]" : "vpp_bilinear_kernel<bilinear,OUT>";
+        info->kernel = name;
         info->grid = (int)grid.x;
         info->lds_bytes = (int)lds_bytes;
         info->geo = d.geo;
         return hipSuccess;
     }
+    record_name(name);
     if (d.geo) return launch_bilinear_geo(out, d, t, grid, block, lds_bytes, stream);
     return areaup ? launch_bilinear_a<true>(out, d, t, grid, block, lds_bytes, stream)
                   : launch_bilinear_a<false>(out, d, t, grid, block, lds_bytes, stream);

@@ -255,14 +255,15 @@ __global__ __launch_bounds__(MAX_THREADS) void vpp_bilinear_rows_kernel(const La
 hipError_t launch_bilinear_rows(OutKind out, const LaunchDesc &d, const FrameTable &t, size_t lds_bytes, hipStream_t stream, LaunchInfo *info) {
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(64 * d.br_waves));
     const int kind = d.point_kind == PK_NEAREST ? BRK_NEAREST : (d.point_kind != PK_NONE ? BRK_POINT : (d.wx_zero != 0 ? BRK_WX0 : BRK_2X2));
+    static const char *const names[4] = { "vpp_bilinear_rows_kernel<OUT, 2x2>", "vpp_bilinear_rows_kernel<OUT, wx0>", "vpp_bilinear_rows_kernel<OUT, point>",
+                                          "vpp_bilinear_rows_kernel<OUT, nearest>" };
     if (info) {
-        static const char *const names[4] = { "vpp_bilinear_rows_kernel<OUT, 2x2>", "vpp_bilinear_rows_kernel<OUT, wx0>", "vpp_bilinear_rows_kernel<OUT, point>",
-                                              "vpp_bilinear_rows_kernel<OUT, nearest>" };
         info->kernel = names[kind];
         info->grid = (int)grid.x;
         info->lds_bytes = (int)lds_bytes;
         return hipSuccess;
     }
+    record_name(names[kind]);
     switch (out) {
 #define TSVPP_BR(O)                                                                                                     \
     case O:                                                                                                             \

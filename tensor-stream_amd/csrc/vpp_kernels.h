@@ -177,11 +177,15 @@ struct LaunchDesc {
 // What the last fused launch of this thread was: tsvpp_api.cpp points `g_launch_rec` at a record while it runs launch_fused and, when exactly ONE kernel was
 // launched, keeps the record -- the host function, the grid and the FINAL descriptor -- so that the next call with the same request replays the launch without
 // re-running the selection (round 6: a single-frame launch is host-bound; the selection, its cache lookups and mutexes are ~0.5 us of ~4).
+// The record also carries what tsvpp_debug_last_launch reports (include/tsvpp.h): the launcher's name of the kernel (the spelling tsvpp_describe uses) and what
+// launch_fused decided besides the descriptor -- written only while a record is armed.
 struct LaunchRecord {
     const void *fn = nullptr;
+    const char *name = nullptr;
     dim3 grid, block;
     uint32_t lds = 0;
     int count = 0; // launches seen since the record was armed
+    int mode = 0, out = 0, staged = 0, pass2 = 0; // request mode, output flavour, launch_fused's `staged`, second pass (TSVPP_UYVY / TSVPP_YUV444, else 0)
     LaunchDesc d;
 };
 extern thread_local LaunchRecord *g_launch_rec;
@@ -195,6 +199,11 @@ inline void record_launch(const void *fn, dim3 grid, dim3 block, size_t lds, con
         r->lds = (uint32_t)lds;
         r->d = d;
     }
+}
+// A launcher names the kernel it is about to launch (before TSVPP_LAUNCH): kept for the first launch of an armed record only.
+inline void record_name(const char *name) {
+    LaunchRecord *r = g_launch_rec;
+    if (r && r->count == 0) r->name = name;
 }
 
 // Every fused-kernel launch goes through this: an ordinary in-order launch, or -- LaunchDesc::any_order -- one whose packet does not wait for its predecessors.
@@ -278,6 +287,8 @@ struct LaunchInfo {
     int tx, ty, rpt, dma, staged, lds_bytes, grid, tiles_x, tiles_y;
     int tail; // a second, element-wise launch covers the two-column row tail (dst_w = 4 k + 2)
     int geo;  // the 2x2-tap kernel reads host-built geometry tables instead of computing coordinates
+    int nt;   // LaunchDesc::nt_stores after sel_store_policy (store variant: bit 0 / 1 non-temporal, bit 2 the 4-byte uint8 stores too)
+    int in4;  // LaunchDesc::in_aligned4
 };
 
 // Launches the fused crop+resize+colour kernel.  `vec` selects the 16-byte/4-byte vector

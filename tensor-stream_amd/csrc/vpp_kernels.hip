@@ -983,6 +983,7 @@ __global__ __launch_bounds__(MAX_THREADS) void vpp_color_kernel(const LaunchDesc
             info->grid = (int)(GRID).x;                                                \
             info->lds_bytes = (int)(LDS);                                              \
         } else {                                                                       \
+            tsvpp::record_name(NAME);                                                  \
             TSVPP_LAUNCH(KERNEL, GRID, BLOCK, LDS, stream, d, t);                \
         }                                                                              \
     } while (0)

@@ -172,6 +172,7 @@ hipError_t launch_point_rn(OutKind out, const LaunchDesc &d, const FrameTable &t
             info->lds_bytes = out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16;
             return hipSuccess;
         }
+        record_name("vpp_rep2_kernel<OUT>");
         switch (out) {
 #define TSVPP_REP2(O) case O: TSVPP_LAUNCH((vpp_rep2_kernel<O>), grid, block, 0, stream, d, t); break;
             TSVPP_REP2(O_U8_PLANAR) TSVPP_REP2(O_U8_MERGED) TSVPP_REP2(O_NV12_U8) TSVPP_REP2(O_Y800_U8)
@@ -195,6 +196,7 @@ hipError_t launch_point_rn(OutKind out, const LaunchDesc &d, const FrameTable &t
         info->lds_bytes = out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16;
         return hipSuccess;
     }
+    record_name(name);
     switch (d.r32) {
     case 130: return launch_prn<3, 0>(out, d, t, grid, block, stream);
     case 131: return launch_prn<3, 1>(out, d, t, grid, block, stream);

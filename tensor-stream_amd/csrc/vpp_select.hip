@@ -721,6 +721,10 @@ hipError_t launch_fused(Mode mode, OutKind out, bool vec, const LaunchDesc &din,
         info->staged = staged ? 1 : 0;
         info->tiles_x = d.tiles_x;
         info->tiles_y = d.tiles_y;
+        info->nt = d.nt_stores;
+        info->in4 = d.in_aligned4;
+    } else if (g_launch_rec && g_launch_rec->count == 0) {
+        g_launch_rec->staged = staged ? 1 : 0; // (tsvpp_debug_last_launch)
     }
     auto dispatch = [&](bool v, bool st, LaunchDesc &dd, size_t lds, LaunchInfo *inf) { return launch_mode(mode, out, v, st, dd, t, lds, stream, inf); };
     if (out >= O_COUNT) { // flavours of the streaming kernel alone (O_UYVY_U8, O_YUV444_U8): the caller falls back to two passes

@@ -39,7 +39,8 @@ class Coeffs(ctypes.Structure):
 SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_dims", "tsvpp_out_bytes",
            "tsvpp_channels", "tsvpp_convert", "tsvpp_convert_batch", "tsvpp_prepare", "tsvpp_prepare_batch", "tsvpp_enable_markers", "tsvpp_get_coeffs",
            "tsvpp_set_coeffs", "tsvpp_default_coeffs", "tsvpp_area_pattern", "tsvpp_describe", "tsvpp_strerror", "tsvpp_version",
-           "tsvpp_table_create", "tsvpp_table_destroy", "tsvpp_table_set", "tsvpp_convert_table", "tsvpp_trim", "tsvpp_set_option", "tsvpp_get_option", "tsvpp_consumer_next_stream", "tsvpp_consumer_synchronize"]
+           "tsvpp_table_create", "tsvpp_table_destroy", "tsvpp_table_set", "tsvpp_convert_table", "tsvpp_trim", "tsvpp_set_option", "tsvpp_get_option", "tsvpp_consumer_next_stream", "tsvpp_consumer_synchronize",
+           "tsvpp_debug_last_launch"]
 
 _lib = None
 
@@ -90,6 +91,8 @@ def lib():
     L.tsvpp_default_coeffs.restype = None
     L.tsvpp_area_pattern.argtypes = [ctypes.c_float, vp, i32, ctypes.POINTER(i32)]
     L.tsvpp_describe.argtypes = [pp, i32, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_debug_last_launch.restype = i32
     L.tsvpp_strerror.argtypes = [i32]
     L.tsvpp_strerror.restype = ctypes.c_char_p
     L.tsvpp_version.argtypes = []

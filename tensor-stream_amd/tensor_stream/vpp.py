@@ -301,17 +301,29 @@ class VideoProcessor:
         N.check(self._lib.tsvpp_set_coeffs(self._ctx, ctypes.byref(c)))
 
 
-def describe(params, in_w, in_h, pitch=0, n_frames=64, aligned_outputs=True):
-    """What a convert_batch of this request would launch (stage selection, kernel, workgroup shape, LDS bytes, grid)
-    as a dict -- host logic only, works without a GPU (tsvpp_describe)."""
-    p = params.parameters if isinstance(params, FrameParameters) else params
-    buf = ctypes.create_string_buffer(512)
-    N.check(N.lib().tsvpp_describe(ctypes.byref(p), in_w, in_h, pitch, pitch, n_frames, 1 if aligned_outputs else 0, buf, len(buf)))
+def _parse_selection(text):
     out = {}
-    for item in buf.value.decode().split(" "):
+    for item in text.split(" "):
         k, _, v = item.partition("=")
         out[k] = int(v) if v.lstrip("-").isdigit() else v
     return out
+
+
+def describe(params, in_w, in_h, pitch=0, n_frames=64, aligned_outputs=True, pitch_uv=None):
+    """What a convert_batch of this request would launch (stage selection, kernel, workgroup shape, LDS bytes, grid)
+    as a dict -- host logic only, works without a GPU (tsvpp_describe).  `pitch_uv`: the chroma pitch (default: `pitch`)."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    buf = ctypes.create_string_buffer(512)
+    puv = pitch if pitch_uv is None else pitch_uv
+    N.check(N.lib().tsvpp_describe(ctypes.byref(p), in_w, in_h, pitch, puv, n_frames, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def debug_last_launch():
+    """DEBUG ONLY (TSVPP_DEBUG_KNOBS=1): what this thread's last conversion launched, in describe()'s keys (tsvpp_debug_last_launch)."""
+    buf = ctypes.create_string_buffer(512)
+    N.check(N.lib().tsvpp_debug_last_launch(buf, len(buf)))
+    return _parse_selection(buf.value.decode())
 
 
 def default_coeffs():

@@ -25,7 +25,7 @@ FLAVOURS = [("BGR24", "PLANAR", True), ("RGB24", "MERGED", False), ("RGB24", "PL
 EXTRA = [("Y800", "MERGED", False), ("NV12", "MERGED", False), ("UYVY", "MERGED", False), ("YUV444", "MERGED", False), ("HSV", "MERGED", True)]
 RT = {"NEAREST": 0, "BILINEAR": 1, "BICUBIC": 2, "AREA": 3}
 FCC = {"Y800": 0, "RGB24": 1, "BGR24": 2, "NV12": 3, "UYVY": 4, "YUV444": 5, "HSV": 6}
-KEYS = ("mode", "out", "kernel", "shape", "rpt", "dma", "tiles", "tail", "geo")
+KEYS = ("mode", "out", "kernel", "shape", "rpt", "dma", "tiles", "tail", "geo", "nt")
 
 
 def requests():

@@ -239,6 +239,42 @@ def test_debug_knobs_are_honoured_only_under_the_gate():
     assert forced != base and "gather" in forced
 
 
+def test_debug_last_launch_answers_only_under_the_gate():
+    """tsvpp_debug_last_launch (include/tsvpp.h, debug only): refused without TSVPP_DEBUG_KNOBS=1; under it, a thread that has converted nothing gets
+    TSVPP_ERROR.  What it reports after a conversion is checked on the GPU against tsvpp_describe (tests/test_gpu_dispatch_cover.py)."""
+    import subprocess
+    import sys
+    code = ("import sys, ctypes; sys.path.insert(0, %r); from tensor_stream import _native as N; "
+            "b = ctypes.create_string_buffer(512); print(N.lib().tsvpp_debug_last_launch(b, len(b)), repr(b.value))"
+            % os.path.join(ROOT, "tensor-stream_amd"))
+    def run(env_extra):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("TSVPP_")}
+        env.update(env_extra)
+        p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=120)
+        assert p.returncode == 0, p.stderr[-400:]
+        return p.stdout.strip()
+    assert run({}) == "-2 b''"
+    assert run({"TSVPP_DEBUG_KNOBS": "1"}) == "-3 b''"
+
+
+def test_describe_reports_store_policy_staging_and_input_alignment(native):
+    """describe's nt= / staged= / in4= keys: the store variant after the store policy, LDS staging, dword-aligned input planes."""
+    import tensor_stream as ts
+    fp = lambda w, h, **kw: ts.FrameParameters(width=w, height=h, **kw)
+    # colour-only kernel, planar uint8, rows a multiple of 64 bytes: non-temporal 4-byte stores too (bit 2)
+    d = ts.describe(fp(0, 0, pixel_format=2, planes_pos=0), 1920, 1080, pitch=2048)
+    assert (d["kernel"], d["nt"], d["staged"], d["in4"]) == ("vpp_color_kernel<OUT>", 5, 1, 1)
+    # planar fp32, 1366 columns: plain stores (rows are no multiple of 64 bytes)
+    d = ts.describe(fp(1366, 768, resize_type=1, pixel_format=2, planes_pos=0, normalization=True), 1920, 1080, pitch=2048)
+    assert d["nt"] == 0 and d["staged"] == 1
+    # an odd crop origin: planes are not dword aligned
+    d = ts.describe(ts.FrameParameters(width=640, height=360, crop_coords=(1, 0, 1281, 720), resize_type=1, pixel_format=2, planes_pos=0), 1920, 1080, pitch=2048)
+    assert d["in4"] == 0
+    # UYVY behind a resize (second pass): the intermediate is written with plain stores
+    d = ts.describe(fp(1366, 768, resize_type=1, pixel_format=4), 1920, 1080, pitch=2048)
+    assert d.get("pass2") == "fmt_uyvy" and d["nt"] == 0
+
+
 def test_adapter_compiles_against_a_libavutil_frame_header():
     """the TSVPP_HAVE_LIBAV branch of cpp/VideoProcessor.h (AVFrame from <libavutil/frame.h>) goes through hipcc -- against a vendored
     compile-check declaration (cpp/compat/libavutil/frame.h), objects only."""

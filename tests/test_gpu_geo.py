@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import synth_nv12, knob_run
+from util import distinct_frames, frame_k, knob_run, synth_nv12
 
 pytestmark = pytest.mark.gpu
 BILINEAR, AREA = 1, 3
@@ -61,12 +61,13 @@ def check(v, oracle, y, uv, w, dst, n=1, geo=1, **kw):
     if n == 1:
         got = v.Convert(ty, tuv, fp, width=w)
     else:
-        got = v.convert_batch([ty] * n, [tuv] * n, fp, width=w)
+        got = v.convert_batch(*distinct_frames(ty, tuv, n), fp, width=w)
     torch.cuda.synchronize()
-    ref, _, _ = oracle.convert(y, uv, crop=crop, dst=dst, resize_type=kw.get("rt", BILINEAR), fourcc=kw.get("fourcc", 2), planes=kw.get("planes", 0),
-                               normalization=kw.get("norm", False), nthreads=8, width=w)
-    frames = [got] if n == 1 else [got[0], got[n // 2], got[n - 1]]
-    for g in frames:
+    ks = [0] if n == 1 else [0, n // 2, n - 1]  # (the batch holds n distinct frames: each compared with its own reference)
+    refs = [oracle.convert(frame_k(y, k), frame_k(uv, k), crop=crop, dst=dst, resize_type=kw.get("rt", BILINEAR), fourcc=kw.get("fourcc", 2),
+                           planes=kw.get("planes", 0), normalization=kw.get("norm", False), nthreads=8, width=w)[0] for k in ks]
+    frames = [got] if n == 1 else [got[k] for k in ks]
+    for g, ref in zip(frames, refs):
         g = g.cpu().numpy().ravel()
         assert g.size == ref.size
         bad = np.flatnonzero(g.view(np.uint8) != ref.view(np.uint8))
@@ -128,10 +129,10 @@ def test_geo_tall_thread_tiles_and_knob_off(oracle):
         with _Env(TSVPP_R32="0", **env):
             v = tensor_stream.VideoProcessor(device=0)
         fp = params((1280, 720))
-        got = v.convert_batch([torch.from_numpy(y).cuda()] * 64, [torch.from_numpy(uv).cuda()] * 64, fp, width=1920)
+        got = v.convert_batch(*distinct_frames(torch.from_numpy(y).cuda(), torch.from_numpy(uv).cuda(), 64), fp, width=1920)
         torch.cuda.synchronize()
-        ref, _, _ = oracle.convert(y, uv, dst=(1280, 720), resize_type=BILINEAR, fourcc=2, planes=0, normalization=False, nthreads=8, width=1920)
         for f in (0, 63):
+            ref, _, _ = oracle.convert(frame_k(y, f), frame_k(uv, f), dst=(1280, 720), resize_type=BILINEAR, fourcc=2, planes=0, normalization=False, nthreads=8, width=1920)
             assert np.array_equal(got[f].cpu().numpy().ravel(), ref), env
         v.Close()
 
@@ -191,9 +192,10 @@ def test_geo_fuzz(gvpp, oracle, chunk):
         n = int(rng.choice([1, 1, 3]))
         y, uv = synth_nv12(w, h, seed=7000 + 100 * chunk + k, pitch=pitch)
         fp = ts.FrameParameters(width=dst[0], height=dst[1], crop_coords=crop, resize_type=rt, pixel_format=fourcc, planes_pos=planes, normalization=norm)
-        ref, _, _ = oracle.convert(y, uv, crop=crop, dst=dst, resize_type=rt, fourcc=fourcc, planes=planes, normalization=norm, nthreads=4, width=w)
+        # (a batch holds n distinct frames: its last one is compared)
+        ref, _, _ = oracle.convert(frame_k(y, n - 1), frame_k(uv, n - 1), crop=crop, dst=dst, resize_type=rt, fourcc=fourcc, planes=planes, normalization=norm, nthreads=4, width=w)
         ty, tuv = torch.from_numpy(y).cuda(), torch.from_numpy(uv).cuda()
-        got = gvpp.Convert(ty, tuv, fp, width=w) if n == 1 else gvpp.convert_batch([ty] * n, [tuv] * n, fp, width=w)[n - 1]
+        got = gvpp.Convert(ty, tuv, fp, width=w) if n == 1 else gvpp.convert_batch(*distinct_frames(ty, tuv, n), fp, width=w)[n - 1]
         torch.cuda.synchronize()
         g = got.cpu().numpy().ravel()
         assert g.size == ref.size, (w, h, pitch, crop, dst, rt, fourcc, planes, norm, n)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import synth_nv12, knob_run
+from util import distinct_frames, frame_k, knob_run, synth_nv12
 
 pytestmark = pytest.mark.gpu
 NEAREST, BILINEAR, BICUBIC, AREA = 0, 1, 2, 3
@@ -26,10 +26,10 @@ def check(vpp, oracle, y, uv, w, fourcc=RGB24, planes=0, crop=(0, 0, 0, 0), n=1,
         k = ts.describe(fp, w, y.shape[0], pitch=y.shape[1], n_frames=n)["kernel"]
         assert k.startswith("vpp_bilinear_up2_kernel") == up2, (k, w, y.shape, dst, crop, fourcc, norm)
     ty, tuv = torch.from_numpy(y).cuda(), torch.from_numpy(uv).cuda()
-    got = vpp.Convert(ty, tuv, fp, width=w) if n == 1 else vpp.convert_batch([ty] * n, [tuv] * n, fp, width=w)
+    got = vpp.Convert(ty, tuv, fp, width=w) if n == 1 else vpp.convert_batch(*distinct_frames(ty, tuv, n), fp, width=w)
     torch.cuda.synchronize()
-    ref, _, _ = oracle.convert(y, uv, crop=crop, dst=dst, resize_type=rt, fourcc=fourcc, planes=planes, normalization=norm, nthreads=8, width=w)
-    for g in ([got] if n == 1 else [got[0], got[n - 1]]):
+    refs = [oracle.convert(frame_k(y, k), frame_k(uv, k), crop=crop, dst=dst, resize_type=rt, fourcc=fourcc, planes=planes, normalization=norm, nthreads=8, width=w)[0] for k in ([0] if n == 1 else [0, n - 1])]  # (the batch holds n distinct frames)
+    for g, ref in zip([got] if n == 1 else [got[0], got[n - 1]], refs):
         g = g.cpu().numpy().ravel()
         assert g.size == ref.size
         bad = np.flatnonzero(g.view(np.uint8) != ref.view(np.uint8))

@@ -20,6 +20,17 @@ def synth_nv12(w, h, seed, pitch=None):
     return y, uv
 
 
+def frame_k(plane, k):
+    """Frame k of a batch built by distinct_frames, on the host: every byte of `plane` + 37 k (mod 256)."""
+    return ((plane.astype(np.uint16) + 37 * k) & 255).astype(np.uint8)
+
+
+def distinct_frames(ty, tuv, n):
+    """n DISTINCT frames on the device from one (frame k: every byte + 37 k mod 256, see frame_k; no two frames of a batch <= 256 share a pixel):
+    a kernel that reads frame 0 for every frame, or writes frame k to another frame's slot, fails the comparison of the last frame."""
+    return [ty + (37 * k) % 256 for k in range(n)], [tuv + (37 * k) % 256 for k in range(n)]
+
+
 def coverage_frame():
     """4096x4096 NV12 frame that enumerates all 2^24 (Y,U,V) triples: each of the 65536 (U,V) pairs
     owns 64 consecutive 2x2 blocks whose 256 luma samples are 0..255."""

@@ -29,15 +29,20 @@ using namespace tsvpp;
 
 namespace {
 
-struct AreaTable {
-    float *dev = nullptr;
+// What the kernel selection needs to know about the AREA weight table of one axis: derived from the scale alone, on the host (area_axis).
+struct AreaAxis {
     int rows = 0, taps = 0;
-    AreaQRow *qdev = nullptr; // integer form, only if every weight is k / 2^shift and taps <= 8
-    int shift = -1;
-    int uniform_sum = 0;      // > 0: every row of the integer table has this weight sum
-    float *dev4 = nullptr;    // the float rows zero-padded to a multiple of four taps
     int nk = 0;               // taps4 = 4 * nk
     int ones_end = 0;         // taps 1 .. ones_end - 1 weigh exactly 1.0f in every row (the streaming kernel multiplies nothing there)
+    bool dyadic = false;      // an integer form exists: every weight is k / 2^shift and taps <= 8
+    int shift = -1;
+    int uniform_sum = 0;      // > 0: every row of the integer table has this weight sum
+};
+// ... and the table itself on a device (get_area_table; tsvpp_describe fills in stand-ins)
+struct AreaTable : AreaAxis {
+    float *dev = nullptr;
+    AreaQRow *qdev = nullptr; // integer form, only if `dyadic` (and its upload succeeded)
+    float *dev4 = nullptr;    // the float rows zero-padded to a multiple of four taps
     std::shared_ptr<std::vector<float>> host4; // host copy of dev4 (divisor tables of the float AREA kernels)
 };
 
@@ -114,6 +119,20 @@ bool build_area_rows(float scale, std::vector<float> &tab, int &rows, int &taps)
         rows++;
     }
     return rows > 0;
+}
+
+// The axis record of a scale; `tab` / `q` receive the float rows and, if dyadic, the integer rows (for the uploads of get_area_table).
+bool area_axis(float scale, AreaAxis &a, std::vector<float> &tab, std::vector<AreaQRow> &q) {
+    if (!build_area_rows(scale, tab, a.rows, a.taps)) return false;
+    a.nk = (a.taps + 3) / 4;
+    a.ones_end = area_ones_end(tab, a.rows, a.taps);
+    a.dyadic = quantise_area_rows(tab, a.rows, a.taps, q, a.shift);
+    if (a.dyadic) {
+        a.uniform_sum = q[0].sum;
+        for (const AreaQRow &row : q)
+            if (row.sum != q[0].sum) a.uniform_sum = 0;
+    }
+    return true;
 }
 
 // Is every interpolation weight of this request zero?  (odd integer ratios; then BILINEAR and
@@ -214,20 +233,14 @@ struct Plan {
     bool f32 = false;
 };
 
-} // namespace
-
-struct tsvpp_ctx {
-    int device = 0;
-    std::vector<std::pair<std::string, hipStream_t>> streams;
-    std::vector<hipStream_t> streams2; // TSVPP_OPT_INPUTS_READY: a consumer's second stream (created on first use), same index as `streams`
-    std::vector<uint8_t> turn;         // ... and which of the two its next conversion takes
-    std::mutex stream_mu;
-    tsvpp_coeffs coeffs;
-    std::map<uint32_t, AreaTable> area; // keyed by the bit pattern of the float scale
-    std::map<uint64_t, float *> area_div; // divisor tables, keyed by both scales' bit patterns (null: too large, not built)
+// Everything of a context that the launch descriptor is filled from (fill_desc): the tuning knobs (read_env_knobs) and the two options the API sets that
+// travel in the descriptor.  Plain data: tsvpp_describe makes one of its own, without a context.
+struct Knobs {
+    tsvpp_coeffs coeffs;                // tsvpp_set_coeffs
+    int color_g = 0;                    // TSVPP_OPT_COLOR_G_TERM
     int force_gather = 0;               // TSVPP_FORCE_GATHER=1: always use the global-gather kernel (A/B, tests)
     int nt_stores = -1, tile_order = 0, shape_tx = 0, shape_ty = 0; // TSVPP_NT, TSVPP_TILE_ORDER, TSVPP_SHAPE=tx,ty
-    int num_cus = 256;
+    int num_cus = 256;                  // compute units of the device (tsvpp_create reads it; 256 without a device)
     // dyadic AREA reads straight from global memory from this ratio on (both axes); below it the LDS kernel wins
     // (measured after its VGPR fix: 2x 501 k vs 368 k fps, 3x 743 k vs 621 k, 4x 162 k vs 251 k)
     float area_direct_min = 3.5f;   // TSVPP_AREA_DIRECT_MIN
@@ -257,7 +270,23 @@ struct tsvpp_ctx {
     int point_rn = 1;               // TSVPP_POINT_RN: streaming point sampler at exact integer ratios 3 / 4 / 5 (vpp_point_rn.hip; 0: the LDS point kernel)
     int bilinear_rows_waves = 0;    // TSVPP_BILINEAR_ROWS_WAVES: its waves per workgroup (1 / 2 / 4; 0 = automatic)
     int geo_pref = 1;               // TSVPP_GEO: host-built geometry tables for the 2x2-tap kernel's window tiles (1: where measured to win, 2: wherever they apply)
-    GeoCache *geo = nullptr;        // ... their device copies, one set per (request geometry, tile shape)
+    int replay = 1;                 // TSVPP_REPLAY=0 (debug knob): every call runs the full selection
+    int debug = 0;                  // read under TSVPP_DEBUG_KNOBS=1: every conversion keeps its launch record for tsvpp_debug_last_launch
+    Knobs() { tsvpp_default_coeffs(&coeffs); }
+};
+
+} // namespace
+
+struct tsvpp_ctx {
+    int device = 0;
+    std::vector<std::pair<std::string, hipStream_t>> streams;
+    std::vector<hipStream_t> streams2; // TSVPP_OPT_INPUTS_READY: a consumer's second stream (created on first use), same index as `streams`
+    std::vector<uint8_t> turn;         // ... and which of the two its next conversion takes
+    std::mutex stream_mu;
+    Knobs knobs;
+    std::map<uint32_t, AreaTable> area; // keyed by the bit pattern of the float scale
+    std::map<uint64_t, float *> area_div; // divisor tables, keyed by both scales' bit patterns
+    GeoCache *geo = nullptr; // device copies of the geometry tables (Knobs::geo_pref), one set per (request geometry, tile shape)
     std::mutex area_mu;
     // NV12 intermediates of the two-pass formats (UYVY / YUV444 with a resize): one grow-only slot per stream.  A slot's
     // mutex is held while BOTH passes of a call are enqueued, so calls that share a stream (typically NULL) cannot
@@ -277,9 +306,6 @@ struct tsvpp_ctx {
     // something a finished launch descriptor depends on changes or may be freed: tsvpp_set_coeffs, tsvpp_set_option, tsvpp_enable_markers, tsvpp_trim.
     uint64_t id = 0;
     std::atomic<uint64_t> epoch{ 1 };
-    int replay = 1; // TSVPP_REPLAY=0 (debug knob): every call runs the full selection
-    int debug = 0;  // created under TSVPP_DEBUG_KNOBS=1: every conversion keeps its launch record for tsvpp_debug_last_launch
-    int color_g = 0; // TSVPP_OPT_COLOR_G_TERM
     int unsafe_coeffs = 0; // TSVPP_OPT_UNSAFE_COEFFS: tsvpp_set_coeffs accepts a block that differs from the defaults
     std::set<struct tsvpp_table *> tables; // live frame tables: released with the context if the caller destroys it first
     std::mutex tables_mu;
@@ -370,40 +396,40 @@ int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl) {
 // set WITHOUT the gate is reported once per process and ignored.
 struct KnobRow {
     const char *name;
-    int tsvpp_ctx::*field;
+    int Knobs::*field;
 };
 const KnobRow kKnobs[] = {
-    { "TSVPP_FORCE_GATHER", &tsvpp_ctx::force_gather }, { "TSVPP_NT", &tsvpp_ctx::nt_stores }, // NT: 0 plain, 1 nt, 2 sc1; default -1 = per kernel
-    { "TSVPP_DMA", &tsvpp_ctx::dma }, { "TSVPP_GEO", &tsvpp_ctx::geo_pref }, { "TSVPP_R32", &tsvpp_ctx::r32 }, { "TSVPP_RPT", &tsvpp_ctx::rpt },
-    { "TSVPP_BICUBIC_INT", &tsvpp_ctx::bicubic_int }, { "TSVPP_BICUBIC_COLS", &tsvpp_ctx::bicubic_cols }, { "TSVPP_BILINEAR_ROWS", &tsvpp_ctx::bilinear_rows },
-    { "TSVPP_BICUBIC_U8X", &tsvpp_ctx::bicubic_u8x }, { "TSVPP_POINT_RN", &tsvpp_ctx::point_rn },
-    { "TSVPP_LDS_KB", &tsvpp_ctx::lds_kb }, // LDS budget of the staged kernels in KiB (tests: a budget nothing fits)
-    { "TSVPP_BILINEAR_ROWS_WAVES", &tsvpp_ctx::bilinear_rows_waves }, { "TSVPP_BICUBIC_ROWS", &tsvpp_ctx::bicubic_rows }, { "TSVPP_AREA_STREAM", &tsvpp_ctx::area_stream },
-    { "TSVPP_BICUBIC_DMA", &tsvpp_ctx::bicubic_dma }, { "TSVPP_AREA_BOX", &tsvpp_ctx::area_box }, { "TSVPP_BILINEAR_INT", &tsvpp_ctx::bilinear_int },
-    { "TSVPP_AREA_DIVTAB", &tsvpp_ctx::area_divtab }, { "TSVPP_AREA_COLS", &tsvpp_ctx::area_cols },
-    { "TSVPP_TAIL_SHIFT", &tsvpp_ctx::tail_shift },         // 0: the two-column tail launch of rounds 1-3 (A/B)
-    { "TSVPP_AREA_COLS_ROWS", &tsvpp_ctx::area_cols_rows }, // 8 | 32: tile height of the column-per-lane AREA kernel (default: by tap count and launch size)
-    { "TSVPP_TILE_ORDER", &tsvpp_ctx::tile_order }, { "TSVPP_REPLAY", &tsvpp_ctx::replay },
+    { "TSVPP_FORCE_GATHER", &Knobs::force_gather }, { "TSVPP_NT", &Knobs::nt_stores }, // NT: 0 plain, 1 nt, 2 sc1; default -1 = per kernel
+    { "TSVPP_DMA", &Knobs::dma }, { "TSVPP_GEO", &Knobs::geo_pref }, { "TSVPP_R32", &Knobs::r32 }, { "TSVPP_RPT", &Knobs::rpt },
+    { "TSVPP_BICUBIC_INT", &Knobs::bicubic_int }, { "TSVPP_BICUBIC_COLS", &Knobs::bicubic_cols }, { "TSVPP_BILINEAR_ROWS", &Knobs::bilinear_rows },
+    { "TSVPP_BICUBIC_U8X", &Knobs::bicubic_u8x }, { "TSVPP_POINT_RN", &Knobs::point_rn },
+    { "TSVPP_LDS_KB", &Knobs::lds_kb }, // LDS budget of the staged kernels in KiB (tests: a budget nothing fits)
+    { "TSVPP_BILINEAR_ROWS_WAVES", &Knobs::bilinear_rows_waves }, { "TSVPP_BICUBIC_ROWS", &Knobs::bicubic_rows }, { "TSVPP_AREA_STREAM", &Knobs::area_stream },
+    { "TSVPP_BICUBIC_DMA", &Knobs::bicubic_dma }, { "TSVPP_AREA_BOX", &Knobs::area_box }, { "TSVPP_BILINEAR_INT", &Knobs::bilinear_int },
+    { "TSVPP_AREA_DIVTAB", &Knobs::area_divtab }, { "TSVPP_AREA_COLS", &Knobs::area_cols },
+    { "TSVPP_TAIL_SHIFT", &Knobs::tail_shift },         // 0: the two-column tail launch of rounds 1-3 (A/B)
+    { "TSVPP_AREA_COLS_ROWS", &Knobs::area_cols_rows }, // 8 | 32: tile height of the column-per-lane AREA kernel (default: by tap count and launch size)
+    { "TSVPP_TILE_ORDER", &Knobs::tile_order }, { "TSVPP_REPLAY", &Knobs::replay },
 };
 // `report`: name the knobs that took effect on stderr (tsvpp_create; tsvpp_describe's dry runs stay silent)
-void read_env_knobs(tsvpp_ctx *ctx, bool report = false) {
+void read_env_knobs(Knobs &kn, bool report = false) {
     const char *gate = std::getenv("TSVPP_DEBUG_KNOBS");
     const bool on = gate && std::atoi(gate) != 0;
     std::string seen;
     auto note = [&](const char *name, const char *val) { seen += std::string(seen.empty() ? "" : " ") + name + "=" + val; };
-    ctx->debug = on ? 1 : 0;
+    kn.debug = on ? 1 : 0;
     for (const KnobRow &k : kKnobs)
         if (const char *e = std::getenv(k.name)) {
             note(k.name, e);
-            if (on) ctx->*(k.field) = std::atoi(e);
+            if (on) kn.*(k.field) = std::atoi(e);
         }
     if (const char *e = std::getenv("TSVPP_AREA_DIRECT_MIN")) {
         note("TSVPP_AREA_DIRECT_MIN", e);
-        if (on) ctx->area_direct_min = (float)std::atof(e);
+        if (on) kn.area_direct_min = (float)std::atof(e);
     }
     if (const char *e = std::getenv("TSVPP_SHAPE")) {
         note("TSVPP_SHAPE", e);
-        if (on) std::sscanf(e, "%d,%d", &ctx->shape_tx, &ctx->shape_ty);
+        if (on) std::sscanf(e, "%d,%d", &kn.shape_tx, &kn.shape_ty);
     }
     if (seen.empty()) return;
     if (on) {
@@ -415,7 +441,7 @@ void read_env_knobs(tsvpp_ctx *ctx, bool report = false) {
 }
 
 // The part of the launch descriptor that depends only on the request and the knobs.
-void fill_desc(const tsvpp_ctx *ctx, const Plan &pl, int pitch_y, int pitch_uv, LaunchDesc &d) {
+void fill_desc(const Knobs &kn, GeoCache *geo, const Plan &pl, int pitch_y, int pitch_uv, LaunchDesc &d) {
     std::memset(&d, 0, sizeof(d));
     d.src_w = pl.src_w;
     d.src_h = pl.src_h;
@@ -429,48 +455,90 @@ void fill_desc(const tsvpp_ctx *ctx, const Plan &pl, int pitch_y, int pitch_uv, 
     d.point_kind = pl.point_kind;
     d.wx_zero = pl.wx_zero;
     d.wy_zero = pl.wy_zero;
-    d.k = ctx->coeffs;
-    d.color_g = ctx->color_g;
-    d.force_gather = ctx->force_gather;
-    d.nt_stores = ctx->nt_stores;
-    d.tile_order = ctx->tile_order;
-    d.shape_tx = ctx->shape_tx;
-    d.shape_ty = ctx->shape_ty;
-    d.dma = ctx->dma;
-    d.rpt_pref = ctx->rpt;
-    d.area_direct_min = ctx->area_direct_min;
-    d.area_direct_fmin = ctx->area_direct_fmin;
-    d.bicubic_int_pref = ctx->bicubic_int;
-    d.bicubic_cols_pref = ctx->bicubic_cols;
-    d.bc_rows = ctx->bicubic_rows;
-    d.area_stream_pref = ctx->area_stream;
-    d.as_rows = ctx->area_stream_rows;
-    d.as_min_taps = ctx->area_stream_min_taps;
-    d.bc_dma_pref = ctx->bicubic_dma;
-    d.area_box_pref = ctx->area_box;
+    d.k = kn.coeffs;
+    d.color_g = kn.color_g;
+    d.force_gather = kn.force_gather;
+    d.nt_stores = kn.nt_stores;
+    d.tile_order = kn.tile_order;
+    d.shape_tx = kn.shape_tx;
+    d.shape_ty = kn.shape_ty;
+    d.dma = kn.dma;
+    d.rpt_pref = kn.rpt;
+    d.area_direct_min = kn.area_direct_min;
+    d.area_direct_fmin = kn.area_direct_fmin;
+    d.bicubic_int_pref = kn.bicubic_int;
+    d.bicubic_cols_pref = kn.bicubic_cols;
+    d.bc_rows = kn.bicubic_rows;
+    d.area_stream_pref = kn.area_stream;
+    d.as_rows = kn.area_stream_rows;
+    d.as_min_taps = kn.area_stream_min_taps;
+    d.bc_dma_pref = kn.bicubic_dma;
+    d.area_box_pref = kn.area_box;
     d.w_dyadic = pl.w_dyadic;
-    d.bil_int_pref = ctx->bilinear_int;
-    d.u8_xchg = ctx->u8_xchg;
-    d.bil_win_pref = ctx->bilinear_win;
-    d.area2_pref = ctx->area2;
-    d.lds_budget_kb = ctx->lds_kb;
-    d.area_cols_pref = ctx->area_cols;
-    d.area_cols_rows = ctx->area_cols_rows;
-    d.last_col0 = ctx->tail_shift ? 0 : -1; // (launch_fused decides; < 0 = not allowed)
-    d.num_cus = ctx->num_cus;
-    d.geo_pref = ctx->geo_pref;
-    d.r32_pref = ctx->r32;
-    d.bil_rows_pref = ctx->bilinear_rows;
-    d.point_rn_pref = ctx->point_rn;
-    d.bc_u8x_pref = ctx->bicubic_u8x;
-    d.br_waves = ctx->bilinear_rows_waves; // (forced; launch_fused chooses)
-    d.geo_cache = ctx->geo;
+    d.bil_int_pref = kn.bilinear_int;
+    d.u8_xchg = kn.u8_xchg;
+    d.bil_win_pref = kn.bilinear_win;
+    d.area2_pref = kn.area2;
+    d.lds_budget_kb = kn.lds_kb;
+    d.area_cols_pref = kn.area_cols;
+    d.area_cols_rows = kn.area_cols_rows;
+    d.last_col0 = kn.tail_shift ? 0 : -1; // (launch_fused decides; < 0 = not allowed)
+    d.num_cus = kn.num_cus;
+    d.geo_pref = kn.geo_pref;
+    d.r32_pref = kn.r32;
+    d.bil_rows_pref = kn.bilinear_rows;
+    d.point_rn_pref = kn.point_rn;
+    d.bc_u8x_pref = kn.bicubic_u8x;
+    d.br_waves = kn.bilinear_rows_waves; // (forced; launch_fused chooses)
+    d.geo_cache = geo;
 }
 
 // Integer box sums are exact (and equal to the reference's float accumulation) while 255 * sum(wx) * sum(wy) stays
 // below 2^24; one divisor for the whole frame allows an exact integer division by a constant in the kernel.
 bool dyadic_usable(float xr, float yr, int shift_x, int shift_y) {
     return (double)255 * ((double)xr * (1 << shift_x) + 1) * ((double)yr * (1 << shift_y) + 1) < 16777216.0;
+}
+
+// Does an AREA down-scale with these tables want the divisor table of the float-weight kernels (get_area_div)?  Not where the integer tables exist, and
+// tables above 2^18 entries are not built (the kernel then sums the weights itself).
+bool wants_area_div(const Knobs &kn, const AreaTable &tx, const AreaTable &ty) {
+    return !(tx.qdev && ty.qdev) && kn.area_divtab && (long)tx.rows * ty.rows <= (1L << 18);
+}
+
+// The AREA down-scale fields of the launch descriptor.  "Dyadic" means that both integer tables are there (qdev); `div` may be null whatever wants_area_div said.
+void set_area_desc(const Plan &pl, const AreaTable &tx, const AreaTable &ty, const float *div, LaunchDesc &d) {
+    d.patx = tx.dev;
+    d.nx = tx.rows;
+    d.rx = tx.taps;
+    d.paty = ty.dev;
+    d.ny = ty.rows;
+    d.ry = ty.taps;
+    d.patx4 = tx.dev4;
+    d.nkx = tx.nk;
+    d.paty4 = ty.dev4;
+    d.nky = ty.nk;
+    d.as_ones_x = tx.ones_end;
+    d.area_div = div;
+    if (tx.qdev && ty.qdev && dyadic_usable(pl.xr, pl.yr, tx.shift, ty.shift)) {
+        d.qx = tx.qdev;
+        d.qy = ty.qdev;
+        d.box_rx = (tx.rows == 1 && tx.shift == 0 && tx.uniform_sum == tx.taps) ? tx.taps : 0; // one row of all ones
+        d.box_ry = (ty.rows == 1 && ty.shift == 0 && ty.uniform_sum == ty.taps) ? ty.taps : 0;
+        // one divisor for the whole frame -> exact integer division by a constant in the kernel
+        if (tx.uniform_sum > 0 && ty.uniform_sum > 0 && (long)tx.uniform_sum * ty.uniform_sum < 4096)
+            d.area_rcp = 1.0f / (float)(tx.uniform_sum * ty.uniform_sum);
+    }
+}
+
+// A host vector as a fresh device allocation; on failure nothing stays allocated and `dev` is null (the runtime's last error is left to the caller).
+template <class T> hipError_t upload(const std::vector<T> &v, T *&dev) {
+    dev = nullptr;
+    hipError_t e = hipMalloc((void **)&dev, v.size() * sizeof(T));
+    if (e == hipSuccess && (e = hipMemcpy(dev, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)) != hipSuccess) {
+        (void)hipFree(dev);
+        dev = nullptr;
+    }
+    return e;
 }
 
 int get_area_table(tsvpp_ctx *ctx, float scale, AreaTable &out) {
@@ -483,40 +551,20 @@ int get_area_table(tsvpp_ctx *ctx, float scale, AreaTable &out) {
         return TSVPP_OK;
     }
     std::vector<float> tab;
-    AreaTable t;
-    if (!build_area_rows(scale, tab, t.rows, t.taps)) return TSVPP_UNSUPPORTED;
-    hipError_t e = hipMalloc((void **)&t.dev, tab.size() * sizeof(float));
-    if (e != hipSuccess) return (int)e;
-    e = hipMemcpy(t.dev, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(t.dev);
-        return (int)e;
-    }
-    {
-        t.nk = (t.taps + 3) / 4;
-        t.ones_end = area_ones_end(tab, t.rows, t.taps);
-        std::vector<float> pad((size_t)t.rows * 4 * t.nk, 0.0f);
-        for (int r = 0; r < t.rows; r++)
-            for (int k = 0; k < t.taps; k++) pad[(size_t)r * 4 * t.nk + k] = tab[(size_t)r * t.taps + k];
-        t.host4 = std::make_shared<std::vector<float>>(pad);
-        if (hipMalloc((void **)&t.dev4, pad.size() * sizeof(float)) != hipSuccess ||
-            hipMemcpy(t.dev4, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(t.dev);
-            if (t.dev4) (void)hipFree(t.dev4);
-            return TSVPP_ERROR;
-        }
-    }
     std::vector<AreaQRow> q;
-    if (quantise_area_rows(tab, t.rows, t.taps, q, t.shift)) {
-        t.uniform_sum = q[0].sum;
-        for (const AreaQRow &row : q)
-            if (row.sum != q[0].sum) t.uniform_sum = 0;
-        if (hipMalloc((void **)&t.qdev, q.size() * sizeof(AreaQRow)) == hipSuccess &&
-            hipMemcpy(t.qdev, q.data(), q.size() * sizeof(AreaQRow), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(t.qdev);
-            t.qdev = nullptr;
-        }
+    AreaTable t;
+    if (!area_axis(scale, t, tab, q)) return TSVPP_UNSUPPORTED;
+    const hipError_t e = upload(tab, t.dev);
+    if (e != hipSuccess) return (int)e;
+    std::vector<float> pad((size_t)t.rows * 4 * t.nk, 0.0f);
+    for (int r = 0; r < t.rows; r++)
+        for (int k = 0; k < t.taps; k++) pad[(size_t)r * 4 * t.nk + k] = tab[(size_t)r * t.taps + k];
+    t.host4 = std::make_shared<std::vector<float>>(pad);
+    if (upload(pad, t.dev4) != hipSuccess) {
+        (void)hipFree(t.dev);
+        return TSVPP_ERROR;
     }
+    if (t.dyadic) (void)upload(q, t.qdev); // (a failed upload leaves it null: the request then runs the float-weight kernels)
     ctx->area[key] = t;
     out = t;
     return TSVPP_OK;
@@ -526,8 +574,8 @@ int get_area_table(tsvpp_ctx *ctx, float scale, AreaTable &out) {
 // accumulates `divide += weight` next to `colorSum = fma(data, weight, colorSum)` (src/Resize.cu:160-178), and the sum depends
 // only on the column's and the row's weight patterns -- nx * ny distinct values per geometry.  Built here with the kernel's
 // own fp32 operations in the kernel's order (product rounded to fp32, then added; rows outer, the 4 * nk zero-padded taps
-// inner), so the kernel can load the divisor instead of spending one add per tap and lane on it.  Tables above 2^18 entries
-// are not built (the kernel then sums the weights itself).
+// inner), so the kernel can load the divisor instead of spending one add per tap and lane on it.  Asked for only where
+// wants_area_div says so.
 #pragma clang fp contract(off)
 // The table is an optimisation, never a requirement (the kernels sum the weights themselves when it is null): while `stream`
 // is capturing, or when the allocation fails, nothing is built or cached and the call still succeeds -- a first conversion
@@ -545,7 +593,7 @@ int get_area_div(tsvpp_ctx *ctx, float xr, float yr, const AreaTable &tx, const 
         return TSVPP_OK;
     }
     float *dev = nullptr;
-    if (tx.host4 && ty.host4 && (long)tx.rows * ty.rows <= (1L << 18)) {
+    if (tx.host4 && ty.host4) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         // (the NULL stream is never queried: asking the legacy stream while another stream captures in global mode invalidates that capture)
         if (stream && hipStreamIsCapturing(stream, &cap) != hipSuccess) (void)hipGetLastError();
@@ -565,19 +613,26 @@ int get_area_div(tsvpp_ctx *ctx, float xr, float yr, const AreaTable &tx, const 
                 tab[(size_t)jx * ty.rows + iy] = div;
             }
         }
-        if (hipMalloc((void **)&dev, tab.size() * sizeof(float)) != hipSuccess) {
+        if (upload(tab, dev) != hipSuccess) {
             (void)hipGetLastError();
             return TSVPP_OK; // out stays null
-        }
-        if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(dev);
-            return TSVPP_OK;
         }
     }
     ctx->area_div[key] = dev;
     out = dev;
     return TSVPP_OK;
+}
+
+// An AREA down-scale's tables -- both axes and, where wanted, the divisor table -- into its descriptor: tsvpp_prepare_batch builds them ahead, a conversion looks them up.
+int area_desc(tsvpp_ctx *ctx, const Plan &pl, hipStream_t stream, LaunchDesc &d) {
+    if (pl.mode != M_AREA_DOWN) return TSVPP_OK;
+    AreaTable tx, ty;
+    const float *div = nullptr;
+    int sts = get_area_table(ctx, pl.xr, tx);
+    if (sts == TSVPP_OK) sts = get_area_table(ctx, pl.yr, ty);
+    if (sts == TSVPP_OK && wants_area_div(ctx->knobs, tx, ty)) sts = get_area_div(ctx, pl.xr, pl.yr, tx, ty, div, stream);
+    if (sts == TSVPP_OK) set_area_desc(pl, tx, ty, div, d);
+    return sts;
 }
 
 // Selects the context's device for the duration of one API call and restores the caller's on exit (as torch's
@@ -670,6 +725,63 @@ size_t plan_moved_bytes(const Plan &pl) {
 
 bool needs_scratch(const Plan &pl) { return (pl.fourcc == TSVPP_UYVY || pl.fourcc == TSVPP_YUV444) && pl.mode != M_NONE; }
 
+// crop = pointer arithmetic (reference src/Crop.cu:10-18: luma at (left + j, top + i), chroma
+// row top/2 + i/2, chroma byte (j & ~1) + left -- an odd `left` therefore swaps U and V,
+// exactly as it does in the reference)
+struct CropOff { size_t y, uv; };
+CropOff crop_offsets(const Plan &pl, int pitch_y, int pitch_uv) {
+    return CropOff{ (size_t)pl.off_y * (size_t)pitch_y + (size_t)pl.off_x, (size_t)(pl.off_y / 2) * (size_t)pitch_uv + (size_t)pl.off_x };
+}
+// LaunchDesc::in_aligned4 for one frame: `y` / `uv` are its crop-adjusted plane addresses (the bare crop offsets where the frame itself is taken as aligned)
+bool planes_aligned4(int pitch_y, int pitch_uv, uintptr_t y, uintptr_t uv) { return pitch_y % 4 == 0 && pitch_uv % 4 == 0 && y % 4 == 0 && uv % 4 == 0; }
+
+// The per-frame checks of a conversion: every pointer set, one geometry, one pair of pitches (an unset pitch means the width: reference fallback) -- and on
+// the way the alignment class of the call: `aligned4` (planes_aligned4 of every frame) and `vec` (every output 16-byte aligned).
+int check_frames(int n, const tsvpp_nv12 *in, void *const *outs, int w, int h, int pitch_y, int pitch_uv, size_t y_off, size_t uv_off, bool &aligned4, bool &vec) {
+    aligned4 = vec = true;
+    for (int f = 0; f < n; f++) {
+        if (!in[f].y || !in[f].uv || !outs[f]) return TSVPP_ERROR;
+        if (in[f].width != w || in[f].height != h) return TSVPP_UNSUPPORTED;
+        if ((in[f].pitch_y ? in[f].pitch_y : in[f].width) != pitch_y) return TSVPP_UNSUPPORTED;
+        if ((in[f].pitch_uv ? in[f].pitch_uv : in[f].width) != pitch_uv) return TSVPP_UNSUPPORTED;
+        aligned4 = aligned4 && planes_aligned4(pitch_y, pitch_uv, (uintptr_t)(in[f].y + y_off), (uintptr_t)(in[f].uv + uv_off));
+        vec = vec && (((uintptr_t)outs[f] & 15) == 0);
+    }
+    return TSVPP_OK;
+}
+
+OutKind single_pass_kind(const Plan &pl) { return pl.fourcc == TSVPP_UYVY ? (pl.f32 ? O_UYVY_F32 : O_UYVY_U8) : O_YUV444_U8; }
+// UYVY / YUV444 (uint8; UYVY also fp32) behind a resize: does the streaming kernel take it (exact 3 : 2 or 2 : 1, BILINEAR / AREA / NEAREST, dword-aligned planes,
+// width % 8 == 0, height % 4 == 0, 16-byte aligned outputs)?  Asked of launch_fused itself, as a dry run: one set of conditions.
+bool single_pass_format(const Plan &pl, OutKind kind, const LaunchDesc &d, int n, bool outs_aligned16, hipStream_t stream) {
+    if ((pl.fourcc != TSVPP_UYVY && pl.fourcc != TSVPP_YUV444) || (pl.f32 && pl.fourcc != TSVPP_UYVY) || pl.mode == M_NONE || !outs_aligned16) return false; // (fp32: UYVY only, round 6)
+    LaunchDesc dd = d;
+    dd.n_frames = n < TSVPP_MAX_BATCH ? (n > 0 ? n : 1) : TSVPP_MAX_BATCH;
+    FrameTable t = {};
+    LaunchInfo info = {};
+    return launch_fused(pl.mode, kind, true, dd, t, stream, &info) == hipSuccess;
+}
+
+// The decisions of a request beyond its plan, taken once for a conversion, for tsvpp_describe and for the dry run of tsvpp_prepare_batch.  `d` comes from
+// fill_desc (+ set_area_desc) and leaves with in_aligned4 and the store override set.
+// Formats other than RGB24/BGR24: the reference feeds its other colour kernels with
+// the resized NV12; here pass 1 (only if there is a resize) writes that intermediate with the
+// fused kernel, pass 2 converts it.  Crop alone needs no pass 1: it is pointer arithmetic.
+// ... unless the streaming 3 : 2 / 2 : 1 kernel takes the request: it writes UYVY / YUV444 (uint8) itself, in one pass (vpp_bilinear_r32.hip)
+struct Resolved {
+    bool two_pass;    // UYVY / YUV444 as a second pass (launch_format) over NV12, not out of the streaming kernel in one
+    bool pass1;       // a fused launch runs (not for crop + format conversion: the second pass alone)
+    OutKind out_kind; // its output flavour
+};
+Resolved resolve_request(const Plan &pl, LaunchDesc &d, int n, bool aligned4, bool outs_aligned16, hipStream_t stream) {
+    d.in_aligned4 = aligned4 ? 1 : 0;
+    const OutKind kind1 = single_pass_kind(pl);
+    const bool single = single_pass_format(pl, kind1, d, n, outs_aligned16, stream);
+    const bool two_pass = (pl.fourcc == TSVPP_UYVY || pl.fourcc == TSVPP_YUV444) && !single;
+    if (two_pass && d.nt_stores < 0) d.nt_stores = 0; // the intermediate is read back at once: keep it in L2 / MALL
+    return Resolved{ two_pass, !(two_pass && pl.mode == M_NONE), single ? kind1 : pl.out };
+}
+
 // ---- replay of a thread's recent launches (round 6) ---------------------------------------------------------------------------------------------------
 // A conversion of ONE frame is host-bound: ~3.3 us of runtime per launch (tools/launch_cost.hip: 3.5 us with this library's 3.7 KiB kernarg segment, 2.65 with a
 // 16-byte one) plus what this file adds -- make_plan, fill_desc, launch_fused's selection, the table caches' mutexes and map lookups.  The latter is the same work for
@@ -679,7 +791,8 @@ bool needs_scratch(const Plan &pl) { return (pl.fourcc == TSVPP_UYVY || pl.fourc
 struct ReplayEntry {
     uint64_t ctx_id = 0, epoch = 0, stamp = 0;
     tsvpp_params p = {};
-    int w = 0, h = 0, py = 0, puv = 0, n = 0, aligned4 = 0, vec = 0;
+    int w = 0, h = 0, py = 0, puv = 0, n = 0;
+    bool aligned4 = false, vec = false;
     size_t y_off = 0, uv_off = 0;
     LaunchRecord rec;
 };
@@ -690,7 +803,7 @@ thread_local uint64_t g_replay_clock = 0;
 // tsvpp_debug_last_launch: the record of this thread's last conversion, if it ran in a context created under TSVPP_DEBUG_KNOBS=1 -- a replay slot's (replayed or
 // just remembered) or a copy of a record that is not replayable (several launches, a second pass, a frame table); null otherwise.  Every conversion clears it first.
 // What that costs every conversion: two thread-local pointer stores, three int stores into the launch record, and in each launcher one thread-local load
-// (record_name) -- the record itself is only armed where the replay cache arms it anyway, or in a debug context.
+// (describe_only) -- the record itself is only armed where the replay cache arms it anyway, or in a debug context.
 thread_local const LaunchRecord *g_last_launch = nullptr;
 thread_local LaunchRecord g_last_copy;
 struct RecordArm { // points launch_fused's launches at `rec` for the lifetime of this object
@@ -701,25 +814,16 @@ struct RecordArm { // points launch_fused's launches at `rec` for the lifetime o
 int try_replay(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, void *const *outs, void *stream) {
     const uint64_t epoch = ctx->epoch.load(std::memory_order_relaxed);
     const int py = in[0].pitch_y ? in[0].pitch_y : in[0].width, puv = in[0].pitch_uv ? in[0].pitch_uv : in[0].width;
-    int flags_for = -1, aligned4 = 0, vec = 0; // alignment class of THIS call, computed once (every entry of one request has the same crop offsets)
+    bool classed = false, aligned4 = false, vec = false; // alignment class of THIS call, computed once (every entry of one request has the same crop offsets)
     for (int k = 0; k < kReplayEntries; k++) {
         ReplayEntry &e = g_replay[k];
         if (e.ctx_id != ctx->id || e.epoch != epoch || e.n != n || e.w != in[0].width || e.h != in[0].height || e.py != py || e.puv != puv ||
             std::memcmp(&e.p, p, sizeof(*p)) != 0)
             continue;
-        if (flags_for < 0) { // the slow path's per-frame checks, in its order
-            bool a4 = (py % 4 == 0) && (puv % 4 == 0), v = true;
-            for (int f = 0; f < n; f++) {
-                if (!in[f].y || !in[f].uv || !outs[f]) return TSVPP_ERROR;
-                if (in[f].width != in[0].width || in[f].height != in[0].height) return TSVPP_UNSUPPORTED;
-                if ((in[f].pitch_y ? in[f].pitch_y : in[f].width) != py) return TSVPP_UNSUPPORTED;
-                if ((in[f].pitch_uv ? in[f].pitch_uv : in[f].width) != puv) return TSVPP_UNSUPPORTED;
-                a4 = a4 && (((uintptr_t)(in[f].y + e.y_off)) % 4 == 0) && (((uintptr_t)(in[f].uv + e.uv_off)) % 4 == 0);
-                v = v && (((uintptr_t)outs[f] & 15) == 0);
-            }
-            aligned4 = a4 ? 1 : 0;
-            vec = v ? 1 : 0;
-            flags_for = k;
+        if (!classed) {
+            const int sts = check_frames(n, in, outs, in[0].width, in[0].height, py, puv, e.y_off, e.uv_off, aligned4, vec);
+            if (sts != TSVPP_OK) return sts;
+            classed = true;
         }
         if (e.aligned4 != aligned4 || e.vec != vec) continue;
         DeviceGuard guard(ctx);
@@ -738,7 +842,7 @@ int try_replay(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *
                                    ? hipExtLaunchKernel(e.rec.fn, e.rec.grid, e.rec.block, args, e.rec.lds, (hipStream_t)stream, nullptr, nullptr, hipExtAnyOrderLaunch)
                                    : hipLaunchKernel(e.rec.fn, e.rec.grid, e.rec.block, args, e.rec.lds, (hipStream_t)stream);
         e.stamp = ++g_replay_clock;
-        if (err == hipSuccess && ctx->debug) g_last_launch = &e.rec;
+        if (err == hipSuccess && ctx->knobs.debug) g_last_launch = &e.rec;
         return (int)err;
     }
     return kReplayMiss;
@@ -758,8 +862,8 @@ const LaunchRecord *remember_launch(const tsvpp_ctx *ctx, uint64_t epoch, int n,
     slot->py = py;
     slot->puv = puv;
     slot->n = n;
-    slot->aligned4 = aligned4 ? 1 : 0;
-    slot->vec = vec ? 1 : 0;
+    slot->aligned4 = aligned4;
+    slot->vec = vec;
     slot->y_off = y_off;
     slot->uv_off = uv_off;
     slot->rec = rec;
@@ -798,12 +902,11 @@ int tsvpp_create(int device, int max_consumers, tsvpp_ctx **out_ctx) {
         delete ctx;
         return guard.status;
     }
-    tsvpp_default_coeffs(&ctx->coeffs);
-    read_env_knobs(ctx, true);
+    read_env_knobs(ctx->knobs, true);
     ctx->geo = geo_cache_create();
     {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->num_cus = prop.multiProcessorCount;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->knobs.num_cus = prop.multiProcessorCount;
     }
     for (int i = 0; i < max_consumers; i++) {
         hipStream_t s = nullptr;
@@ -850,24 +953,6 @@ void tsvpp_destroy(tsvpp_ctx *ctx) {
     delete ctx;
 }
 
-int tsvpp_consumer_stream(tsvpp_ctx *ctx, const char *name, void **out_stream) {
-    if (!ctx || !name || !out_stream) return TSVPP_ERROR;
-    std::lock_guard<std::mutex> lk(ctx->stream_mu);
-    for (auto &s : ctx->streams) {
-        if (s.first == name) {
-            *out_stream = (void *)s.second;
-            return TSVPP_OK;
-        }
-        if (s.first == "empty") {
-            s.first = name;
-            *out_stream = (void *)s.second;
-            return TSVPP_OK;
-        }
-    }
-    *out_stream = nullptr;
-    return TSVPP_ERROR; // pool exhausted (reference src/VideoProcessor.cpp:100-103)
-}
-
 // Index of the consumer's pool slot (claiming a free one for a new name), or -1 (caller holds stream_mu).
 static int consumer_slot(tsvpp_ctx *ctx, const char *name) {
     for (size_t i = 0; i < ctx->streams.size(); i++) {
@@ -879,6 +964,14 @@ static int consumer_slot(tsvpp_ctx *ctx, const char *name) {
         }
     }
     return -1;
+}
+
+int tsvpp_consumer_stream(tsvpp_ctx *ctx, const char *name, void **out_stream) {
+    if (!ctx || !name || !out_stream) return TSVPP_ERROR;
+    std::lock_guard<std::mutex> lk(ctx->stream_mu);
+    const int i = consumer_slot(ctx, name);
+    *out_stream = i < 0 ? nullptr : (void *)ctx->streams[(size_t)i].second;
+    return i < 0 ? TSVPP_ERROR : TSVPP_OK; // pool exhausted (reference src/VideoProcessor.cpp:100-103)
 }
 
 int tsvpp_consumer_next_stream(tsvpp_ctx *ctx, const char *name, size_t launch_bytes, void **out_stream) {
@@ -953,35 +1046,26 @@ int tsvpp_prepare_batch(tsvpp_ctx *ctx, const tsvpp_params *p, int in_width, int
     if (sts != TSVPP_OK) return sts;
     DeviceGuard guard(ctx);
     if (guard.status != TSVPP_OK) return guard.status;
-    if (pl.mode == M_AREA_DOWN) {
-        AreaTable tx, ty;
-        sts = get_area_table(ctx, pl.xr, tx);
-        if (sts != TSVPP_OK) return sts;
-        sts = get_area_table(ctx, pl.yr, ty);
-        if (sts != TSVPP_OK) return sts;
-        if (!(tx.qdev && ty.qdev) && ctx->area_divtab) { // the float-weight kernels' divisor table: the same condition as in convert
-            const float *div = nullptr;
-            sts = get_area_div(ctx, pl.xr, pl.yr, tx, ty, div, (hipStream_t)stream);
-            if (sts != TSVPP_OK) return sts;
-        }
-    }
+    LaunchDesc d;
+    const int pitch = (in_width + 255) & ~255;
+    fill_desc(ctx->knobs, ctx->geo, pl, pitch, pitch, d);
+    sts = area_desc(ctx, pl, (hipStream_t)stream, d);
+    if (sts != TSVPP_OK) return sts;
     if (needs_scratch(pl) && n_frames > 0) { // the NV12 intermediate of UYVY / YUV444 behind a resize
         tsvpp_ctx::ScratchSlot *slot = scratch_slot(ctx, stream);
         std::lock_guard<std::mutex> lk(slot->mu);
         sts = scratch_grow(ctx, slot, scratch_frame_bytes(pl) * (size_t)n_frames);
         if (sts != TSVPP_OK) return sts;
     }
-    if (((pl.mode == M_BILINEAR || pl.mode == M_AREA_UP) && ctx->geo_pref) || (pl.mode == M_BICUBIC && ctx->bicubic_cols)) {
+    if (((pl.mode == M_BILINEAR || pl.mode == M_AREA_UP) && ctx->knobs.geo_pref) || (pl.mode == M_BICUBIC && ctx->knobs.bicubic_cols)) {
         // geometry tables of the 2x2-tap kernel: a dry run of the launch chooses the tile shape and builds them.  They do not
         // depend on the pitches (only their use does: multiples of 16) nor on the batch size beyond the tile shape -- a
         // conversion that ends up with another shape builds its own set on first use.
-        LaunchDesc d;
-        const int pitch = (in_width + 255) & ~255;
-        fill_desc(ctx, pl, pitch, pitch, d);
-        d.in_aligned4 = 1;
+        const int total = n_frames > 0 ? n_frames : 1;
+        // (the outputs are unknown: UYVY / YUV444 are prepared as the two passes they may need -- pass 1 reads tables, the single-pass kernel none)
+        const Resolved rq = resolve_request(pl, d, total, true, false, (hipStream_t)stream);
         d.geo_build = 1;
         FrameTable t = {};
-        const int total = n_frames > 0 ? n_frames : 1;
         // the launch groups tsvpp_convert_batch forms: full groups of TSVPP_MAX_BATCH frames, then the remainder; and, for more frames than that, the groups
         // tsvpp_convert_table forms (up to TSVPP_MAX_TABLE_LAUNCH per launch; a launch the grid limit caps lower builds its tables on first use)
         const int groups[4] = { total >= TSVPP_MAX_BATCH ? TSVPP_MAX_BATCH : 0, total % TSVPP_MAX_BATCH,
@@ -991,7 +1075,7 @@ int tsvpp_prepare_batch(tsvpp_ctx *ctx, const tsvpp_params *p, int in_width, int
             if (cnt == 0) continue;
             d.n_frames = cnt;
             LaunchInfo info = {};
-            hipError_t e = launch_fused(pl.mode, pl.out, true, d, t, (hipStream_t)stream, &info);
+            hipError_t e = launch_fused(pl.mode, rq.out_kind, true, d, t, (hipStream_t)stream, &info);
             if (e != hipSuccess) return (int)e;
         }
     }
@@ -1010,21 +1094,6 @@ int tsvpp_enable_markers(tsvpp_ctx *ctx, int on) {
     return TSVPP_OK;
 }
 
-static OutKind single_pass_kind(const Plan &pl) { return pl.fourcc == TSVPP_UYVY ? (pl.f32 ? O_UYVY_F32 : O_UYVY_U8) : O_YUV444_U8; }
-// UYVY / YUV444 (uint8; UYVY also fp32) behind a resize: does the streaming kernel take it (exact 3 : 2 or 2 : 1, BILINEAR / AREA / NEAREST, dword-aligned planes,
-// width % 8 == 0, height % 4 == 0, 16-byte aligned outputs)?  Asked of launch_fused itself, as a dry run: one set of conditions.
-static bool single_pass_format(const Plan &pl, const LaunchDesc &d, int n, void *const *outs, hipStream_t stream) {
-    if ((pl.fourcc != TSVPP_UYVY && pl.fourcc != TSVPP_YUV444) || (pl.f32 && pl.fourcc != TSVPP_UYVY) || pl.mode == M_NONE) return false; // (fp32: UYVY only, round 6)
-    if (outs)
-        for (int f = 0; f < n; f++)
-            if (((uintptr_t)outs[f] & 15) != 0) return false;
-    LaunchDesc dd = d;
-    dd.n_frames = n < TSVPP_MAX_BATCH ? (n > 0 ? n : 1) : TSVPP_MAX_BATCH;
-    FrameTable t = {};
-    LaunchInfo info = {};
-    return launch_fused(pl.mode, single_pass_kind(pl), true, dd, t, stream, &info) == hipSuccess;
-}
-
 // Device-resident columns of a tsvpp_table, already advanced to the run's first entry (null: the pointer triples travel in the kernarg segment).
 struct TableCols {
     const uint64_t *y = nullptr, *uv = nullptr, *out = nullptr;
@@ -1035,7 +1104,7 @@ static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
     g_last_launch = nullptr; // (tsvpp_debug_last_launch: no stale record survives a conversion that records none)
     if (!ctx || !in || !p || !outs || n < 0) return TSVPP_ERROR;
     if (n == 0) return TSVPP_OK;
-    const bool replayable = ctx->replay && tab.y == nullptr && n <= TSVPP_MAX_BATCH && !ctx->markers;
+    const bool replayable = ctx->knobs.replay && tab.y == nullptr && n <= TSVPP_MAX_BATCH && !ctx->markers;
     const uint64_t epoch0 = ctx->epoch.load(std::memory_order_relaxed);
     if (replayable) { // the same request as one of this thread's recent ones: its finished launch again, with this call's frame pointers
         const int r = try_replay(ctx, n, in, p, outs, stream);
@@ -1052,12 +1121,10 @@ static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
     // off the vector alignment, which global stores tolerate.
     // (alignment is decided per launch group of TSVPP_MAX_BATCH frames below: one odd pointer does not push the
     // whole batch onto the element-wise kernel)
-    for (int f = 0; f < n; f++) {
-        if (!in[f].y || !in[f].uv || !outs[f]) return TSVPP_ERROR;
-        if (in[f].width != in[0].width || in[f].height != in[0].height) return TSVPP_UNSUPPORTED;
-        if ((in[f].pitch_y ? in[f].pitch_y : in[f].width) != pitch_y) return TSVPP_UNSUPPORTED;
-        if ((in[f].pitch_uv ? in[f].pitch_uv : in[f].width) != pitch_uv) return TSVPP_UNSUPPORTED;
-    }
+    const CropOff off = crop_offsets(pl, pitch_y, pitch_uv);
+    bool aligned4, all_vec;
+    sts = check_frames(n, in, outs, in[0].width, in[0].height, pitch_y, pitch_uv, off.y, off.uv, aligned4, all_vec);
+    if (sts != TSVPP_OK) return sts;
     DeviceGuard guard(ctx);
     if (guard.status != TSVPP_OK) return guard.status;
     char label[96] = "";
@@ -1068,57 +1135,14 @@ static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
     RangeGuard range(markers, label);
 
     LaunchDesc d;
-    fill_desc(ctx, pl, pitch_y, pitch_uv, d);
-    if (pl.mode == M_AREA_DOWN) {
-        AreaTable tx, ty;
-        sts = get_area_table(ctx, pl.xr, tx);
-        if (sts != TSVPP_OK) return sts;
-        sts = get_area_table(ctx, pl.yr, ty);
-        if (sts != TSVPP_OK) return sts;
-        d.patx = tx.dev;
-        d.nx = tx.rows;
-        d.rx = tx.taps;
-        d.paty = ty.dev;
-        d.ny = ty.rows;
-        d.ry = ty.taps;
-        d.patx4 = tx.dev4;
-        d.nkx = tx.nk;
-        d.paty4 = ty.dev4;
-        d.nky = ty.nk;
-        d.as_ones_x = tx.ones_end;
-        if (!(tx.qdev && ty.qdev) && ctx->area_divtab) { // float-weight kernels only
-            sts = get_area_div(ctx, pl.xr, pl.yr, tx, ty, d.area_div, (hipStream_t)stream);
-            if (sts != TSVPP_OK) return sts;
-        }
-        if (tx.qdev && ty.qdev && dyadic_usable(pl.xr, pl.yr, tx.shift, ty.shift)) {
-            d.qx = tx.qdev;
-            d.qy = ty.qdev;
-            d.box_rx = (tx.rows == 1 && tx.shift == 0 && tx.uniform_sum == tx.taps) ? tx.taps : 0; // one row of all ones
-            d.box_ry = (ty.rows == 1 && ty.shift == 0 && ty.uniform_sum == ty.taps) ? ty.taps : 0;
-            // one divisor for the whole frame -> exact integer division by a constant in the kernel
-            if (tx.uniform_sum > 0 && ty.uniform_sum > 0 && (long)tx.uniform_sum * ty.uniform_sum < 4096)
-                d.area_rcp = 1.0f / (float)(tx.uniform_sum * ty.uniform_sum);
-        }
-    }
-    // crop = pointer arithmetic (reference src/Crop.cu:10-18: luma at (left + j, top + i), chroma
-    // row top/2 + i/2, chroma byte (j & ~1) + left -- an odd `left` therefore swaps U and V,
-    // exactly as it does in the reference)
-    const size_t y_off = (size_t)pl.off_y * (size_t)pitch_y + (size_t)pl.off_x;
-    const size_t uv_off = (size_t)(pl.off_y / 2) * (size_t)pitch_uv + (size_t)pl.off_x;
-    bool aligned4 = (pitch_y % 4 == 0) && (pitch_uv % 4 == 0);
-    for (int f = 0; f < n && aligned4; f++)
-        aligned4 = (((uintptr_t)(in[f].y + y_off)) % 4 == 0) && (((uintptr_t)(in[f].uv + uv_off)) % 4 == 0);
-    d.in_aligned4 = aligned4 ? 1 : 0;
-    // Formats other than RGB24/BGR24: the reference feeds its other colour kernels with
-    // the resized NV12; here pass 1 (only if there is a resize) writes that intermediate with the
-    // fused kernel, pass 2 converts it.  Crop alone needs no pass 1: it is pointer arithmetic.
-    // ... unless the streaming 3 : 2 / 2 : 1 kernel takes the request: it writes UYVY / YUV444 (uint8) itself, in one pass (vpp_bilinear_r32.hip)
-    const bool single = single_pass_format(pl, d, n, outs, (hipStream_t)stream);
-    const bool two_pass = (pl.fourcc == TSVPP_UYVY || pl.fourcc == TSVPP_YUV444) && !single;
+    fill_desc(ctx->knobs, ctx->geo, pl, pitch_y, pitch_uv, d);
+    sts = area_desc(ctx, pl, (hipStream_t)stream, d);
+    if (sts != TSVPP_OK) return sts;
+    const Resolved rq = resolve_request(pl, d, n, aligned4, all_vec, (hipStream_t)stream);
     uint8_t *scratch = nullptr;
     size_t frame_scratch = 0;
     std::unique_lock<std::mutex> scratch_lock; // held until both passes of this call are enqueued
-    if (needs_scratch(pl) && !single) {
+    if (needs_scratch(pl) && rq.two_pass) {
         frame_scratch = scratch_frame_bytes(pl);
         tsvpp_ctx::ScratchSlot *slot = scratch_slot(ctx, stream);
         scratch_lock = std::unique_lock<std::mutex>(slot->mu);
@@ -1127,16 +1151,14 @@ static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
         if (sts != TSVPP_OK) return sts;
         scratch = slot->buf;
     }
-    const OutKind out_kind = single ? single_pass_kind(pl) : pl.out;
-    if (two_pass && d.nt_stores < 0) d.nt_stores = 0; // the intermediate is read back at once: keep it in L2 / MALL
     // Frames per launch: TSVPP_MAX_BATCH with the pointer triples in the kernarg segment; out of a device-resident table (single-pass requests) up to
     // TSVPP_MAX_TABLE_LAUNCH, less where the grid would outgrow 2^31 threads (the smallest tile any kernel uses is 64 x 4 output pixels per workgroup of 256).
-    const bool from_table = tab.y != nullptr && !two_pass;
+    const bool from_table = tab.y != nullptr && !rq.two_pass;
     // TSVPP_OPT_INPUTS_READY: never out of a table (tsvpp_table_set's upload is enqueued on this stream: the launch must wait for it), never for the two-pass
     // formats (pass 1 writes the stream's scratch buffer, which the previous call's pass 2 may still be reading)
     // ... and only for launches small enough to gain from starting beside their predecessor: measured on the headline (profiles/r06_curve_values.txt, one consumer on two
     // streams) 1 / 2 / 4 frames per launch 0.367 / 0.573 / 0.661 -> 0.410 / 0.583 / 0.682 of the roofline, but 8 frames (113 MB) 0.719 -> 0.682
-    d.any_order = ((ctx->inputs_ready == 1 || ctx->inputs_ready == 2) && tab.y == nullptr && !two_pass &&
+    d.any_order = ((ctx->inputs_ready == 1 || ctx->inputs_ready == 2) && tab.y == nullptr && !rq.two_pass &&
                    (size_t)n * plan_moved_bytes(pl) <= TSVPP_BARRIER_FREE_MAX_BYTES) ? 1 : 0;
     int max_launch = TSVPP_MAX_BATCH;
     if (from_table) {
@@ -1150,60 +1172,60 @@ static int convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
         FrameTable t = {};
         if (from_table) {
             t.y.ext = (const uint8_t *const *)(tab.y + base);
-            t.y.off = (int64_t)y_off;
+            t.y.off = (int64_t)off.y;
             t.uv.ext = (const uint8_t *const *)(tab.uv + base);
-            t.uv.off = (int64_t)uv_off;
+            t.uv.off = (int64_t)off.uv;
             t.out.ext = (void *const *)(tab.out + base);
             t.out.off = 0;
         } else {
             for (int f = 0; f < cnt; f++) {
-                t.y[f] = in[base + f].y + y_off;
-                t.uv[f] = in[base + f].uv + uv_off;
-                t.out[f] = (two_pass && pl.mode != M_NONE) ? (void *)(scratch + (size_t)(base + f) * frame_scratch) : outs[base + f];
+                t.y[f] = in[base + f].y + off.y;
+                t.uv[f] = in[base + f].uv + off.uv;
+                t.out[f] = (rq.two_pass && pl.mode != M_NONE) ? (void *)(scratch + (size_t)(base + f) * frame_scratch) : outs[base + f];
             }
         }
         d.n_frames = cnt;
         // Vector-store kernels need 16-byte aligned outputs (else: the element-wise gather kernel); scratch frames are
         // 256-byte aligned.
         bool vec = true;
-        if (!two_pass)
+        if (!rq.two_pass)
             for (int f = 0; f < cnt; f++)
                 if (((uintptr_t)outs[base + f] & 15) != 0) vec = false;
-        if (!(two_pass && pl.mode == M_NONE)) {
+        if (rq.pass1) {
             LaunchRecord rec;
             rec.mode = pl.mode;
-            rec.out = out_kind;
-            rec.pass2 = two_pass ? pl.fourcc : 0;
-            const bool keep = replayable && !two_pass && n <= max_launch; // one launch group, one pass
+            rec.out = rq.out_kind;
+            rec.pass2 = rq.two_pass ? pl.fourcc : 0;
+            const bool keep = replayable && !rq.two_pass && n <= max_launch; // one launch group, one pass
             hipError_t e;
             {
-                RecordArm arm((keep || ctx->debug) ? &rec : nullptr);
-                e = launch_fused(pl.mode, out_kind, vec, d, t, (hipStream_t)stream);
+                RecordArm arm((keep || ctx->knobs.debug) ? &rec : nullptr);
+                e = launch_fused(pl.mode, rq.out_kind, vec, d, t, (hipStream_t)stream);
             }
             if (e != hipSuccess) {
                 g_last_launch = nullptr; // (an earlier launch group's record does not describe a failed conversion)
                 return (int)e;
             }
             if (keep && rec.count == 1 && rec.fn) {
-                const LaunchRecord *kept = remember_launch(ctx, epoch0, n, in, p, pitch_y, pitch_uv, aligned4, vec, y_off, uv_off, rec);
-                if (ctx->debug) g_last_launch = kept;
-            } else if (ctx->debug && rec.count > 0) { // (count == 0: nothing was launched, and rec.d was never written)
+                const LaunchRecord *kept = remember_launch(ctx, epoch0, n, in, p, pitch_y, pitch_uv, aligned4, vec, off.y, off.uv, rec);
+                if (ctx->knobs.debug) g_last_launch = kept;
+            } else if (ctx->knobs.debug && rec.count > 0) { // (count == 0: nothing was launched, and rec.d was never written)
                 g_last_copy = rec;
                 g_last_launch = &g_last_copy;
             } else {
                 g_last_launch = nullptr;
             }
-        } else if (ctx->debug) { // crop + format conversion: the second pass alone
+        } else if (ctx->knobs.debug) { // crop + format conversion: the second pass alone
             g_last_copy = LaunchRecord();
             g_last_copy.name = "(none)";
             g_last_copy.mode = pl.mode;
-            g_last_copy.out = out_kind;
+            g_last_copy.out = rq.out_kind;
             g_last_copy.pass2 = pl.fourcc;
             g_last_copy.d.in_aligned4 = aligned4 ? 1 : 0;
             g_last_copy.d.n_frames = cnt;
             g_last_launch = &g_last_copy;
         }
-        if (two_pass) {
+        if (rq.two_pass) {
             int fpy = pitch_y, fpuv = pitch_uv;
             if (pl.mode != M_NONE) { // resized intermediate: tight, pitch = width (as the reference's)
                 for (int f = 0; f < cnt; f++) {
@@ -1319,11 +1341,9 @@ int tsvpp_table_set(tsvpp_table *table, int first, int n, const tsvpp_nv12 *in, 
     std::lock_guard<std::mutex> lk(table->mu);
     const tsvpp_nv12 g = table->have_geom ? table->geom : in[0];
     const int gpy = g.pitch_y ? g.pitch_y : g.width, gpuv = g.pitch_uv ? g.pitch_uv : g.width;
-    for (int f = 0; f < n; f++) { // one geometry per table, as one per batch (tsvpp_convert_batch)
-        if (!in[f].y || !in[f].uv || !outs[f]) return TSVPP_ERROR;
-        if (in[f].width != g.width || in[f].height != g.height) return TSVPP_UNSUPPORTED;
-        if ((in[f].pitch_y ? in[f].pitch_y : in[f].width) != gpy || (in[f].pitch_uv ? in[f].pitch_uv : in[f].width) != gpuv) return TSVPP_UNSUPPORTED;
-    }
+    bool a4, v16; // (not a table's business: a conversion classes its run of entries)
+    const int sts = check_frames(n, in, outs, g.width, g.height, gpy, gpuv, 0, 0, a4, v16); // one geometry per table, as one per batch (tsvpp_convert_batch)
+    if (sts != TSVPP_OK) return sts;
     DeviceGuard guard(table->ctx);
     if (guard.status != TSVPP_OK) return guard.status;
     // this upload's staging slot: wait for the copies that last read it, grow it if needed
@@ -1423,7 +1443,7 @@ int tsvpp_set_option(tsvpp_ctx *ctx, int option, int value) {
         return TSVPP_OK;
     case TSVPP_OPT_COLOR_G_TERM:
         if (value < 0 || value > 2) return TSVPP_ERROR;
-        ctx->color_g = value;
+        ctx->knobs.color_g = value;
         ctx->epoch.fetch_add(1);
         return TSVPP_OK;
     case TSVPP_OPT_INPUTS_READY:
@@ -1439,7 +1459,7 @@ int tsvpp_get_option(const tsvpp_ctx *ctx, int option, int *value) {
     if (!ctx || !value) return TSVPP_ERROR;
     switch (option) {
     case TSVPP_OPT_INPUTS_READY: *value = ctx->inputs_ready; return TSVPP_OK;
-    case TSVPP_OPT_COLOR_G_TERM: *value = ctx->color_g; return TSVPP_OK;
+    case TSVPP_OPT_COLOR_G_TERM: *value = ctx->knobs.color_g; return TSVPP_OK;
     case TSVPP_OPT_UNSAFE_COEFFS: *value = ctx->unsafe_coeffs; return TSVPP_OK;
     default: return TSVPP_UNSUPPORTED;
     }
@@ -1447,7 +1467,7 @@ int tsvpp_get_option(const tsvpp_ctx *ctx, int option, int *value) {
 
 int tsvpp_get_coeffs(const tsvpp_ctx *ctx, tsvpp_coeffs *out) {
     if (!ctx || !out) return TSVPP_ERROR;
-    *out = ctx->coeffs;
+    *out = ctx->knobs.coeffs;
     return TSVPP_OK;
 }
 
@@ -1458,7 +1478,7 @@ int tsvpp_set_coeffs(tsvpp_ctx *ctx, const tsvpp_coeffs *in) {
     tsvpp_coeffs def;
     tsvpp_default_coeffs(&def);
     if (std::memcmp(&def, in, sizeof(def)) != 0 && !ctx->unsafe_coeffs) return TSVPP_UNSUPPORTED;
-    ctx->coeffs = *in;
+    ctx->knobs.coeffs = *in;
     ctx->epoch.fetch_add(1);
     return TSVPP_OK;
 }
@@ -1501,60 +1521,36 @@ int tsvpp_describe(const tsvpp_params *p, int in_width, int in_height, int pitch
     if (pitch_y == 0) pitch_y = in_width;
     if (pitch_uv == 0) pitch_uv = in_width;
     if (pitch_y < in_width || pitch_uv < in_width || n_frames < 1) return TSVPP_ERROR;
-    tsvpp_ctx tmp; // knobs only: no device, no streams
-    tsvpp_default_coeffs(&tmp.coeffs);
-    read_env_knobs(&tmp);
+    Knobs kn; // no context: no device, no streams
+    read_env_knobs(kn);
     LaunchDesc d;
-    fill_desc(&tmp, pl, pitch_y, pitch_uv, d);
-    // frame pointers are assumed 256-byte aligned; the crop origin decides the rest
-    d.in_aligned4 = (pitch_y % 4 == 0 && pitch_uv % 4 == 0 && ((size_t)pl.off_y * pitch_y + pl.off_x) % 4 == 0 &&
-                     ((size_t)(pl.off_y / 2) * pitch_uv + pl.off_x) % 4 == 0)
-                        ? 1
-                        : 0;
-    static const float dummy_f[4] = { 0, 0, 0, 0 };
-    static const AreaQRow dummy_q = {};
-    if (pl.mode == M_AREA_DOWN) { // the same table properties get_area_table derives, without touching a device
-        int shift[2] = { -1, -1 }, uniform[2] = { 0, 0 };
-        bool dyadic[2] = { false, false };
+    fill_desc(kn, nullptr, pl, pitch_y, pitch_uv, d);
+    if (pl.mode == M_AREA_DOWN) { // the tables' properties without touching a device, stand-ins for their device copies
+        static float dummy_f[4] = { 0, 0, 0, 0 };
+        static AreaQRow dummy_q = {};
+        AreaTable tab[2];
         for (int axis = 0; axis < 2; axis++) {
-            std::vector<float> tab;
-            int rows = 0, taps = 0;
-            if (!build_area_rows(axis ? pl.yr : pl.xr, tab, rows, taps)) return TSVPP_UNSUPPORTED;
+            std::vector<float> rows;
             std::vector<AreaQRow> q;
-            dyadic[axis] = quantise_area_rows(tab, rows, taps, q, shift[axis]);
-            if (dyadic[axis]) {
-                uniform[axis] = q[0].sum;
-                for (const AreaQRow &e : q)
-                    if (e.sum != q[0].sum) uniform[axis] = 0;
-            }
-            (axis ? d.ny : d.nx) = rows;
-            (axis ? d.ry : d.rx) = taps;
-            (axis ? d.nky : d.nkx) = (taps + 3) / 4;
-            if (axis == 0) d.as_ones_x = area_ones_end(tab, rows, taps);
+            if (!area_axis(axis ? pl.yr : pl.xr, tab[axis], rows, q)) return TSVPP_UNSUPPORTED;
+            tab[axis].dev = tab[axis].dev4 = dummy_f;
+            if (tab[axis].dyadic) tab[axis].qdev = &dummy_q;
         }
-        d.patx = d.paty = d.patx4 = d.paty4 = dummy_f;
-        if (!(dyadic[0] && dyadic[1]) && tmp.area_divtab && (long)d.nx * d.ny <= (1L << 18)) d.area_div = dummy_f; // as get_area_div would
-        if (dyadic[0] && dyadic[1] && dyadic_usable(pl.xr, pl.yr, shift[0], shift[1])) {
-            d.qx = d.qy = &dummy_q;
-            d.box_rx = (d.nx == 1 && shift[0] == 0 && uniform[0] == d.rx) ? d.rx : 0;
-            d.box_ry = (d.ny == 1 && shift[1] == 0 && uniform[1] == d.ry) ? d.ry : 0;
-            if (uniform[0] > 0 && uniform[1] > 0 && (long)uniform[0] * uniform[1] < 4096) d.area_rcp = 1.0f / (float)(uniform[0] * uniform[1]);
-        }
+        set_area_desc(pl, tab[0], tab[1], wants_area_div(kn, tab[0], tab[1]) ? dummy_f : nullptr, d);
     }
-    const bool single = aligned_outputs != 0 && single_pass_format(pl, d, n_frames, nullptr, nullptr);
-    const OutKind out_kind = single ? single_pass_kind(pl) : pl.out;
-    const bool two_pass = (pl.fourcc == TSVPP_UYVY || pl.fourcc == TSVPP_YUV444) && !single;
+    // frame pointers are assumed 256-byte aligned; the crop origin decides the rest
+    const CropOff off = crop_offsets(pl, pitch_y, pitch_uv);
+    const Resolved rq = resolve_request(pl, d, n_frames, planes_aligned4(pitch_y, pitch_uv, off.y, off.uv), aligned_outputs != 0, nullptr);
     d.n_frames = n_frames < TSVPP_MAX_BATCH ? n_frames : TSVPP_MAX_BATCH;
-    if (two_pass && d.nt_stores < 0) d.nt_stores = 0; // (as convert_impl: the intermediate is read back at once)
     LaunchInfo info = {};
     info.kernel = "(none)";
     info.in4 = d.in_aligned4;
-    if (!(two_pass && pl.mode == M_NONE)) {
+    if (rq.pass1) {
         FrameTable t = {};
-        hipError_t e = launch_fused(pl.mode, out_kind, aligned_outputs != 0 || two_pass, d, t, nullptr, &info);
+        hipError_t e = launch_fused(pl.mode, rq.out_kind, aligned_outputs != 0 || rq.two_pass, d, t, nullptr, &info);
         if (e != hipSuccess) return (int)e;
     }
-    format_selection(buf, buf_len, pl.mode, out_kind, pl.src_w, pl.src_h, pl.dst_w, pl.dst_h, info, d.n_frames, two_pass ? pl.fourcc : 0);
+    format_selection(buf, buf_len, pl.mode, rq.out_kind, pl.src_w, pl.src_h, pl.dst_w, pl.dst_h, info, d.n_frames, rq.two_pass ? pl.fourcc : 0);
     return TSVPP_OK;
 }
 

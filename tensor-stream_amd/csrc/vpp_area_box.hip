@@ -182,13 +182,7 @@ hipError_t launch_area_box(OutKind out, const LaunchDesc &d, const FrameTable &t
                                              { "vpp_area_box_kernel<2,1,OUT>", "vpp_area_box_kernel<3,1,OUT>", "vpp_area_box_kernel<4,1,OUT>", "vpp_area_box_kernel<5,1,OUT>",
                                                "vpp_area_box_kernel<6,1,OUT>", "vpp_area_box_kernel<7,1,OUT>", "vpp_area_box_kernel<8,1,OUT>" } };
     if (d.box_rx < 2 || d.box_rx > 8) return hipErrorInvalidValue;
-    if (info) {
-        info->kernel = names[square ? 1 : 0][d.box_rx - 2];
-        info->grid = (int)grid.x;
-        info->lds_bytes = 0;
-        return hipSuccess;
-    }
-    record_name(names[square ? 1 : 0][d.box_rx - 2]);
+    if (describe_only(info, names[square ? 1 : 0][d.box_rx - 2], grid, 0)) return hipSuccess;
     switch (d.box_rx * 2 + (square ? 1 : 0)) {
     case 4: return launch_box_rs<2, false>(out, d, t, grid, block, stream);
     case 5: return launch_box_rs<2, true>(out, d, t, grid, block, stream);

@@ -298,13 +298,7 @@ hipError_t launch_area_stream(OutKind out, const LaunchDesc &d, const FrameTable
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD));
     static const char *const names[9] = { "", "vpp_area_stream_kernel<1,OUT>", "vpp_area_stream_kernel<2,OUT>", "vpp_area_stream_kernel<3,OUT>", "vpp_area_stream_kernel<4,OUT>",
                                           "", "vpp_area_stream_kernel<6,OUT>", "", "vpp_area_stream_kernel<8,OUT>" };
-    if (info) {
-        info->kernel = (d.as_nk >= 1 && d.as_nk <= 8) ? names[d.as_nk] : "";
-        info->grid = (int)grid.x;
-        info->lds_bytes = (int)lds_bytes;
-        return hipSuccess;
-    }
-    if (d.as_nk >= 1 && d.as_nk <= 8) record_name(names[d.as_nk]);
+    if (describe_only(info, (d.as_nk >= 1 && d.as_nk <= 8) ? names[d.as_nk] : "", grid, lds_bytes)) return hipSuccess;
     switch (d.as_nk) {
     case 1: return launch_area_stream_nk<1>(out, d, t, grid, lds_bytes, stream);
     case 2: return launch_area_stream_nk<2>(out, d, t, grid, lds_bytes, stream);

@@ -582,14 +582,9 @@ hipError_t launch_bicubic_cols(OutKind out, bool exact, const LaunchDesc &d, con
     const bool sparse = d.bc_sparse != 0;
     const char *name = exact ? (sparse ? "vpp_bicubic_cols_kernel<OUT, exact, sparse>" : "vpp_bicubic_cols_kernel<OUT, exact, dense>")
                              : (sparse ? "vpp_bicubic_cols_kernel<OUT, tie, sparse>" : "vpp_bicubic_cols_kernel<OUT, tie, dense>");
-    if (info) {
-        info->kernel = name;
-        info->grid = (int)grid.x;
-        info->lds_bytes = (int)lds_bytes + (out == O_U8_MERGED ? MAX_THREADS * 24 : 0); // + the static exchange slab of the uint8 merged output side
-        return hipSuccess;
-    }
+    // (+ the static exchange slab of the uint8 merged output side)
+    if (describe_only(info, name, grid, lds_bytes + (out == O_U8_MERGED ? MAX_THREADS * 24 : 0))) return hipSuccess;
     if (!d.bc_tab) return hipErrorInvalidValue;
-    record_name(name);
     switch (out) {
 #define TSVPP_BC(O)                                                                                                               \
     case O:                                                                                                                       \

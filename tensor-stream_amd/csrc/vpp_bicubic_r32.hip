@@ -126,13 +126,7 @@ hipError_t launch_bicubic_r32(OutKind out, const LaunchDesc &d, const FrameTable
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
     if (d.r32 != 7 && d.r32 != 8) return hipErrorInvalidValue;
     const char *name = d.r32 == 7 ? "vpp_bicubic_r32_kernel<OUT,3:2>" : "vpp_bicubic_r32_kernel<OUT,2:1>";
-    if (info) {
-        info->kernel = name;
-        info->grid = (int)grid.x;
-        info->lds_bytes = out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16;
-        return hipSuccess;
-    }
-    record_name(name);
+    if (describe_only(info, name, grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16)) return hipSuccess;
     return d.r32 == 7 ? launch_bcr_k<3>(out, d, t, grid, block, stream) : launch_bcr_k<4>(out, d, t, grid, block, stream);
 }
 

@@ -746,14 +746,10 @@ hipError_t launch_bilinear(bool areaup, OutKind out, const LaunchDesc &din, cons
         lds_bytes -= (cols + cols / 2) * sizeof(XEntry) + (rows + rows / 2) * sizeof(YEntry);
     }
     const char *name = areaup ? "vpp_bilinear_kernel<areaup,OUT>" : d.tap22 ? "vpp_bilinear_kernel<bilinear,OUT>[area-weights]" : "vpp_bilinear_kernel<bilinear,OUT>";
-    if (info) {
-        info->kernel = name;
-        info->grid = (int)grid.x;
-        info->lds_bytes = (int)lds_bytes;
+    if (describe_only(info, name, grid, lds_bytes)) {
         info->geo = d.geo;
         return hipSuccess;
     }
-    record_name(name);
     if (d.geo) return launch_bilinear_geo(out, d, t, grid, block, lds_bytes, stream);
     return areaup ? launch_bilinear_a<true>(out, d, t, grid, block, lds_bytes, stream)
                   : launch_bilinear_a<false>(out, d, t, grid, block, lds_bytes, stream);

@@ -525,13 +525,7 @@ hipError_t launch_bilinear_r32(OutKind out, const LaunchDesc &d, const FrameTabl
     static const char *const names[6] = { "vpp_bilinear_r32_kernel<OUT,bilinear,3:2>", "vpp_bilinear_r32_kernel<OUT,area,3:2>", "vpp_bilinear_r32_kernel<OUT,nearest,3:2>",
                                           "vpp_bilinear_r32_kernel<OUT,bilinear,2:1>", "vpp_bilinear_r32_kernel<OUT,area,2:1>", "vpp_bilinear_r32_kernel<OUT,nearest,2:1>" };
     if (d.r32 < 1 || d.r32 > 6) return hipErrorInvalidValue;
-    if (info) {
-        info->kernel = names[d.r32 - 1];
-        info->grid = (int)grid.x;
-        info->lds_bytes = out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : out == O_UYVY_F32 ? MAX_THREADS * 16 : 16;
-        return hipSuccess;
-    }
-    record_name(names[d.r32 - 1]);
+    if (describe_only(info, names[d.r32 - 1], grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : out == O_UYVY_F32 ? MAX_THREADS * 16 : 16)) return hipSuccess;
     switch (d.r32) {
     case 1: return launch_r32_k<R32_BILINEAR, 3>(out, d, t, grid, block, stream);
     case 2: return launch_r32_k<R32_AREA, 3>(out, d, t, grid, block, stream);

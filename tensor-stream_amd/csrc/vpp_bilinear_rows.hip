@@ -257,13 +257,7 @@ hipError_t launch_bilinear_rows(OutKind out, const LaunchDesc &d, const FrameTab
     const int kind = d.point_kind == PK_NEAREST ? BRK_NEAREST : (d.point_kind != PK_NONE ? BRK_POINT : (d.wx_zero != 0 ? BRK_WX0 : BRK_2X2));
     static const char *const names[4] = { "vpp_bilinear_rows_kernel<OUT, 2x2>", "vpp_bilinear_rows_kernel<OUT, wx0>", "vpp_bilinear_rows_kernel<OUT, point>",
                                           "vpp_bilinear_rows_kernel<OUT, nearest>" };
-    if (info) {
-        info->kernel = names[kind];
-        info->grid = (int)grid.x;
-        info->lds_bytes = (int)lds_bytes;
-        return hipSuccess;
-    }
-    record_name(names[kind]);
+    if (describe_only(info, names[kind], grid, lds_bytes)) return hipSuccess;
     switch (out) {
 #define TSVPP_BR(O)                                                                                                     \
     case O:                                                                                                             \

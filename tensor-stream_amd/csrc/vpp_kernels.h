@@ -200,11 +200,6 @@ inline void record_launch(const void *fn, dim3 grid, dim3 block, size_t lds, con
         r->d = d;
     }
 }
-// A launcher names the kernel it is about to launch (before TSVPP_LAUNCH): kept for the first launch of an armed record only.
-inline void record_name(const char *name) {
-    LaunchRecord *r = g_launch_rec;
-    if (r && r->count == 0) r->name = name;
-}
 
 // Every fused-kernel launch goes through this: an ordinary in-order launch, or -- LaunchDesc::any_order -- one whose packet does not wait for its predecessors.
 #define TSVPP_LAUNCH(KERNEL, GRID, BLOCK, LDS, STREAM, D, T)                                                                         \
@@ -290,6 +285,21 @@ struct LaunchInfo {
     int nt;   // LaunchDesc::nt_stores after sel_store_policy (store variant: bit 0 / 1 non-temporal, bit 2 the 4-byte uint8 stores too)
     int in4;  // LaunchDesc::in_aligned4
 };
+
+// Every launcher, once it knows its kernel: in a dry run (`info`) the choice is written there and the caller launches nothing (true); otherwise the name goes
+// into the armed launch record, if any -- kept for its first launch only -- and the caller launches (false).  One name for both: what tsvpp_describe announces is
+// what tsvpp_debug_last_launch reports.
+inline bool describe_only(LaunchInfo *info, const char *name, dim3 grid, size_t lds_bytes) {
+    if (info) {
+        info->kernel = name;
+        info->grid = (int)grid.x;
+        info->lds_bytes = (int)lds_bytes;
+        return true;
+    }
+    LaunchRecord *r = g_launch_rec;
+    if (r && r->count == 0) r->name = name;
+    return false;
+}
 
 // Launches the fused crop+resize+colour kernel.  `vec` selects the 16-byte/4-byte vector
 // store path (needs 16-byte aligned outputs; when dst_w = 4 k + 2 a row's last thread tile takes the generic path).

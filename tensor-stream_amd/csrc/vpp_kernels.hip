@@ -978,14 +978,7 @@ __global__ __launch_bounds__(MAX_THREADS) void vpp_color_kernel(const LaunchDesc
 // logic) -- record the choice and launch nothing.
 #define TSVPP_LAUNCH_OR_DESCRIBE(NAME, KERNEL, GRID, BLOCK, LDS)                                   \
     do {                                                                               \
-        if (info) {                                                                    \
-            info->kernel = NAME;                                                       \
-            info->grid = (int)(GRID).x;                                                \
-            info->lds_bytes = (int)(LDS);                                              \
-        } else {                                                                       \
-            tsvpp::record_name(NAME);                                                  \
-            TSVPP_LAUNCH(KERNEL, GRID, BLOCK, LDS, stream, d, t);                \
-        }                                                                              \
+        if (!tsvpp::describe_only(info, NAME, GRID, LDS)) TSVPP_LAUNCH(KERNEL, GRID, BLOCK, LDS, stream, d, t); \
     } while (0)
 
 template <int OUT>

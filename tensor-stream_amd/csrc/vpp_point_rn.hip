@@ -166,13 +166,7 @@ hipError_t launch_point_rn(OutKind out, const LaunchDesc &d, const FrameTable &t
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
     const char *name = nullptr;
     if (d.r32 == 20) { // pixel replication at 1 : 2 (NEAREST, AREA up-scale)
-        if (info) {
-            info->kernel = "vpp_rep2_kernel<OUT>";
-            info->grid = (int)grid.x;
-            info->lds_bytes = out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16;
-            return hipSuccess;
-        }
-        record_name("vpp_rep2_kernel<OUT>");
+        if (describe_only(info, "vpp_rep2_kernel<OUT>", grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16)) return hipSuccess;
         switch (out) {
 #define TSVPP_REP2(O) case O: TSVPP_LAUNCH((vpp_rep2_kernel<O>), grid, block, 0, stream, d, t); break;
             TSVPP_REP2(O_U8_PLANAR) TSVPP_REP2(O_U8_MERGED) TSVPP_REP2(O_NV12_U8) TSVPP_REP2(O_Y800_U8)
@@ -190,13 +184,7 @@ hipError_t launch_point_rn(OutKind out, const LaunchDesc &d, const FrameTable &t
     case 152: name = "vpp_point_rn_kernel<OUT,5:1,centre>"; break;
     default: return hipErrorInvalidValue;
     }
-    if (info) {
-        info->kernel = name;
-        info->grid = (int)grid.x;
-        info->lds_bytes = out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16;
-        return hipSuccess;
-    }
-    record_name(name);
+    if (describe_only(info, name, grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16)) return hipSuccess;
     switch (d.r32) {
     case 130: return launch_prn<3, 0>(out, d, t, grid, block, stream);
     case 131: return launch_prn<3, 1>(out, d, t, grid, block, stream);

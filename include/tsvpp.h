@@ -157,6 +157,48 @@ void tsvpp_table_destroy(tsvpp_table *table);
 int tsvpp_table_set(tsvpp_table *table, int first, int n, const tsvpp_nv12 *in, void *const *outs, void *stream);
 int tsvpp_convert_table(tsvpp_ctx *ctx, const tsvpp_table *table, int first, int n, const tsvpp_params *p, void *stream);
 
+/* ---- regions of interest (not in the reference: one crop box per Convert, src/VideoProcessor.cpp:106-135) ------------------------------------------------
+ * The cascade behind a detector: `n_rois` boxes, taken from one or several NV12 frames, each resized to the SAME p->dst_width x p->dst_height, colour-converted
+ * and stored to its own output, in ceil(n_rois / TSVPP_MAX_ROIS) kernel launches (one tsvpp_convert with crop_* per box is one launch per box: ~4 us of host
+ * time and a dependent-launch boundary for well under 1 us of HBM time).
+ *   rois[i]     box [left, right) x [top, bottom) of frames[rois[i].frame], in luma pixels; even width and height; inside its frame.  Boxes may overlap,
+ *               touch the frame's edges or span its full width / height (such a box IS cut out here, unlike Convert's crop stage, which ignores a crop that
+ *               is not smaller than the frame in both dimensions), and may be smaller than the output (up-scaling) on either axis.
+ *   frames      may differ in size and pitch (a detector batch over several streams).
+ *   outs[i]     device memory of box i, tight: channels * dst_width * dst_height elements (channels = tsvpp_channels(p->fourcc): 3 for RGB24 / BGR24, 1 for
+ *               Y800) of uint8 (p->normalization == 0) or float, i.e. tsvpp_out_bytes(p, dst_width, dst_height) bytes, laid out as tsvpp_convert's output.
+ *   p           dst_width / dst_height (> 0, even), resize_type, fourcc, planes, normalization; p->crop_* must be zero (the boxes are the crops).
+ * The result of a box is, bit for bit, what tsvpp_convert returns for a frame that consists of the box alone (luma rows [top, bottom) x columns [left, right);
+ * chroma rows [top / 2, top / 2 + height / 2) x BYTE columns [left, right): the crop rule of Convert, an odd `left` swaps U and V as it does there), resized
+ * with xr = (float)width / dst_width, yr = (float)height / dst_height; for a box Convert's crop stage accepts it equals tsvpp_convert(crop = box).  A box of
+ * exactly dst_width x dst_height is a plain colour conversion (every interpolation weight is zero).
+ * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  NOT YET supported (TSVPP_UNSUPPORTED): AREA (its down-scale
+ * needs a weight table per distinct ratio), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes, rotated boxes,
+ * fp16 outputs.
+ * `frames`, `rois`, `outs` are HOST arrays and may be freed on return: the per-box records (plane origins, pitches, size, ratios, output pointer: 48 bytes)
+ * travel BY VALUE in the kernarg segment of their launch -- no staging buffer, no copy, no allocation, no host synchronisation -- which is what bounds a
+ * launch to TSVPP_MAX_ROIS boxes.  The call is therefore legal while `stream` is being captured into a hipGraph: the graph replays the records (the pointers
+ * and boxes of the captured call) as they were.  Always an ordinary in-order launch (TSVPP_OPT_INPUTS_READY does not apply); TSVPP_OPT_COLOR_G_TERM and the
+ * context's coefficient block are honoured; the replay cache is not involved.
+ * Status, decided before any device is touched (tsvpp_describe_rois returns the same one):
+ *   TSVPP_ERROR        null arguments, n_rois <= 0, n_frames <= 0, a frame without size or with a pitch below its width, `frame` out of range, a box that is
+ *                      empty, inverted or not inside its frame, dst_width / dst_height <= 0, non-zero crop_* in `p` (and, converting: a null plane or output)
+ *   TSVPP_UNSUPPORTED  odd box width / height, odd dst_*, odd frame size, AREA, an unknown resize type, an output format outside the list above. */
+#define TSVPP_MAX_ROIS 64 /* boxes per launch; more are split */
+typedef struct tsvpp_roi {
+    int32_t frame;                    /* index into `frames` */
+    int32_t left, top, right, bottom; /* as CropOptions: leftTopCorner (x, y), rightBottomCorner (x, y) */
+} tsvpp_roi;
+int tsvpp_convert_rois(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
+                       void *stream);
+/* What tsvpp_convert_rois WOULD launch, as one line of key=value text in tsvpp_describe's style: "mode=bilinear out=f32_planar dst=224x224 rois=33 frames=1
+ * launches=1 kernel=vpp_rois<...> shape=8x16 lds=.. grid=.. tiles=7x7 staged=.. tail=.. nt=.. limit=64".  Host only: needs no context and no GPU, the plane
+ * pointers in `frames` are not read (taken as 256-byte aligned); TSVPP_* knobs are honoured.  lds= / grid= are the first launch's; staged= is the number of
+ * boxes whose every tile stages its source footprint in LDS (the LDS budget, TSVPP_LDS_KB, decides; the others gather from global memory); tail= as in
+ * tsvpp_describe (2: shifted last tile column; 0). */
+int tsvpp_describe_rois(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
+                        size_t buf_len);
+
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them
  * per frame, src/Resize.cu:389-406,436-452) and, for UYVY / YUV444 behind a resize, the resized-NV12 scratch of

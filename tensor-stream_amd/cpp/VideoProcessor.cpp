@@ -6,6 +6,7 @@
 #include <iostream>
 #include <mutex>
 #include <thread>
+#include <vector>
 
 namespace {
 // reference include/Common.h:107-114 (CHECK_STATUS): report where, return the code
@@ -171,6 +172,22 @@ int VideoProcessor::ConvertInto(AVFrame *input, void *deviceOut, FrameParameters
     CHECK_STATUS(tsvpp_convert(ctx, &in, &p, deviceOut, stream));
     if (outW) *outW = w;
     if (outH) *outH = h;
+    return VREADER_OK;
+}
+
+int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                std::string consumerName) {
+    if (isClosed || !inputs || nInputs <= 0 || !rois || nRois <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
+    void *stream = nullptr;
+    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    std::vector<tsvpp_nv12> frames((size_t)nInputs);
+    for (int f = 0; f < nInputs; f++) {
+        const AVFrame *in = inputs[f];
+        if (!in) CHECK_STATUS(VREADER_ERROR);
+        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
+    }
+    const tsvpp_params p = flatten(options); // options.crop must be empty: the boxes are the crops
+    CHECK_STATUS(tsvpp_convert_rois(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
     return VREADER_OK;
 }
 

@@ -115,6 +115,11 @@ public:
     // Same conversion into caller-owned memory (no allocation at all) -- what a torch-backed
     // getFrame should call with tensor.data_ptr().
     int ConvertInto(AVFrame *input, void *deviceOut, FrameParameters &options, std::string consumerName, int *outWidth = nullptr, int *outHeight = nullptr);
+    // The cascade behind a detector (tsvpp_convert_rois, include/tsvpp.h; not in the reference): box rois[i] of inputs[rois[i].frame] -- the frames may differ in size
+    // and pitch -- is cut out, resized to options.resize.width x height, colour-converted and written to deviceOuts[i] (caller-owned device memory of
+    // channels * width * height elements), one kernel launch per TSVPP_MAX_ROIS boxes on the consumer's stream.  options.crop must be empty; the inputs are NOT
+    // consumed (no av_frame_unref: a frame usually serves several calls).  Same status convention as ConvertInto.
+    int ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

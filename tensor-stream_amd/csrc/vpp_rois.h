@@ -1,0 +1,110 @@
+// vpp_rois.h -- launch descriptor and tile geometry of the region-of-interest kernel (vpp_rois.hip), shared with the host API
+// (tsvpp_api.cpp: tsvpp_convert_rois / tsvpp_describe_rois).  Product code -- never includes anything from oracle/.
+#pragma once
+#include "vpp_kernels.h"
+#include "vpp_axis.h"
+
+#pragma clang fp contract(off)
+
+namespace tsvpp {
+
+// Workgroup of the ROI kernel: ROI_TX x ROI_TY thread tiles of 4 x 2 output pixels = a 32 x 32 pixel tile, two waves.  Boxes are small (NN-input sizes: 112 / 224 /
+// 256 squared), many, and their ratios differ: 32 columns divide 224 and 256 exactly, a 32 x 32 tile at a ratio of 4.6 (a 512-pixel box to 112) still taps
+// only 164 x 148 luma bytes + half as many chroma bytes = 36 KiB, inside the 40 KiB budget that keeps four workgroups on a CU.
+constexpr int ROI_TX = 8, ROI_TY = 16, ROI_TX_SHIFT = 3;
+constexpr int ROI_TILE_W = ROI_TX * 4, ROI_TILE_H = ROI_TY * 2, ROI_THREADS = ROI_TX * ROI_TY;
+
+// What differs per box.  Wave-uniform: the kernel indexes the record array with its workgroup's box and reads the fields with scalar loads out of the kernarg segment.
+struct RoiRec {
+    uint64_t y, uv, out;       // plane addresses ADVANCED to the box origin (luma: top * pitch_y + left; chroma: (top / 2) * pitch_uv + left), output address
+    int32_t pitch_y, pitch_uv; // of the box's frame
+    int32_t src_w, src_h;      // the box
+    float xr, yr;              // (float)src_w / dst_w, (float)src_h / dst_h   (reference src/Resize.cu:418-419)
+};
+static_assert(sizeof(RoiRec) == 48, "RoiRec layout");
+
+// One launch: up to TSVPP_MAX_ROIS boxes, by value in the kernarg segment (3.1 KiB; HIP's hidden arguments take up to 256 bytes of the segment's 4 KiB).
+struct RoiLaunch {
+    int32_t dst_w, dst_h;
+    int32_t swap_rb, color_g;
+    tsvpp_coeffs k;
+    int32_t tiles_x, tiles_y, n_rois;
+    int32_t nt_stores, last_col0, u8_xchg; // as LaunchDesc's
+    int32_t lds_bytes;                     // dynamic LDS of the launch: a tile whose footprint needs more gathers from global memory
+    int32_t pad;
+    RoiRec r[TSVPP_MAX_ROIS];
+};
+static_assert(sizeof(RoiLaunch) + 256 <= 4096, "RoiLaunch no longer fits the kernarg segment");
+
+// Source footprint of output indices [o0, o1] along one axis: first and last source sample any of them taps -- axis_span (vpp_device.h) with the mode as a
+// run-time value, for host and device alike (the host sizes the launch's LDS with exactly the numbers the kernel will compute).
+__host__ __device__ inline void roi_axis_span(int mode, int o0, int o1, float ratio, int limit, int &lo, int &hi) {
+    if (mode == M_NEAREST) {
+        lo = (int)(ratio * (float)o0);
+        hi = (int)(ratio * (float)o1);
+    } else if (mode == M_BILINEAR) {
+        float w;
+        bilinear_axis(o0, ratio, limit, lo, w);
+        bilinear_axis(o1, ratio, limit, hi, w);
+        hi += 1;
+    } else { // M_BICUBIC
+        double w;
+        bicubic_axis(o0, ratio, limit, lo, w);
+        bicubic_axis(o1, ratio, limit, hi, w);
+        lo -= 1;
+        hi += 2;
+    }
+}
+
+// Footprint of the tile that starts at output (i_first, j_first) in both planes, as tile_footprint (vpp_device.h) computes it: luma columns / rows, chroma
+// PAIR columns / rows (the same formulas on the chroma grid's own indices), clamped into the box.
+struct RoiFootprint {
+    int xlo, xhi, ylo, yhi, cxlo, cxhi, cylo, cyhi;
+};
+__host__ __device__ inline void roi_clamp(int &lo, int &hi, int limit) {
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > limit - 1 ? limit - 1 : hi;
+    if (lo > hi) lo = hi; // (never for a valid request)
+}
+__host__ __device__ inline void roi_span_x(int mode, int j_first, int dst_w, int src_w, float xr, RoiFootprint &f) {
+    const int j_last = (j_first + ROI_TILE_W < dst_w ? j_first + ROI_TILE_W : dst_w) - 1;
+    roi_axis_span(mode, j_first, j_last, xr, src_w, f.xlo, f.xhi);
+    roi_clamp(f.xlo, f.xhi, src_w);
+    roi_axis_span(mode, j_first >> 1, j_last >> 1, xr, src_w, f.cxlo, f.cxhi);
+    roi_clamp(f.cxlo, f.cxhi, src_w >> 1);
+}
+__host__ __device__ inline void roi_span_y(int mode, int i_first, int dst_h, int src_h, float yr, RoiFootprint &f) {
+    const int i_last = (i_first + ROI_TILE_H < dst_h ? i_first + ROI_TILE_H : dst_h) - 1;
+    roi_axis_span(mode, i_first, i_last, yr, src_h, f.ylo, f.yhi);
+    roi_clamp(f.ylo, f.yhi, src_h);
+    roi_axis_span(mode, i_first >> 1, i_last >> 1, yr, src_h, f.cylo, f.cyhi);
+    roi_clamp(f.cylo, f.cyhi, src_h >> 1);
+}
+// 16-byte chunks of one staged row that holds `span` bytes at any misalignment (0..15) of its first byte
+__host__ __device__ inline int roi_chunks(int span) { return ((span + 14) >> 4) + 1; }
+// LDS bytes of a staged tile: luma rows, then chroma rows
+__host__ __device__ inline int roi_lds_need(const RoiFootprint &f, bool luma_only) {
+    const int ny = f.yhi - f.ylo + 1, nuv = luma_only ? 0 : f.cyhi - f.cylo + 1;
+    return 16 * (ny * roi_chunks(f.xhi - f.xlo + 1) + nuv * roi_chunks(2 * (f.cxhi - f.cxlo + 1)));
+}
+// ... and whether the staging loop can serve it: the lanes of one row are a power of two of the workgroup's threads
+__host__ __device__ inline bool roi_stageable(const RoiFootprint &f) {
+    return roi_chunks(f.xhi - f.xlo + 1) <= ROI_THREADS && roi_chunks(2 * (f.cxhi - f.cxlo + 1)) <= ROI_THREADS;
+}
+// first output column of tile column `tx` (tile_col0, vpp_device.h: the shifted last tile column of outputs 4 k + 2 columns wide)
+__host__ __device__ inline int roi_tile_col0(int tx, int dst_w, int last_col0) {
+    const int j = tx * ROI_TILE_W;
+    return (last_col0 > 0 && j + ROI_TILE_W > dst_w) ? last_col0 : j;
+}
+
+// static LDS of the kernel's output side (MergedRun's exchange slabs, vpp_device.h): counts against the workgroup's LDS budget
+inline int roi_static_lds(OutKind out, bool vec) {
+    if (!vec) return 0;
+    return out == O_F32_MERGED ? 256 * 48 : (out == O_U8_MERGED ? 256 * 12 : 0);
+}
+
+// (vpp_rois.hip) launches -- or, with `info`, only names -- the kernel of (mode, out, vec, staged); `name` receives the name tsvpp_describe_rois reports
+hipError_t launch_rois(Mode mode, OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
+                       size_t name_len, bool dry_run);
+
+} // namespace tsvpp

@@ -9,6 +9,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_PKG, "..", "lib", "libtsvpp.so"))
 
 TSVPP_MAX_BATCH = 128
+TSVPP_MAX_ROIS = 64  # boxes per launch of tsvpp_convert_rois (their records travel in the kernarg segment)
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
 TSVPP_OPT_UNSAFE_COEFFS = 3
@@ -30,6 +31,12 @@ class Params(ctypes.Structure):
                 ("planes", ctypes.c_int32), ("normalization", ctypes.c_int32)]
 
 
+class Roi(ctypes.Structure):
+    """struct tsvpp_roi: box [left, right) x [top, bottom) of frame `frame` (tsvpp_convert_rois)."""
+    _fields_ = [("frame", ctypes.c_int32), ("left", ctypes.c_int32), ("top", ctypes.c_int32),
+                ("right", ctypes.c_int32), ("bottom", ctypes.c_int32)]
+
+
 class Coeffs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in
                 ("y_scale", "v_to_r", "u_to_b", "v_to_g", "u_to_g", "round_bias", "y_offset", "c_offset")]
@@ -40,7 +47,7 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_channels", "tsvpp_convert", "tsvpp_convert_batch", "tsvpp_prepare", "tsvpp_prepare_batch", "tsvpp_enable_markers", "tsvpp_get_coeffs",
            "tsvpp_set_coeffs", "tsvpp_default_coeffs", "tsvpp_area_pattern", "tsvpp_describe", "tsvpp_strerror", "tsvpp_version",
            "tsvpp_table_create", "tsvpp_table_destroy", "tsvpp_table_set", "tsvpp_convert_table", "tsvpp_trim", "tsvpp_set_option", "tsvpp_get_option", "tsvpp_consumer_next_stream", "tsvpp_consumer_synchronize",
-           "tsvpp_debug_last_launch"]
+           "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois"]
 
 _lib = None
 
@@ -91,6 +98,11 @@ def lib():
     L.tsvpp_default_coeffs.restype = None
     L.tsvpp_area_pattern.argtypes = [ctypes.c_float, vp, i32, ctypes.POINTER(i32)]
     L.tsvpp_describe.argtypes = [pp, i32, i32, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    pr = ctypes.POINTER(Roi)
+    L.tsvpp_convert_rois.argtypes = [vp, i32, pn, i32, pr, pp, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_rois.restype = i32
+    L.tsvpp_describe_rois.argtypes = [pp, i32, pn, i32, pr, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_rois.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_debug_last_launch.restype = i32
     L.tsvpp_strerror.argtypes = [i32]

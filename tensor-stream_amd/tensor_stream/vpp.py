@@ -216,6 +216,30 @@ class VideoProcessor:
         N.check(self._lib.tsvpp_convert_batch(self._ctx, n, frames, ctypes.byref(p), outs, stream))
         return out
 
+    def convert_rois(self, ys, uvs, rois, params, out=None, width=None, height=None):
+        """The cascade behind a detector (tsvpp_convert_rois): every box of `rois` is cut out of its frame, resized to params' width x height,
+        colour-converted and stored to its own output, one launch per 64 boxes.  ys / uvs: the NV12 planes of ONE frame (a pair of 2-D uint8
+        tensors: rows x pitch) or lists of them -- the frames may differ in size and pitch; rois: (left, top, right, bottom) boxes of frame 0 or
+        (frame, left, top, right, bottom); width / height: the frames' picture size (an int for all frames or one per frame; default: the planes'
+        own).  Returns (or fills `out`, indexed out[i]) a tensor of shape (n, ...frame shape) with the padded frame stride of convert_batch
+        (every box starts 16-byte aligned), on torch's current stream."""
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        ys, uvs, boxes = _normalize_rois(ys, uvs, rois)
+        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
+        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
+        n = len(boxes)
+        if n == 0:
+            raise RuntimeError("-3: convert_rois needs at least one box")
+        if out is None:
+            if p.dst_width <= 0 or p.dst_height <= 0 or (p.dst_width | p.dst_height) & 1:
+                raise RuntimeError("-3: convert_rois needs an even, positive output size (width / height of the parameters)")
+            out = self._alloc(p, p.dst_width, p.dst_height, n)  # (a frame of the output size: no stage changes it)
+        recs = (N.Roi * n)(*[N.Roi(*b) for b in boxes])
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        N.check(self._lib.tsvpp_convert_rois(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), outs, stream))
+        return out
+
     def make_batch(self, ys, uvs, params, out=None, width=None, height=None):
         """Pre-builds the descriptor arrays of a batch (the per-frame structs are built once, not per
         call): returns a handle for run_batch().  Keeps the tensors alive."""
@@ -316,6 +340,58 @@ def describe(params, in_w, in_h, pitch=0, n_frames=64, aligned_outputs=True, pit
     buf = ctypes.create_string_buffer(512)
     puv = pitch if pitch_uv is None else pitch_uv
     N.check(N.lib().tsvpp_describe(ctypes.byref(p), in_w, in_h, pitch, puv, n_frames, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def _per_frame(value, n):
+    if value is None or isinstance(value, int):
+        return [value] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError(f"{len(value)} sizes for {n} frames")
+    return value
+
+
+def _normalize_rois(ys, uvs, rois):
+    """The argument forms of convert_rois / describe_rois as (list of luma planes, list of chroma planes, list of (frame, left, top, right, bottom)):
+    one frame may be given as a bare pair of planes, a box of frame 0 as a 4-tuple.  Pure Python: touches no device."""
+    if not isinstance(ys, (list, tuple)):
+        ys, uvs = [ys], [uvs]
+    elif isinstance(uvs, (list, tuple)):
+        ys, uvs = list(ys), list(uvs)
+    else:
+        raise ValueError("ys is a list of planes but uvs is not")
+    if len(ys) != len(uvs) or not ys:
+        raise ValueError(f"{len(ys)} luma planes and {len(uvs)} chroma planes")
+    boxes = []
+    for b in rois:
+        b = tuple(int(v) for v in b)
+        if len(b) == 4:
+            b = (0,) + b
+        if len(b) != 5:
+            raise ValueError(f"a box is (left, top, right, bottom) or (frame, left, top, right, bottom), not {b}")
+        boxes.append(b)
+    return ys, uvs, boxes
+
+
+def describe_rois(params, frames, rois, aligned_outputs=True):
+    """What a convert_rois of this request would launch, as a dict (tsvpp_describe_rois: mode, out, rois, launches, kernel, grid, lds, staged, ...) -- host logic
+    only, works without a GPU.  frames: (width, height) or (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list; rois as for convert_rois."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    if frames and isinstance(frames[0], int):
+        frames = [frames]
+    recs = []
+    for f in frames:
+        f = tuple(int(v) for v in f)
+        w, h = f[0], f[1]
+        py = f[2] if len(f) > 2 else 0
+        puv = f[3] if len(f) > 3 else py
+        recs.append(N.NV12(None, None, py, puv, w, h))
+    _, _, boxes = _normalize_rois([None] * len(recs), [None] * len(recs), rois)
+    fr = (N.NV12 * len(recs))(*recs)
+    bx = (N.Roi * max(len(boxes), 1))(*[N.Roi(*b) for b in boxes])
+    buf = ctypes.create_string_buffer(512)
+    N.check(N.lib().tsvpp_describe_rois(ctypes.byref(p), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

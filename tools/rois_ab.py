@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""A/B: n boxes of a 1080p frame to one NN-input size -- (a) n tsvpp_convert calls with crop set (one launch per box: all the library offered
+before tsvpp_convert_rois) against (b) ONE tsvpp_convert_rois -- on one stream, timed with HIP events.
+
+    python tools/rois_ab.py [--out profiles/rois_ab.txt] [--repeats 20] [--iters 50] [--ns 1,4,16,32,64]
+
+Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the
+MEDIAN block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next frame of a pool of 96 distinct 1080p frames
+(298 MB) and the next output set of a pool, so that neither the 256 MiB last-level cache nor L2 serves a second pass over the same bytes.  Before a
+number is printed both legs are parity-checked against the CPU oracle on the last output set they wrote (every box, bit for bit).
+Both legs are driven through ctypes with pre-built argument objects; leg (a) pays the interpreter's call overhead n times per iteration, leg (b) once
+(a C++ caller pays ~0.5 us less per call): the per-call cost of (a) is therefore an upper bound, the one of (b) is not.
+"bytes" = what a box moves at the least: its output + the source rows and columns it taps (1.5 bytes per box pixel, all of them at these ratios);
+"roofline" = bytes / time as a fraction of 8 TB/s."""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tensor-stream_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import tensor_stream as ts  # noqa: E402
+from oracle import oracle as O  # noqa: E402
+from tensor_stream import _native as N  # noqa: E402
+
+W, H = 1920, 1080
+HBM = 8e12
+CONFIGS = [("224x224 BILINEAR BGR24 planar fp32", (224, 224), 1, 2, 0, True),
+           ("112x112 BILINEAR RGB24 merged uint8", (112, 112), 1, 1, 1, False)]
+
+
+def boxes_for(n, seed):
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        bw, bh = 2 * int(rng.integers(32, 257)), 2 * int(rng.integers(32, 257))  # sides 64 .. 512
+        l, t = int(rng.integers(0, W - bw)), int(rng.integers(0, H - bh))        # strictly inside: Convert's crop stage accepts every one
+        out.append((l, t, l + bw, t + bh))
+    return out
+
+
+def timed(fn, stream, repeats, iters, warm):
+    for k in range(warm):
+        fn(k)
+    stream.synchronize()
+    blocks = []
+    k = warm
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(iters):
+            fn(k)
+            k += 1
+        e1.record(stream)
+        e1.synchronize()
+        blocks.append(e0.elapsed_time(e1) * 1e3 / iters)  # us per iteration
+    return blocks, k - 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rois_ab.txt"))
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--ns", default="1,4,16,32,64")
+    ap.add_argument("--frames", type=int, default=96)
+    a = ap.parse_args()
+    assert a.repeats >= 1 and a.iters >= 1
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    base_y = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev, generator=gen)
+    base_uv = torch.randint(0, 256, (H // 2, W), dtype=torch.uint8, device=dev, generator=gen)
+    ys = [base_y + (37 * k) % 256 for k in range(a.frames)]  # distinct frames: every byte + 37 k (mod 256)
+    uvs = [base_uv + (37 * k) % 256 for k in range(a.frames)]
+    frames = [N.NV12(ys[k].data_ptr(), uvs[k].data_ptr(), W, W, W, H) for k in range(a.frames)]
+    lines = [f"# tools/rois_ab.py: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {a.frames} x 1080p "
+             f"({a.frames * W * H * 3 // 2 >> 20} MiB), median of {a.repeats} blocks of {a.iters} iterations, one stream",
+             "# (a) = n x tsvpp_convert(crop = box)   (b) = 1 x tsvpp_convert_rois   spread = min .. max of the blocks   roofline = moved bytes / time / 8 TB/s"]
+    for name, dst, rt, fcc, planes, norm in CONFIGS:
+        fp = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=rt, pixel_format=fcc, planes_pos=planes, normalization=norm)
+        p = fp.parameters
+        out_bytes = 3 * dst[0] * dst[1] * (4 if norm else 1)
+        lines.append("")
+        lines.append(f"## {name}")
+        lines.append(f"{'n':>3} | {'(a) us/call':>11} {'us/box':>7} {'spread':>15} {'roofline':>8} | {'(b) us/call':>11} {'us/box':>7} {'spread':>15} {'roofline':>8} | {'a / b':>6}")
+        for n in [int(v) for v in a.ns.split(",")]:
+            boxes = boxes_for(n, seed=100 + n)
+            sets = max(2, min(64, (300 << 20) // (n * out_bytes) + 1))
+            pool = [vpp._alloc(p, dst[0], dst[1], n) for _ in range(sets)]
+            moved = sum(out_bytes + (b[2] - b[0]) * (b[3] - b[1]) * 3 // 2 for b in boxes)
+            # leg (a): one parameter block per box (crop = the box), one call per box
+            crops = [ts.FrameParameters(width=dst[0], height=dst[1], crop_coords=b, resize_type=rt, pixel_format=fcc, planes_pos=planes,
+                                        normalization=norm).parameters for b in boxes]
+            crop_refs = [ctypes.byref(c) for c in crops]
+            frame_refs = [ctypes.byref(f) for f in frames]
+            out_ptrs = [[pool[s][i].data_ptr() for i in range(n)] for s in range(sets)]
+            ctx, conv = vpp._ctx, L.tsvpp_convert
+
+            def leg_a(k):
+                fr, ptrs = frame_refs[k % a.frames], out_ptrs[k % sets]
+                for i in range(n):
+                    if conv(ctx, fr, crop_refs[i], ptrs[i], raw) != 0:
+                        raise RuntimeError("tsvpp_convert failed")
+
+            # leg (b): one call
+            recs = (N.Roi * n)(*[N.Roi(0, *b) for b in boxes])
+            out_arrs = [(ctypes.c_void_p * n)(*out_ptrs[s]) for s in range(sets)]
+            frame_arrs = [(N.NV12 * 1)(frames[k]) for k in range(a.frames)]
+            pref, rois = ctypes.byref(p), L.tsvpp_convert_rois
+
+            def leg_b(k):
+                if rois(ctx, 1, frame_arrs[k % a.frames], n, recs, pref, out_arrs[k % sets], raw) != 0:
+                    raise RuntimeError("tsvpp_convert_rois failed")
+
+            res = {}
+            for leg, fn in (("a", leg_a), ("b", leg_b)):
+                for t in pool:
+                    t.zero_()
+                torch.cuda.synchronize()
+                blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(10, a.iters // 2))
+                # parity of the last output set this leg wrote, every box, against the oracle on the sliced planes
+                y, uv = ys[last % a.frames].cpu().numpy(), uvs[last % a.frames].cpu().numpy()
+                got = pool[last % sets]
+                for i, (l, t, r, b) in enumerate(boxes):
+                    ref = O.convert(y[t:b, l:r], uv[t // 2:t // 2 + (b - t) // 2, l:r], dst=dst, resize_type=rt, fourcc=fcc, planes=planes, normalization=norm,
+                                    nthreads=8)[0]
+                    if not np.array_equal(got[i].contiguous().cpu().numpy().ravel().view(np.uint8), ref.view(np.uint8).ravel()):
+                        raise SystemExit(f"PARITY FAILURE: leg ({leg}) {name} n={n} box {i} {(l, t, r, b)}")
+                res[leg] = blocks
+            ma, mb = statistics.median(res["a"]), statistics.median(res["b"])
+            cols = []
+            for m, blocks in ((ma, res["a"]), (mb, res["b"])):
+                cols.append(f"{m:11.2f} {m / n:7.2f} {min(blocks):7.2f}..{max(blocks):<6.2f} {moved / (m * 1e-6) / HBM:8.4f}")
+            lines.append(f"{n:>3} | {cols[0]} | {cols[1]} | {ma / mb:6.2f}")
+            print(lines[-1], flush=True)
+            del pool
+            torch.cuda.empty_cache()
+    lines.append("")
+    lines.append("# parity: both legs bit-exact against the CPU oracle on the last output set of every row")
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
+if __name__ == "__main__":
+    main()

@@ -583,22 +583,16 @@ hipError_t launch_bicubic_cols(OutKind out, bool exact, const LaunchDesc &d, con
     const char *name = exact ? (sparse ? "vpp_bicubic_cols_kernel<OUT, exact, sparse>" : "vpp_bicubic_cols_kernel<OUT, exact, dense>")
                              : (sparse ? "vpp_bicubic_cols_kernel<OUT, tie, sparse>" : "vpp_bicubic_cols_kernel<OUT, tie, dense>");
     // (+ the static exchange slab of the uint8 merged output side)
-    if (describe_only(info, name, grid, lds_bytes + (out == O_U8_MERGED ? MAX_THREADS * 24 : 0))) return hipSuccess;
+    if (describe_only(info, name, grid, lds_bytes + (out == O_U8_MERGED ? out_side_static_lds(out) : 0))) return hipSuccess;
     if (!d.bc_tab) return hipErrorInvalidValue;
-    switch (out) {
-#define TSVPP_BC(O)                                                                                                               \
-    case O:                                                                                                                       \
-        if (exact && sparse) TSVPP_LAUNCH((vpp_bicubic_cols_kernel<O, true, true>), grid, block, lds_bytes, stream, d, t);   \
-        else if (exact) TSVPP_LAUNCH((vpp_bicubic_cols_kernel<O, true, false>), grid, block, lds_bytes, stream, d, t);       \
-        else if (sparse) TSVPP_LAUNCH((vpp_bicubic_cols_kernel<O, false, true>), grid, block, lds_bytes, stream, d, t);      \
-        else TSVPP_LAUNCH((vpp_bicubic_cols_kernel<O, false, false>), grid, block, lds_bytes, stream, d, t);                 \
-        break;
-        TSVPP_BC(O_U8_PLANAR) TSVPP_BC(O_U8_MERGED) TSVPP_BC(O_F32_PLANAR) TSVPP_BC(O_F32_MERGED) TSVPP_BC(O_NV12_U8)
-        TSVPP_BC(O_NV12_F32) TSVPP_BC(O_Y800_U8) TSVPP_BC(O_Y800_F32) TSVPP_BC(O_HSV_F32)
-#undef TSVPP_BC
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_out_kind(out, [&](auto O) {
+        constexpr int OUT = decltype(O)::value;
+        if (exact && sparse) TSVPP_LAUNCH((vpp_bicubic_cols_kernel<OUT, true, true>), grid, block, lds_bytes, stream, d, t);
+        else if (exact) TSVPP_LAUNCH((vpp_bicubic_cols_kernel<OUT, true, false>), grid, block, lds_bytes, stream, d, t);
+        else if (sparse) TSVPP_LAUNCH((vpp_bicubic_cols_kernel<OUT, false, true>), grid, block, lds_bytes, stream, d, t);
+        else TSVPP_LAUNCH((vpp_bicubic_cols_kernel<OUT, false, false>), grid, block, lds_bytes, stream, d, t);
+        return hipGetLastError();
+    });
 }
 
 } // namespace tsvpp

@@ -258,14 +258,7 @@ size_t bicubic_int_table_bytes(int tw, int th, int rows_y, int rows_uv, int hcs_
 hipError_t launch_bicubic_int(OutKind out, const LaunchDesc &d, const FrameTable &t, size_t lds_bytes, hipStream_t stream, LaunchInfo *info) {
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
     if (describe_only(info, "vpp_bicubic_int_kernel<OUT>", grid, lds_bytes)) return hipSuccess;
-    switch (out) {
-#define TSVPP_BI(O) case O: TSVPP_LAUNCH((vpp_bicubic_int_kernel<O>), grid, block, lds_bytes, stream, d, t); break;
-        TSVPP_BI(O_U8_PLANAR) TSVPP_BI(O_U8_MERGED) TSVPP_BI(O_F32_PLANAR) TSVPP_BI(O_F32_MERGED) TSVPP_BI(O_NV12_U8)
-        TSVPP_BI(O_NV12_F32) TSVPP_BI(O_Y800_U8) TSVPP_BI(O_Y800_F32) TSVPP_BI(O_HSV_F32)
-#undef TSVPP_BI
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_out_kind(out, [&](auto O) { TSVPP_LAUNCH((vpp_bicubic_int_kernel<decltype(O)::value>), grid, block, lds_bytes, stream, d, t); return hipGetLastError(); });
 }
 
 } // namespace tsvpp

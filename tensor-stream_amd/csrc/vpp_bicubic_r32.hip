@@ -111,14 +111,7 @@ __global__ __launch_bounds__(MAX_THREADS) void vpp_bicubic_r32_kernel(const Laun
 }
 
 template <int P2> static hipError_t launch_bcr_k(OutKind out, const LaunchDesc &d, const FrameTable &t, dim3 grid, dim3 block, hipStream_t stream) {
-    switch (out) {
-#define TSVPP_BCR(O) case O: TSVPP_LAUNCH((vpp_bicubic_r32_kernel<O, P2>), grid, block, 0, stream, d, t); break;
-        TSVPP_BCR(O_U8_PLANAR) TSVPP_BCR(O_U8_MERGED) TSVPP_BCR(O_F32_PLANAR) TSVPP_BCR(O_F32_MERGED) TSVPP_BCR(O_NV12_U8) TSVPP_BCR(O_NV12_F32)
-        TSVPP_BCR(O_Y800_U8) TSVPP_BCR(O_Y800_F32) TSVPP_BCR(O_HSV_F32)
-#undef TSVPP_BCR
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_out_kind(out, [&](auto O) { TSVPP_LAUNCH((vpp_bicubic_r32_kernel<decltype(O)::value, P2>), grid, block, 0, stream, d, t); return hipGetLastError(); });
 }
 
 // d.r32: 7 = BICUBIC at 3 : 2, 8 = BICUBIC at 2 : 1 (launch_fused)
@@ -126,7 +119,7 @@ hipError_t launch_bicubic_r32(OutKind out, const LaunchDesc &d, const FrameTable
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
     if (d.r32 != 7 && d.r32 != 8) return hipErrorInvalidValue;
     const char *name = d.r32 == 7 ? "vpp_bicubic_r32_kernel<OUT,3:2>" : "vpp_bicubic_r32_kernel<OUT,2:1>";
-    if (describe_only(info, name, grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16)) return hipSuccess;
+    if (describe_only(info, name, grid, out_side_static_lds(out))) return hipSuccess;
     return d.r32 == 7 ? launch_bcr_k<3>(out, d, t, grid, block, stream) : launch_bcr_k<4>(out, d, t, grid, block, stream);
 }
 

@@ -690,33 +690,16 @@ static bool geo_lookup(GeoCache *cache, bool areaup, const LaunchDesc &d, hipStr
 }
 
 static hipError_t launch_bilinear_geo(OutKind out, const LaunchDesc &d, const FrameTable &t, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
-    switch (out) {
-#define TSVPP_GEO(O)                                                                                      \
-    case O:                                                                                               \
-        if (d.tx >= 64) TSVPP_LAUNCH((vpp_bilinear_geo_kernel<O, true>), grid, block, lds, stream, d, t); \
-        else TSVPP_LAUNCH((vpp_bilinear_geo_kernel<O, false>), grid, block, lds, stream, d, t);     \
-        break;
-        TSVPP_GEO(O_U8_PLANAR) TSVPP_GEO(O_U8_MERGED) TSVPP_GEO(O_F32_PLANAR) TSVPP_GEO(O_F32_MERGED) TSVPP_GEO(O_NV12_U8)
-        TSVPP_GEO(O_NV12_F32) TSVPP_GEO(O_Y800_U8) TSVPP_GEO(O_Y800_F32) TSVPP_GEO(O_HSV_F32)
-#undef TSVPP_GEO
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_out_kind(out, [&](auto O) {
+        if (d.tx >= 64) TSVPP_LAUNCH((vpp_bilinear_geo_kernel<decltype(O)::value, true>), grid, block, lds, stream, d, t);
+        else TSVPP_LAUNCH((vpp_bilinear_geo_kernel<decltype(O)::value, false>), grid, block, lds, stream, d, t);
+        return hipGetLastError();
+    });
 }
 
 template <bool AREAUP>
 static hipError_t launch_bilinear_a(OutKind out, const LaunchDesc &d, const FrameTable &t, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
-    switch (out) {
-#define TSVPP_BIL(O)                                                                                                            \
-    case O:                                                                                                                     \
-        TSVPP_LAUNCH((vpp_bilinear_kernel<AREAUP, O>), grid, block, lds, stream, d, t);                                   \
-        break;
-        TSVPP_BIL(O_U8_PLANAR) TSVPP_BIL(O_U8_MERGED) TSVPP_BIL(O_F32_PLANAR) TSVPP_BIL(O_F32_MERGED) TSVPP_BIL(O_NV12_U8)
-        TSVPP_BIL(O_NV12_F32) TSVPP_BIL(O_Y800_U8) TSVPP_BIL(O_Y800_F32) TSVPP_BIL(O_HSV_F32)
-#undef TSVPP_BIL
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_out_kind(out, [&](auto O) { TSVPP_LAUNCH((vpp_bilinear_kernel<AREAUP, decltype(O)::value>), grid, block, lds, stream, d, t); return hipGetLastError(); });
 }
 
 hipError_t launch_bilinear(bool areaup, OutKind out, const LaunchDesc &din, const FrameTable &t, unsigned grid_x, size_t lds_bytes,
@@ -731,7 +714,7 @@ hipError_t launch_bilinear(bool areaup, OutKind out, const LaunchDesc &din, cons
     // fp32 outputs LOSE 8..19 % (headline 0.742 -> 0.658): they are bound by the memory pipeline, and a thread's records are ten
     // 16-byte loads per 8 or 16 pixels -- several times the source bytes the tile stages.  So: uint8 flavours with dyadic weights
     // only; TSVPP_GEO=2 forces the tables wherever they apply, TSVPP_GEO=0 disables them.
-    const bool u8_out = (out == O_U8_PLANAR || out == O_U8_MERGED || out == O_NV12_U8 || out == O_Y800_U8);
+    const bool u8_out = out_u8(out); // (one of the nine flavours of the colour back end here)
     const bool geo_want = d.geo_pref == 2 || (d.geo_pref == 1 && u8_out && d.bil_int == 2);
     const bool geo_ok = geo_want && !d.last_col0 && d.dma && (d.bil_int == 2 || d.bil_win) && (d.pitch_y & 15) == 0 && (d.pitch_uv & 15) == 0;
     if (geo_ok) {

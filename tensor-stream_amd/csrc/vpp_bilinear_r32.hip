@@ -509,14 +509,13 @@ __global__ __launch_bounds__(MAX_THREADS) void vpp_bilinear_r32_kernel(const Lau
 
 template <int KIND, int P2>
 static hipError_t launch_r32_k(OutKind out, const LaunchDesc &d, const FrameTable &t, dim3 grid, dim3 block, hipStream_t stream) {
-    switch (out) {
-#define TSVPP_R32(O) case O: TSVPP_LAUNCH((vpp_bilinear_r32_kernel<O, KIND, P2>), grid, block, 0, stream, d, t); break;
-        TSVPP_R32(O_U8_PLANAR) TSVPP_R32(O_U8_MERGED) TSVPP_R32(O_NV12_U8) TSVPP_R32(O_Y800_U8) TSVPP_R32(O_UYVY_U8) TSVPP_R32(O_YUV444_U8) TSVPP_R32(O_UYVY_F32)
-        TSVPP_R32(O_F32_PLANAR) TSVPP_R32(O_F32_MERGED) TSVPP_R32(O_NV12_F32) TSVPP_R32(O_Y800_F32) TSVPP_R32(O_HSV_F32)
-#undef TSVPP_R32
-    default: return hipErrorInvalidValue;
+    auto launch = [&](auto O) { TSVPP_LAUNCH((vpp_bilinear_r32_kernel<decltype(O)::value, KIND, P2>), grid, block, 0, stream, d, t); return hipGetLastError(); };
+    switch (out) { // the single-pass flavours are this kernel's alone; the rest: the nine of the colour back end
+    case O_UYVY_U8: return launch(std::integral_constant<int, O_UYVY_U8>());
+    case O_YUV444_U8: return launch(std::integral_constant<int, O_YUV444_U8>());
+    case O_UYVY_F32: return launch(std::integral_constant<int, O_UYVY_F32>());
+    default: return with_out_kind(out, launch);
     }
-    return hipGetLastError();
 }
 
 // d.r32: 1 BILINEAR, 2 AREA, 3 NEAREST at 3 : 2; 4 / 5 / 6 the same at 2 : 1 (launch_fused)
@@ -525,7 +524,7 @@ hipError_t launch_bilinear_r32(OutKind out, const LaunchDesc &d, const FrameTabl
     static const char *const names[6] = { "vpp_bilinear_r32_kernel<OUT,bilinear,3:2>", "vpp_bilinear_r32_kernel<OUT,area,3:2>", "vpp_bilinear_r32_kernel<OUT,nearest,3:2>",
                                           "vpp_bilinear_r32_kernel<OUT,bilinear,2:1>", "vpp_bilinear_r32_kernel<OUT,area,2:1>", "vpp_bilinear_r32_kernel<OUT,nearest,2:1>" };
     if (d.r32 < 1 || d.r32 > 6) return hipErrorInvalidValue;
-    if (describe_only(info, names[d.r32 - 1], grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : out == O_UYVY_F32 ? MAX_THREADS * 16 : 16)) return hipSuccess;
+    if (describe_only(info, names[d.r32 - 1], grid, out == O_UYVY_F32 ? MAX_THREADS * 16 /* (its own exchange slab, uslab) */ : out_side_static_lds(out))) return hipSuccess;
     switch (d.r32) {
     case 1: return launch_r32_k<R32_BILINEAR, 3>(out, d, t, grid, block, stream);
     case 2: return launch_r32_k<R32_AREA, 3>(out, d, t, grid, block, stream);

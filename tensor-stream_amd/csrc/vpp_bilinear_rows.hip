@@ -258,20 +258,14 @@ hipError_t launch_bilinear_rows(OutKind out, const LaunchDesc &d, const FrameTab
     static const char *const names[4] = { "vpp_bilinear_rows_kernel<OUT, 2x2>", "vpp_bilinear_rows_kernel<OUT, wx0>", "vpp_bilinear_rows_kernel<OUT, point>",
                                           "vpp_bilinear_rows_kernel<OUT, nearest>" };
     if (describe_only(info, names[kind], grid, lds_bytes)) return hipSuccess;
-    switch (out) {
-#define TSVPP_BR(O)                                                                                                     \
-    case O:                                                                                                             \
-        if (kind == BRK_NEAREST) TSVPP_LAUNCH((vpp_bilinear_rows_kernel<O, BRK_NEAREST>), grid, block, lds_bytes, stream, d, t);  \
-        else if (kind == BRK_POINT) TSVPP_LAUNCH((vpp_bilinear_rows_kernel<O, BRK_POINT>), grid, block, lds_bytes, stream, d, t); \
-        else if (kind == BRK_WX0) TSVPP_LAUNCH((vpp_bilinear_rows_kernel<O, BRK_WX0>), grid, block, lds_bytes, stream, d, t);     \
-        else TSVPP_LAUNCH((vpp_bilinear_rows_kernel<O, BRK_2X2>), grid, block, lds_bytes, stream, d, t);                          \
-        break;
-        TSVPP_BR(O_U8_PLANAR) TSVPP_BR(O_U8_MERGED) TSVPP_BR(O_F32_PLANAR) TSVPP_BR(O_F32_MERGED) TSVPP_BR(O_NV12_U8)
-        TSVPP_BR(O_NV12_F32) TSVPP_BR(O_Y800_U8) TSVPP_BR(O_Y800_F32) TSVPP_BR(O_HSV_F32)
-#undef TSVPP_BR
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_out_kind(out, [&](auto O) {
+        constexpr int OUT = decltype(O)::value;
+        if (kind == BRK_NEAREST) TSVPP_LAUNCH((vpp_bilinear_rows_kernel<OUT, BRK_NEAREST>), grid, block, lds_bytes, stream, d, t);
+        else if (kind == BRK_POINT) TSVPP_LAUNCH((vpp_bilinear_rows_kernel<OUT, BRK_POINT>), grid, block, lds_bytes, stream, d, t);
+        else if (kind == BRK_WX0) TSVPP_LAUNCH((vpp_bilinear_rows_kernel<OUT, BRK_WX0>), grid, block, lds_bytes, stream, d, t);
+        else TSVPP_LAUNCH((vpp_bilinear_rows_kernel<OUT, BRK_2X2>), grid, block, lds_bytes, stream, d, t);
+        return hipGetLastError();
+    });
 }
 
 } // namespace tsvpp

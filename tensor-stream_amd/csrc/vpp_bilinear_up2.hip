@@ -100,15 +100,8 @@ __global__ __launch_bounds__(MAX_THREADS) void vpp_bilinear_up2_kernel(const Lau
 hipError_t launch_bilinear_up2(OutKind out, const LaunchDesc &d, const FrameTable &t, hipStream_t stream, LaunchInfo *info) {
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
     if (d.r32 != 10) return hipErrorInvalidValue;
-    if (describe_only(info, "vpp_bilinear_up2_kernel<OUT>", grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16)) return hipSuccess;
-    switch (out) {
-#define TSVPP_U2(O) case O: TSVPP_LAUNCH((vpp_bilinear_up2_kernel<O>), grid, block, 0, stream, d, t); break;
-        TSVPP_U2(O_U8_PLANAR) TSVPP_U2(O_U8_MERGED) TSVPP_U2(O_F32_PLANAR) TSVPP_U2(O_F32_MERGED) TSVPP_U2(O_NV12_U8) TSVPP_U2(O_NV12_F32)
-        TSVPP_U2(O_Y800_U8) TSVPP_U2(O_Y800_F32) TSVPP_U2(O_HSV_F32)
-#undef TSVPP_U2
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (describe_only(info, "vpp_bilinear_up2_kernel<OUT>", grid, out_side_static_lds(out))) return hipSuccess;
+    return with_out_kind(out, [&](auto O) { TSVPP_LAUNCH((vpp_bilinear_up2_kernel<decltype(O)::value>), grid, block, 0, stream, d, t); return hipGetLastError(); });
 }
 
 } // namespace tsvpp

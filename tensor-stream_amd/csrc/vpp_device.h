@@ -16,8 +16,7 @@ namespace tsvpp {
 // Thread tile: 2 output rows x 4 output columns (= one resized-chroma row of 2 pairs).
 // Workgroup: tx x ty thread tiles (launch-time choice, tx a power of two, tx*ty <= 256), i.e.
 // (4*tx) x (2*ty) output pixels; 32 x 8 threads -> 128 x 16 pixels is the default.
-constexpr int PXW = 4, PXH = 2;
-constexpr int MAX_THREADS = 256;
+constexpr int PXW = 4, PXH = 2; // (MAX_THREADS: vpp_kernels.h)
 constexpr int NUM_XCD = 8;
 
 // Two floats per lane: gfx950 executes v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 on such pairs in

@@ -9,6 +9,7 @@
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #include "tsvpp.h"
 
@@ -17,6 +18,8 @@
 #endif
 
 namespace tsvpp {
+
+constexpr int MAX_THREADS = 256; // threads of the largest workgroup (every kernel's launch bound)
 
 // Resize mode of the fused kernel.  AREA splits in two exactly as the reference's host
 // dispatch does (src/Resize.cu:435): weighted box if both ratios > 1, else the bilinear variant.
@@ -275,6 +278,31 @@ enum OutKind : int { O_U8_PLANAR = 0, O_U8_MERGED, O_F32_PLANAR, O_F32_MERGED, O
                      // flavours of the streaming 3 : 2 / 2 : 1 kernel only (vpp_bilinear_r32.hip): UYVY / YUV444 (uint8) behind such a resize in ONE pass -- everywhere else UYVY /
                      // YUV444 are a second pass over O_NV12_U8 (vpp_formats.hip).  launch_fused answers hipErrorNotSupported when the request is not that kernel's.
                      O_UYVY_U8 = O_COUNT, O_YUV444_U8, O_UYVY_F32 /* round 6: the same, every value / 255 as a float */, O_COUNT_ALL };
+// What the host needs to know about a flavour, said once: the launch selection (vpp_select.hip) and the launchers ask these instead of listing flavours.
+constexpr bool out_stream_only(OutKind o) { return o >= O_COUNT; } // a flavour of the streaming 3 : 2 / 2 : 1 kernel alone (single-pass UYVY / YUV444)
+constexpr bool out_f32(OutKind o) { return o == O_F32_PLANAR || o == O_F32_MERGED || o == O_NV12_F32 || o == O_Y800_F32 || o == O_HSV_F32 || o == O_UYVY_F32; } // fp32 elements
+constexpr bool out_u8(OutKind o) { return o == O_U8_PLANAR || o == O_U8_MERGED || o == O_NV12_U8 || o == O_Y800_U8 || o == O_UYVY_U8 || o == O_YUV444_U8; } // uint8 elements
+constexpr bool out_luma_only(OutKind o) { return o == O_Y800_U8 || o == O_Y800_F32; }                       // Y800: no chroma is sampled
+constexpr bool out_merged3(OutKind o) { return o == O_U8_MERGED || o == O_F32_MERGED || o == O_HSV_F32; }  // three interleaved values per pixel (RGB / BGR triples, HSV)
+// static LDS of the shared 8 x 4 output side (r32_store_tile's exchange slab, vpp_r32_store.h): a lane's merged row piece, 24 / 96 bytes
+constexpr size_t out_side_static_lds(OutKind o) { return out_merged3(o) ? MAX_THREADS * (out_f32(o) ? 96 : 24) : 16; }
+
+// The one place that turns a run-time flavour of the colour back end into a template argument: f(std::integral_constant<int, O_...>()) for the nine
+// flavours below O_COUNT, hipErrorInvalidValue for anything else.  A launcher whose kernel exists for fewer (or more) flavours says so itself.
+template <class F> inline hipError_t with_out_kind(OutKind out, F &&f) {
+    switch (out) {
+    case O_U8_PLANAR: return f(std::integral_constant<int, O_U8_PLANAR>());
+    case O_U8_MERGED: return f(std::integral_constant<int, O_U8_MERGED>());
+    case O_F32_PLANAR: return f(std::integral_constant<int, O_F32_PLANAR>());
+    case O_F32_MERGED: return f(std::integral_constant<int, O_F32_MERGED>());
+    case O_NV12_U8: return f(std::integral_constant<int, O_NV12_U8>());
+    case O_NV12_F32: return f(std::integral_constant<int, O_NV12_F32>());
+    case O_Y800_U8: return f(std::integral_constant<int, O_Y800_U8>());
+    case O_Y800_F32: return f(std::integral_constant<int, O_Y800_F32>());
+    case O_HSV_F32: return f(std::integral_constant<int, O_HSV_F32>());
+    default: return hipErrorInvalidValue;
+    }
+}
 
 // What launch_fused chose (dry run, see tsvpp_describe).
 struct LaunchInfo {
@@ -306,8 +334,32 @@ inline bool describe_only(LaunchInfo *info, const char *name, dim3 grid, size_t 
 // Returns hipError_t.
 // `info` != nullptr: a dry run -- the selection is recorded there and nothing is launched.
 hipError_t launch_fused(Mode mode, OutKind out, bool vec, const LaunchDesc &d, const FrameTable &t, hipStream_t stream, LaunchInfo *info = nullptr);
-// (vpp_kernels.hip, for vpp_select.hip) the kernel of a (mode, flavour) pair as chosen; LDS bytes of the AREA kernels' coordinate tables
-hipError_t launch_mode(Mode mode, OutKind out, bool vec, bool staged, LaunchDesc &d, const FrameTable &t, size_t lds, hipStream_t stream, LaunchInfo *info);
+// The kernel family a fused launch ends in.  launch_fused decides it in ONE place (sel_kernel, vpp_select.hip); launch_mode (vpp_kernels.hip) is a switch over it
+// that calls the family's launcher.  A family still picks its own instance (ratio, tap count, tile height, geometry tables ...) from the descriptor.
+enum FusedKernel : int {
+    FK_STREAM_TAP22,      // BILINEAR / AREA / NEAREST at 3 : 2 / 2 : 1, streaming (vpp_bilinear_r32.hip; d.r32 = 1 .. 6)
+    FK_STREAM_BICUBIC,    // BICUBIC at 3 : 2 / 2 : 1 (vpp_bicubic_r32.hip; d.r32 = 7, 8)
+    FK_UP2,               // BILINEAR at 1 : 2 (vpp_bilinear_up2.hip; d.r32 = 10)
+    FK_REP2,              // 2 x 2 pixel replication at 1 : 2 (vpp_point_rn.hip; d.r32 = 20)
+    FK_POINT_RN,          // point samplers at integer ratios 3 / 4 / 5 (vpp_point_rn.hip; d.r32 >= 100)
+    FK_BILINEAR_ROWS,     // row-segment kernel: sparse BILINEAR and sparse point samplers (vpp_bilinear_rows.hip)
+    FK_POINT,             // LDS point kernel (vpp_point_kernel)
+    FK_TAP22,             // the 2x2-tap family: BILINEAR / AREA up-scale / AREA weights on the integer tile (vpp_bilinear.hip)
+    FK_BICUBIC_INT,       // integer BICUBIC for dyadic weights (vpp_bicubic_int.hip)
+    FK_BICUBIC_COLS,      // BICUBIC, one lane per output column (vpp_bicubic_cols.hip)
+    FK_AREA_STREAM,       // float-weight AREA through a wave-private ring (vpp_area_stream.hip)
+    FK_AREA_BOX,          // AREA at integer horizontal ratios (vpp_area_box.hip)
+    FK_AREA_DIRECT,       // dyadic AREA straight from global memory (vpp_area_direct_kernel)
+    FK_AREA_COLS,         // float-weight AREA, one output column per lane (vpp_area_cols_kernel)
+    FK_AREA_DIRECT_FLOAT, // float-weight AREA straight from global memory (vpp_area_direct_float_kernel)
+    FK_AREA_DYADIC,       // LDS-staged dyadic AREA (vpp_area_dyadic_kernel)
+    FK_AREAF,             // LDS-staged float AREA, at most 3 x 3 taps (vpp_areaf_kernel)
+    FK_COPY16,            // no resize, uint8 Y800 / NV12: plane copy (vpp_copy16_kernel)
+    FK_COLOR,             // no resize: colour conversion alone (vpp_color_kernel)
+    FK_GATHER,            // element-wise byte gathers: every (mode, flavour) pair, aligned outputs or not (vpp_fused_gather_kernel)
+};
+// (vpp_kernels.hip, for vpp_select.hip) launches -- or, in a dry run, names -- the chosen family; LDS bytes of the AREA kernels' coordinate tables
+hipError_t launch_mode(FusedKernel k, Mode mode, OutKind out, bool vec, const LaunchDesc &d, const FrameTable &t, size_t lds, hipStream_t stream, LaunchInfo *info);
 size_t area_dyadic_table_bytes(size_t cols, size_t rows);
 size_t areaf_table_bytes(size_t cols, size_t rows);
 

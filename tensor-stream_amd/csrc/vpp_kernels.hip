@@ -15,6 +15,7 @@
 // Written for wave64 / CDNA4 only; no other target is supported.
 
 #include "vpp_device.h"
+#include "vpp_up2.h"
 
 #pragma clang fp contract(off)
 
@@ -993,129 +994,113 @@ static hipError_t launch_point(const LaunchDesc &d, const FrameTable &t, size_t 
     return info ? hipSuccess : hipGetLastError();
 }
 
-template <int MODE, int OUT>
-static hipError_t launch_mo(bool vec, bool staged, LaunchDesc &d, const FrameTable &t, size_t lds_bytes, hipStream_t stream, LaunchInfo *info) {
-    dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
-    if constexpr (MODE == M_NEAREST || MODE == M_BILINEAR || MODE == M_BICUBIC) {
-        if (d.r32 >= 100) return launch_point_rn((OutKind)OUT, d, t, stream, info);
-    }
-    if constexpr (MODE == M_NEAREST || MODE == M_AREA_UP) {
-        if (d.r32 == 20) return launch_point_rn((OutKind)OUT, d, t, stream, info); // pixel replication at 1 : 2 (vpp_point_rn.hip)
-    }
-    if constexpr (MODE == M_NEAREST || MODE == M_BILINEAR || MODE == M_BICUBIC) { // row-segment kernel: sparse BILINEAR, and (round 6) the point samplers at sparse ratios
-        if (d.bil_rows && (MODE == M_BILINEAR || d.point_kind != PK_NONE)) return launch_bilinear_rows((OutKind)OUT, d, t, lds_bytes, stream, info);
-    }
-    if (staged && d.point_kind != PK_NONE && (MODE == M_NEAREST || MODE == M_BILINEAR || MODE == M_BICUBIC))
-        return launch_point<OUT>(d, t, lds_bytes, stream, info);
-    if constexpr (MODE == M_BILINEAR || MODE == M_AREA_DOWN || MODE == M_NEAREST) {
-        if (d.r32 >= 1 && d.r32 <= 6) return launch_bilinear_r32((OutKind)OUT, d, t, stream, info);
-    }
-    if constexpr (MODE == M_BILINEAR) {
-        if (d.bil_rows) return launch_bilinear_rows((OutKind)OUT, d, t, lds_bytes, stream, info);
-    }
-    if constexpr (MODE == M_BILINEAR || MODE == M_AREA_UP) {
-        if (staged) {
-            return launch_bilinear(MODE == M_AREA_UP, (OutKind)OUT, d, t, grid.x, lds_bytes, stream, info);
-        }
-    } else if constexpr (MODE == M_BICUBIC) {
-        if (d.r32 >= 7) return launch_bicubic_r32((OutKind)OUT, d, t, stream, info);
-        if (d.bicubic_cols) return launch_bicubic_cols((OutKind)OUT, d.bicubic_cols == 2, d, t, lds_bytes, stream, info);
-        if (staged && d.bicubic_int) return launch_bicubic_int((OutKind)OUT, d, t, lds_bytes, stream, info);
-    } else if constexpr (MODE != M_NONE) {
-        if constexpr (MODE == M_AREA_DOWN) {
-            if (d.area_stream) return launch_area_stream((OutKind)OUT, d, t, lds_bytes, stream, info);
-            if (vec && d.area_direct == 1 && d.area_box && !d.force_gather) // integer ratio: contiguous dword runs
-                return launch_area_box((OutKind)OUT, d, t, stream, info);
-            if (vec && d.area_direct == 1 && d.qx && d.qy && !d.force_gather) { // large dyadic ratios: no LDS at all
-                if (d.rx <= 4) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_kernel<1, OUT>", (vpp_area_direct_kernel<1, OUT>), grid, block, 0);
-                else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_kernel<2, OUT>", (vpp_area_direct_kernel<2, OUT>), grid, block, 0);
-                return info ? hipSuccess : hipGetLastError();
-            }
-            if (vec && d.area_direct == 2 && d.area_cols && !d.force_gather) { // one output column per lane, taps straight from global memory
-                const dim3 cblock(MAX_THREADS); // 256 threads whatever the tile height
-                if (d.area_cols_rows == 32) {
-                    if (d.nkx == 1) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<1, 32, OUT>", (vpp_area_cols_kernel<1, 32, OUT>), grid, cblock, 0);
-                    else if (d.nkx == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<2, 32, OUT>", (vpp_area_cols_kernel<2, 32, OUT>), grid, cblock, 0);
-                    else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<3, 32, OUT>", (vpp_area_cols_kernel<3, 32, OUT>), grid, cblock, 0);
-                } else {
-                    if (d.nkx == 1) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<1, 8, OUT>", (vpp_area_cols_kernel<1, 8, OUT>), grid, cblock, 0);
-                    else if (d.nkx == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<2, 8, OUT>", (vpp_area_cols_kernel<2, 8, OUT>), grid, cblock, 0);
-                    else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<3, 8, OUT>", (vpp_area_cols_kernel<3, 8, OUT>), grid, cblock, 0);
-                }
-                return info ? hipSuccess : hipGetLastError();
-            }
-            if (vec && d.area_direct == 2 && !d.force_gather) { // large non-dyadic ratios: float sums straight from global memory
-                if (d.nkx == 1) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_float_kernel<1, OUT>", (vpp_area_direct_float_kernel<1, OUT>), grid, block, 0);
-                else if (d.nkx == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_float_kernel<2, OUT>", (vpp_area_direct_float_kernel<2, OUT>), grid, block, 0);
-                else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_float_kernel<3, OUT>", (vpp_area_direct_float_kernel<3, OUT>), grid, block, 0);
-                return info ? hipSuccess : hipGetLastError();
-            }
-            if (staged && d.qx && d.qy) {
-                if (d.rx <= 4) {
-                    if (d.ry == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<1, 2, OUT>", (vpp_area_dyadic_kernel<1, 2, OUT>), grid, block, lds_bytes);
-                    else if (d.ry == 3) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<1, 3, OUT>", (vpp_area_dyadic_kernel<1, 3, OUT>), grid, block, lds_bytes);
-                    else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<1, 0, OUT>", (vpp_area_dyadic_kernel<1, 0, OUT>), grid, block, lds_bytes);
-                } else {
-                    TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<2, 0, OUT>", (vpp_area_dyadic_kernel<2, 0, OUT>), grid, block, lds_bytes);
-                }
-                return info ? hipSuccess : hipGetLastError();
-            }
-        }
-        if constexpr (MODE == M_AREA_DOWN) {
-            if (staged && d.area2) { // float weights, at most 3 x 3 taps
-                if (d.rx == 2 && d.ry == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<2, 2, OUT>", (vpp_areaf_kernel<2, 2, OUT>), grid, block, lds_bytes);
-                else if (d.rx == 3 && d.ry == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<3, 2, OUT>", (vpp_areaf_kernel<3, 2, OUT>), grid, block, lds_bytes);
-                else if (d.rx == 2 && d.ry == 3) TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<2, 3, OUT>", (vpp_areaf_kernel<2, 3, OUT>), grid, block, lds_bytes);
-                else TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<3, 3, OUT>", (vpp_areaf_kernel<3, 3, OUT>), grid, block, lds_bytes);
-                return info ? hipSuccess : hipGetLastError();
-            }
-        }
-    } else {
-        if constexpr (OUT == O_Y800_U8 || OUT == O_NV12_U8) {
-            if (staged && d.copy16) {
-                TSVPP_LAUNCH_OR_DESCRIBE("vpp_copy16_kernel<OUT>", (vpp_copy16_kernel<OUT>), grid, block, 0);
-                return info ? hipSuccess : hipGetLastError();
-            }
-        }
-        if (staged) { // colour-only fast path ("staged" = eligible)
-            TSVPP_LAUNCH_OR_DESCRIBE("vpp_color_kernel<OUT>", (vpp_color_kernel<OUT>), grid, block, 0);
-            return info ? hipSuccess : hipGetLastError();
-        }
-    }
-    if (vec)
-        TSVPP_LAUNCH_OR_DESCRIBE("vpp_fused_gather_kernel<MODE, OUT, true>", (vpp_fused_gather_kernel<MODE, OUT, true>), grid, block, 0);
-    else // outputs that are not 16-byte aligned: element-wise stores
-        TSVPP_LAUNCH_OR_DESCRIBE("vpp_fused_gather_kernel<MODE, OUT, false>", (vpp_fused_gather_kernel<MODE, OUT, false>), grid, block, 0);
-    return info ? hipSuccess : hipGetLastError();
-}
-
+// The element-wise / byte-gather kernel: every (mode, flavour) pair has one, so nothing falls through it silently.
 template <int MODE>
-static hipError_t launch_m(OutKind out, bool vec, bool staged, LaunchDesc &d, const FrameTable &t, size_t lds, hipStream_t stream, LaunchInfo *info) {
-    switch (out) {
-    case O_U8_PLANAR: return launch_mo<MODE, O_U8_PLANAR>(vec, staged, d, t, lds, stream, info);
-    case O_U8_MERGED: return launch_mo<MODE, O_U8_MERGED>(vec, staged, d, t, lds, stream, info);
-    case O_F32_PLANAR: return launch_mo<MODE, O_F32_PLANAR>(vec, staged, d, t, lds, stream, info);
-    case O_F32_MERGED: return launch_mo<MODE, O_F32_MERGED>(vec, staged, d, t, lds, stream, info);
-    case O_NV12_U8: return launch_mo<MODE, O_NV12_U8>(vec, staged, d, t, lds, stream, info);
-    case O_NV12_F32: return launch_mo<MODE, O_NV12_F32>(vec, staged, d, t, lds, stream, info);
-    case O_Y800_U8: return launch_mo<MODE, O_Y800_U8>(vec, staged, d, t, lds, stream, info);
-    case O_Y800_F32: return launch_mo<MODE, O_Y800_F32>(vec, staged, d, t, lds, stream, info);
-    case O_HSV_F32: return launch_mo<MODE, O_HSV_F32>(vec, staged, d, t, lds, stream, info);
-    default: return hipErrorInvalidValue;
-    }
+static hipError_t launch_gather(OutKind out, bool vec, dim3 grid, dim3 block, const LaunchDesc &d, const FrameTable &t, hipStream_t stream, LaunchInfo *info) {
+    return with_out_kind(out, [&](auto O) {
+        constexpr int OUT = decltype(O)::value;
+        if (vec)
+            TSVPP_LAUNCH_OR_DESCRIBE("vpp_fused_gather_kernel<MODE, OUT, true>", (vpp_fused_gather_kernel<MODE, OUT, true>), grid, block, 0);
+        else // outputs that are not 16-byte aligned: element-wise stores
+            TSVPP_LAUNCH_OR_DESCRIBE("vpp_fused_gather_kernel<MODE, OUT, false>", (vpp_fused_gather_kernel<MODE, OUT, false>), grid, block, 0);
+        return info ? hipSuccess : hipGetLastError();
+    });
 }
 
-// The kernel of a (mode, output flavour) pair as chosen by launch_fused (vpp_select.hip) -- or, with `info`, only its name and grid.
-hipError_t launch_mode(Mode mode, OutKind out, bool vec, bool staged, LaunchDesc &d, const FrameTable &t, size_t lds, hipStream_t stream, LaunchInfo *info) {
-    switch (mode) {
-    case M_NONE: return launch_m<M_NONE>(out, vec, staged, d, t, lds, stream, info);
-    case M_NEAREST: return launch_m<M_NEAREST>(out, vec, staged, d, t, lds, stream, info);
-    case M_BILINEAR: return launch_m<M_BILINEAR>(out, vec, staged, d, t, lds, stream, info);
-    case M_BICUBIC: return launch_m<M_BICUBIC>(out, vec, staged, d, t, lds, stream, info);
-    case M_AREA_DOWN: return launch_m<M_AREA_DOWN>(out, vec, staged, d, t, lds, stream, info);
-    case M_AREA_UP: return launch_m<M_AREA_UP>(out, vec, staged, d, t, lds, stream, info);
-    default: return hipErrorInvalidValue;
+// Launches the kernel family launch_fused chose (vpp_select.hip, sel_kernel) -- or, with `info`, only names it.  The families of other translation units have
+// their own launchers; for the ones that live here the descriptor picks the template instance and with_out_kind the flavour.
+hipError_t launch_mode(FusedKernel k, Mode mode, OutKind out, bool vec, const LaunchDesc &d, const FrameTable &t, size_t lds_bytes, hipStream_t stream, LaunchInfo *info) {
+    const dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
+    auto done = [&] { return info ? hipSuccess : hipGetLastError(); };
+    if (out < 0 || (out_stream_only(out) && k != FK_STREAM_TAP22)) return hipErrorInvalidValue;
+    switch (k) {
+    case FK_STREAM_TAP22: return launch_bilinear_r32(out, d, t, stream, info);
+    case FK_STREAM_BICUBIC: return launch_bicubic_r32(out, d, t, stream, info);
+    case FK_UP2: return launch_bilinear_up2(out, d, t, stream, info);
+    case FK_REP2: // pixel replication at 1 : 2
+    case FK_POINT_RN: return launch_point_rn(out, d, t, stream, info);
+    case FK_BILINEAR_ROWS: return launch_bilinear_rows(out, d, t, lds_bytes, stream, info);
+    case FK_POINT: return with_out_kind(out, [&](auto O) { return launch_point<decltype(O)::value>(d, t, lds_bytes, stream, info); });
+    case FK_TAP22: return launch_bilinear(mode == M_AREA_UP, out, d, t, grid.x, lds_bytes, stream, info);
+    case FK_BICUBIC_COLS: return launch_bicubic_cols(out, d.bicubic_cols == 2, d, t, lds_bytes, stream, info);
+    case FK_BICUBIC_INT: return launch_bicubic_int(out, d, t, lds_bytes, stream, info);
+    case FK_AREA_STREAM: return launch_area_stream(out, d, t, lds_bytes, stream, info);
+    case FK_AREA_BOX: return launch_area_box(out, d, t, stream, info); // integer ratio: contiguous dword runs
+    case FK_AREA_DIRECT: // large dyadic ratios: no LDS at all
+        return with_out_kind(out, [&](auto O) {
+            constexpr int OUT = decltype(O)::value;
+            if (d.rx <= 4) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_kernel<1, OUT>", (vpp_area_direct_kernel<1, OUT>), grid, block, 0);
+            else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_kernel<2, OUT>", (vpp_area_direct_kernel<2, OUT>), grid, block, 0);
+            return done();
+        });
+    case FK_AREA_COLS: // one output column per lane, taps straight from global memory
+        return with_out_kind(out, [&](auto O) {
+            constexpr int OUT = decltype(O)::value;
+            const dim3 cblock(MAX_THREADS); // 256 threads whatever the tile height
+            if (d.area_cols_rows == 32) {
+                if (d.nkx == 1) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<1, 32, OUT>", (vpp_area_cols_kernel<1, 32, OUT>), grid, cblock, 0);
+                else if (d.nkx == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<2, 32, OUT>", (vpp_area_cols_kernel<2, 32, OUT>), grid, cblock, 0);
+                else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<3, 32, OUT>", (vpp_area_cols_kernel<3, 32, OUT>), grid, cblock, 0);
+            } else {
+                if (d.nkx == 1) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<1, 8, OUT>", (vpp_area_cols_kernel<1, 8, OUT>), grid, cblock, 0);
+                else if (d.nkx == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<2, 8, OUT>", (vpp_area_cols_kernel<2, 8, OUT>), grid, cblock, 0);
+                else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_cols_kernel<3, 8, OUT>", (vpp_area_cols_kernel<3, 8, OUT>), grid, cblock, 0);
+            }
+            return done();
+        });
+    case FK_AREA_DIRECT_FLOAT: // large non-dyadic ratios: float sums straight from global memory
+        return with_out_kind(out, [&](auto O) {
+            constexpr int OUT = decltype(O)::value;
+            if (d.nkx == 1) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_float_kernel<1, OUT>", (vpp_area_direct_float_kernel<1, OUT>), grid, block, 0);
+            else if (d.nkx == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_float_kernel<2, OUT>", (vpp_area_direct_float_kernel<2, OUT>), grid, block, 0);
+            else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_direct_float_kernel<3, OUT>", (vpp_area_direct_float_kernel<3, OUT>), grid, block, 0);
+            return done();
+        });
+    case FK_AREA_DYADIC:
+        return with_out_kind(out, [&](auto O) {
+            constexpr int OUT = decltype(O)::value;
+            if (d.rx > 4) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<2, 0, OUT>", (vpp_area_dyadic_kernel<2, 0, OUT>), grid, block, lds_bytes);
+            else if (d.ry == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<1, 2, OUT>", (vpp_area_dyadic_kernel<1, 2, OUT>), grid, block, lds_bytes);
+            else if (d.ry == 3) TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<1, 3, OUT>", (vpp_area_dyadic_kernel<1, 3, OUT>), grid, block, lds_bytes);
+            else TSVPP_LAUNCH_OR_DESCRIBE("vpp_area_dyadic_kernel<1, 0, OUT>", (vpp_area_dyadic_kernel<1, 0, OUT>), grid, block, lds_bytes);
+            return done();
+        });
+    case FK_AREAF: // float weights, at most 3 x 3 taps
+        return with_out_kind(out, [&](auto O) {
+            constexpr int OUT = decltype(O)::value;
+            if (d.rx == 2 && d.ry == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<2, 2, OUT>", (vpp_areaf_kernel<2, 2, OUT>), grid, block, lds_bytes);
+            else if (d.rx == 3 && d.ry == 2) TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<3, 2, OUT>", (vpp_areaf_kernel<3, 2, OUT>), grid, block, lds_bytes);
+            else if (d.rx == 2 && d.ry == 3) TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<2, 3, OUT>", (vpp_areaf_kernel<2, 3, OUT>), grid, block, lds_bytes);
+            else TSVPP_LAUNCH_OR_DESCRIBE("vpp_areaf_kernel<3, 3, OUT>", (vpp_areaf_kernel<3, 3, OUT>), grid, block, lds_bytes);
+            return done();
+        });
+    case FK_COPY16: // the kernel exists for the two flavours that are the source planes themselves
+        return with_out_kind(out, [&](auto O) {
+            constexpr int OUT = decltype(O)::value;
+            if constexpr (OUT == O_Y800_U8 || OUT == O_NV12_U8) {
+                TSVPP_LAUNCH_OR_DESCRIBE("vpp_copy16_kernel<OUT>", (vpp_copy16_kernel<OUT>), grid, block, 0);
+                return done();
+            } else {
+                return hipErrorInvalidValue;
+            }
+        });
+    case FK_COLOR:
+        return with_out_kind(out, [&](auto O) {
+            TSVPP_LAUNCH_OR_DESCRIBE("vpp_color_kernel<OUT>", (vpp_color_kernel<decltype(O)::value>), grid, block, 0);
+            return done();
+        });
+    case FK_GATHER:
+        switch (mode) {
+        case M_NONE: return launch_gather<M_NONE>(out, vec, grid, block, d, t, stream, info);
+        case M_NEAREST: return launch_gather<M_NEAREST>(out, vec, grid, block, d, t, stream, info);
+        case M_BILINEAR: return launch_gather<M_BILINEAR>(out, vec, grid, block, d, t, stream, info);
+        case M_BICUBIC: return launch_gather<M_BICUBIC>(out, vec, grid, block, d, t, stream, info);
+        case M_AREA_DOWN: return launch_gather<M_AREA_DOWN>(out, vec, grid, block, d, t, stream, info);
+        case M_AREA_UP: return launch_gather<M_AREA_UP>(out, vec, grid, block, d, t, stream, info);
+        default: return hipErrorInvalidValue;
+        }
     }
+    return hipErrorInvalidValue;
 }
 // LDS bytes of the coordinate tables of the dyadic / small float AREA kernels for a tile of cols x rows outputs (their entry types live here)
 size_t area_dyadic_table_bytes(size_t cols, size_t rows) { return cols * sizeof(AXEntry) + cols / 2 * sizeof(ACEntry) + (rows + rows / 2) * sizeof(AYEntry); }

@@ -151,14 +151,7 @@ __global__ __launch_bounds__(MAX_THREADS) void vpp_rep2_kernel(const LaunchDesc 
 
 template <int N, int OFF>
 static hipError_t launch_prn(OutKind out, const LaunchDesc &d, const FrameTable &t, dim3 grid, dim3 block, hipStream_t stream) {
-    switch (out) {
-#define TSVPP_PRN(O) case O: TSVPP_LAUNCH((vpp_point_rn_kernel<O, N, OFF>), grid, block, 0, stream, d, t); break;
-        TSVPP_PRN(O_U8_PLANAR) TSVPP_PRN(O_U8_MERGED) TSVPP_PRN(O_NV12_U8) TSVPP_PRN(O_Y800_U8)
-        TSVPP_PRN(O_F32_PLANAR) TSVPP_PRN(O_F32_MERGED) TSVPP_PRN(O_NV12_F32) TSVPP_PRN(O_Y800_F32) TSVPP_PRN(O_HSV_F32)
-#undef TSVPP_PRN
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_out_kind(out, [&](auto O) { TSVPP_LAUNCH((vpp_point_rn_kernel<decltype(O)::value, N, OFF>), grid, block, 0, stream, d, t); return hipGetLastError(); });
 }
 
 // d.r32 = 100 + 10 N + OFF, or 20: replication at 1 : 2 (launch_fused)
@@ -166,15 +159,8 @@ hipError_t launch_point_rn(OutKind out, const LaunchDesc &d, const FrameTable &t
     dim3 grid((unsigned)(d.blocks_per_xcd * NUM_XCD)), block((unsigned)(d.tx * d.ty));
     const char *name = nullptr;
     if (d.r32 == 20) { // pixel replication at 1 : 2 (NEAREST, AREA up-scale)
-        if (describe_only(info, "vpp_rep2_kernel<OUT>", grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16)) return hipSuccess;
-        switch (out) {
-#define TSVPP_REP2(O) case O: TSVPP_LAUNCH((vpp_rep2_kernel<O>), grid, block, 0, stream, d, t); break;
-            TSVPP_REP2(O_U8_PLANAR) TSVPP_REP2(O_U8_MERGED) TSVPP_REP2(O_NV12_U8) TSVPP_REP2(O_Y800_U8)
-            TSVPP_REP2(O_F32_PLANAR) TSVPP_REP2(O_F32_MERGED) TSVPP_REP2(O_NV12_F32) TSVPP_REP2(O_Y800_F32) TSVPP_REP2(O_HSV_F32)
-#undef TSVPP_REP2
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        if (describe_only(info, "vpp_rep2_kernel<OUT>", grid, out_side_static_lds(out))) return hipSuccess;
+        return with_out_kind(out, [&](auto O) { TSVPP_LAUNCH((vpp_rep2_kernel<decltype(O)::value>), grid, block, 0, stream, d, t); return hipGetLastError(); });
     }
     switch (d.r32) {
     case 130: name = "vpp_point_rn_kernel<OUT,3:1,nearest>"; break;
@@ -184,7 +170,7 @@ hipError_t launch_point_rn(OutKind out, const LaunchDesc &d, const FrameTable &t
     case 152: name = "vpp_point_rn_kernel<OUT,5:1,centre>"; break;
     default: return hipErrorInvalidValue;
     }
-    if (describe_only(info, name, grid, out == O_U8_MERGED ? MAX_THREADS * 24 : (out == O_F32_MERGED || out == O_HSV_F32) ? MAX_THREADS * 96 : 16)) return hipSuccess;
+    if (describe_only(info, name, grid, out_side_static_lds(out))) return hipSuccess;
     switch (d.r32) {
     case 130: return launch_prn<3, 0>(out, d, t, grid, block, stream);
     case 131: return launch_prn<3, 1>(out, d, t, grid, block, stream);

@@ -114,25 +114,22 @@ hipError_t launch_mo(bool vec, bool staged, const RoiLaunch &L, unsigned grid, s
     if (vec) return staged ? launch_k<MODE, OUT, true, true>(L, grid, lds, stream) : launch_k<MODE, OUT, true, false>(L, grid, 0, stream);
     return staged ? launch_k<MODE, OUT, false, true>(L, grid, lds, stream) : launch_k<MODE, OUT, false, false>(L, grid, 0, stream);
 }
+// the flavours this kernel is instantiated for: RGB / BGR planar and merged, Y800
+constexpr bool roi_flavour(int out) { return out == O_U8_PLANAR || out == O_U8_MERGED || out == O_F32_PLANAR || out == O_F32_MERGED || out == O_Y800_U8 || out == O_Y800_F32; }
 template <int MODE>
 hipError_t launch_m(OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds, hipStream_t stream) {
-    switch (out) {
-    case O_U8_PLANAR: return launch_mo<MODE, O_U8_PLANAR>(vec, staged, L, grid, lds, stream);
-    case O_U8_MERGED: return launch_mo<MODE, O_U8_MERGED>(vec, staged, L, grid, lds, stream);
-    case O_F32_PLANAR: return launch_mo<MODE, O_F32_PLANAR>(vec, staged, L, grid, lds, stream);
-    case O_F32_MERGED: return launch_mo<MODE, O_F32_MERGED>(vec, staged, L, grid, lds, stream);
-    case O_Y800_U8: return launch_mo<MODE, O_Y800_U8>(vec, staged, L, grid, lds, stream);
-    case O_Y800_F32: return launch_mo<MODE, O_Y800_F32>(vec, staged, L, grid, lds, stream);
-    default: return hipErrorNotSupported; // a missing kernel is an error, never a fallback
-    }
+    return with_out_kind(out, [&](auto O) {
+        constexpr int OUT = decltype(O)::value;
+        if constexpr (roi_flavour(OUT)) return launch_mo<MODE, OUT>(vec, staged, L, grid, lds, stream);
+        else return hipErrorNotSupported; // a missing kernel is an error, never a fallback
+    });
 }
 
 } // namespace
 
 hipError_t launch_rois(Mode mode, OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
                        size_t name_len, bool dry_run) {
-    const bool known = (mode == M_NEAREST || mode == M_BILINEAR || mode == M_BICUBIC) &&
-                       (out == O_U8_PLANAR || out == O_U8_MERGED || out == O_F32_PLANAR || out == O_F32_MERGED || out == O_Y800_U8 || out == O_Y800_F32);
+    const bool known = (mode == M_NEAREST || mode == M_BILINEAR || mode == M_BICUBIC) && roi_flavour(out);
     if (!known) return hipErrorNotSupported;
     if (name && name_len) snprintf(name, name_len, "vpp_rois<%s,%s,%s,%s>", kModeNames[mode], kOutNames[out], vec ? "vec" : "elem", staged ? "staged" : "gather");
     if (dry_run) return hipSuccess;

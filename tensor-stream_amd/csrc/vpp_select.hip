@@ -1,9 +1,10 @@
 // vpp_select.hip -- the HOST side of a launch: which kernel, workgroup shape, rows per thread, staging layout and LDS budget a request gets
-// (launch_fused and its sel_* steps).  No kernel lives here: the choice ends in launch_mode (vpp_kernels.hip) or in one of the per-kernel launchers,
-// so a changed threshold does not touch a kernel's translation unit (bench.py stamps PMC traffic entries with the hash of the dispatched kernel's
-// sources).  tsvpp_describe runs the same code as a dry run; tests/golden/describe_snapshot.json pins its answers for 417 requests.
+// (launch_fused and its sel_* steps).  No kernel lives here.  The sel_* steps fill the descriptor; sel_kernel, the last of them, turns it into ONE kernel
+// family (FusedKernel, vpp_kernels.h), and launch_mode (vpp_kernels.hip) is a switch over that family which calls its launcher -- nothing downstream chooses
+// again, except a family among its own instances.  A changed threshold does not touch a kernel's translation unit (bench.py stamps PMC traffic entries with
+// the hash of the dispatched kernel's sources).  tsvpp_describe runs the same code as a dry run; tests/golden/describe_snapshot.json pins its answers for
+// 417 requests.
 #include "vpp_device.h"
-#include "vpp_up2.h"
 
 namespace tsvpp {
 
@@ -56,7 +57,7 @@ static int stream_select(Mode mode, OutKind out, bool vec, const LaunchDesc &d, 
     // 0 for NEAREST, (N - 1) / 2 for the BILINEAR / BICUBIC requests whose weights are all zero (N odd).  Every flavour of the colour back end.
     // profiles/r05_point_rn_ab.txt: C4 (4K -> 720p BICUBIC -> BGR24 merged uint8) against vpp_point_kernel
     // uint8 flavours only (TSVPP_POINT_RN=2: fp32 too): fp32 outputs lose 5..12 % against the LDS point kernel, whose 4 x 2 thread tiles store whole lines without an exchange
-    const bool prn_u8 = (out == O_U8_PLANAR || out == O_U8_MERGED || out == O_NV12_U8 || out == O_Y800_U8);
+    const bool prn_u8 = out_u8(out) && !out_stream_only(out);
     if (point_kind != PK_NONE && d.point_rn_pref && out < O_COUNT && (prn_u8 || d.point_rn_pref == 2) && (mode == M_NEAREST || mode == M_BILINEAR || mode == M_BICUBIC)) {
         for (int n = 3; n <= 5; n++)
             if ((long)d.src_w == (long)n * d.dst_w && (long)d.src_h == (long)n * d.dst_h) {
@@ -67,9 +68,8 @@ static int stream_select(Mode mode, OutKind out, bool vec, const LaunchDesc &d, 
     const int p2 = (2L * d.src_w == 3L * d.dst_w && 2L * d.src_h == 3L * d.dst_h) ? 3 : ((d.src_w == 2 * d.dst_w && d.src_h == 2 * d.dst_h) ? 4 :
                    ((2 * d.src_w == d.dst_w && 2 * d.src_h == d.dst_h) ? 1 : 0));
     if (!p2) return 0;
-    const bool f32_out = (out == O_F32_PLANAR || out == O_F32_MERGED || out == O_NV12_F32 || out == O_Y800_F32 || out == O_HSV_F32);
-    const bool u8_flavour = (out == O_U8_PLANAR || out == O_U8_MERGED || out == O_NV12_U8 || out == O_Y800_U8 || out == O_UYVY_U8 || out == O_YUV444_U8 ||
-                             out == O_UYVY_F32); // (fp32, but a flavour of this kernel alone: nothing else to lose against)
+    const bool f32_out = out_f32(out) && !out_stream_only(out);
+    const bool u8_flavour = out_u8(out) || out == O_UYVY_F32; // (fp32, but a flavour of this kernel alone: nothing else to lose against)
     int r32 = 0;
     for (const StreamRow &row : kStreamRows)
         if (row.mode == mode && row.p2 == p2) r32 = row.r32;
@@ -93,7 +93,7 @@ static int stream_select(Mode mode, OutKind out, bool vec, const LaunchDesc &d, 
 // Workgroup shape of a streaming launch (thread tile = 8 columns x 4 rows).  Measured: 64 x 4 threads (512 x 16 pixels) +0.4..3 % over 32 x 8 and 16 x 16 for
 // the uint8 flavours of the 2x2-tap kinds (profiles/r02_r32_ab.txt); the exceptions below each carry their file.
 static void stream_shape(int r32, OutKind out, const LaunchDesc &d, int &tx, int &ty) {
-    const bool f32_out = (out == O_F32_PLANAR || out == O_F32_MERGED || out == O_NV12_F32 || out == O_Y800_F32 || out == O_HSV_F32);
+    const bool f32_out = out_f32(out) && !out_stream_only(out); // (single-pass UYVY fp32 keeps the uint8 flavours' shapes)
     const int n = d.dst_w / 8; // threads per output row
     auto waste = [&](int w) { return (double)((n + w - 1) / w * w) / (double)n - 1.0; };
     tx = 64;
@@ -146,7 +146,7 @@ static void sel_tap22(Mode &mode, OutKind out, bool vec, LaunchDesc &d) {
     // TSVPP_BILINEAR_INT=0 / 2 switch it off.
     d.tap22 = 0;
     {
-        const bool f32 = (out == O_F32_PLANAR || out == O_F32_MERGED || out == O_NV12_F32 || out == O_Y800_F32); // (Y800: round 6, with two row pairs per thread -- see sel_staged)
+        const bool f32 = out_f32(out) && !out_stream_only(out) && out != O_HSV_F32; // (not HSV: see above.  Y800: round 6, with two row pairs per thread -- see sel_staged)
         const bool r32x = 2L * d.src_w == 3L * d.dst_w && 2L * d.src_h == 3L * d.dst_h, r21 = d.src_w == 2 * d.dst_w && d.src_h == 2 * d.dst_h;
         // (4 k + 2 columns: the tail launch samples by MODE)
         if (!d.tap22_off && f32 && vec && !d.force_gather && d.bil_int_pref == 1 && d.r32_pref != 2 && (r32x || r21) && (d.dst_w & 3) == 0 && mode == M_AREA_DOWN && d.qx && d.qy &&
@@ -179,8 +179,8 @@ static void sel_store_policy(Mode mode, OutKind out, bool vec, LaunchDesc &d) {
         // fp32 outputs: every store instruction of a wave covers whole 128-byte lines (planar: 16 contiguous
         // bytes per lane; merged: after the in-wave exchange of MergedRun) and nothing re-reads them.  The
         // scalar fallback of merged outputs (!vec) interleaves partial lines: plain stores, L2 combines them.
-        const bool f32_lines = (out == O_F32_PLANAR || out == O_NV12_F32 || out == O_Y800_F32) || (vec && (out == O_F32_MERGED || out == O_HSV_F32));
-        const bool f32_partial = !vec && (out == O_F32_MERGED || out == O_HSV_F32);
+        const bool f32 = out_f32(out) && !out_stream_only(out), f32_merged = f32 && out_merged3(out);
+        const bool f32_partial = !vec && f32_merged, f32_lines = f32 && !f32_partial;
         d.nt_stores = f32_partial ? 0 : ((mode == M_NONE && f32_lines) ? 2 : 1);
         // The colour-only kernel's variant 2 was chosen on C2 (1080p planar fp32: 0.71 against 0.66 on variant 1) -- and holds for three-plane / merged outputs 1920 and 2048
         // columns wide only (round 6, profiles/r06_color_shapes.txt part 5): Y800 fp32 gains 6-22 % on variant 1 at every size (1080p 0.74 -> 0.79, 720p 0.70 -> 0.85, 4K 0.74 ->
@@ -198,13 +198,16 @@ static void sel_store_policy(Mode mode, OutKind out, bool vec, LaunchDesc &d) {
         if (out == O_F32_PLANAR && vec && ((size_t)d.dst_w * 4) % 64 != 0 && d.dst_w >= 800) d.nt_stores = 0;
         // ... and the colour-only kernel with EVERY fp32 flavour (profiles/r06_row_alignment.txt, part 6): 1366 x 768 merged 0.44 -> 0.55, HSV 0.43 -> 0.53, NV12 0.46 -> 0.57,
         // Y800 0.45 -> 0.56 (behind a resize those flavours tie or lose with plain stores: the LDS kernels keep their non-temporal ones)
-        if (mode == M_NONE && vec && (out == O_F32_MERGED || out == O_HSV_F32 || out == O_NV12_F32 || out == O_Y800_F32) && d.dst_w >= 800 &&
-            ((size_t)d.dst_w * 4 * ((out == O_F32_MERGED || out == O_HSV_F32) ? 3 : 1)) % 64 != 0)
+        if (mode == M_NONE && vec && f32 && out != O_F32_PLANAR /* (its own rule above) */ && d.dst_w >= 800 && ((size_t)d.dst_w * 4 * (f32_merged ? 3 : 1)) % 64 != 0)
             d.nt_stores = 0;
     }
 }
 
 // 4. candidate workgroup shapes
+static void prefer_64x4(int (&shapes)[5][2]) { // 64 x 4 to the front of the list, the first three candidates one place down
+    for (int i = 3; i > 0; i--) { shapes[i][0] = shapes[i - 1][0]; shapes[i][1] = shapes[i - 1][1]; }
+    shapes[0][0] = 64; shapes[0][1] = 4;
+}
 static void sel_shapes(Mode mode, OutKind out, LaunchDesc &d, FusedSel &S) {
     int (&shapes)[5][2] = S.shapes;
     const bool f32_out = S.f32_out, two_tap = S.two_tap;
@@ -219,28 +222,19 @@ static void sel_shapes(Mode mode, OutKind out, LaunchDesc &d, FusedSel &S) {
     // fills them (a half-empty last tile column costs more than the pattern gains: 1920-wide outputs stay on 128).
     // (the point samplers write the same pattern: NEAREST 1080p -> 720p 0.770 -> 0.795 on 64 x 4, profiles/r04_shape_sweep_misc.txt)
     if ((two_tap || (d.point_kind != PK_NONE && (mode == M_NEAREST || mode == M_BILINEAR || mode == M_BICUBIC))) && f32_out && d.dst_w % 256 == 0) {
-        shapes[3][0] = shapes[2][0]; shapes[3][1] = shapes[2][1];
-        shapes[2][0] = shapes[1][0]; shapes[2][1] = shapes[1][1];
-        shapes[1][0] = shapes[0][0]; shapes[1][1] = shapes[0][1];
-        shapes[0][0] = 64; shapes[0][1] = 4;
+        prefer_64x4(shapes);
     }
     // The colour-only kernel (no resize) with planar fp32 outputs writes the same three-plane pattern (round 6, profiles/r06_color_shapes.txt): at output widths that are
     // multiples of 256 its 32 x 8 workgroups (128 x 16 pixels) reach 0.62-0.64 of the roofline at 1280 / 2560 / 3840 columns against 0.73-0.74 at 1920 -- and 0.72-0.74 on
     // 64 x 4 (256 x 8 pixels: 1 KiB row segments per plane); 2048 columns 0.73 -> 0.76.  1024 and 640 columns do not care (-1.5 % / 0), uint8 planar loses at 1280 (-6 %).
     if (mode == M_NONE && out == O_F32_PLANAR && d.dst_w % 256 == 0 && d.dst_w >= 1280) {
-        shapes[3][0] = shapes[2][0]; shapes[3][1] = shapes[2][1];
-        shapes[2][0] = shapes[1][0]; shapes[2][1] = shapes[1][1];
-        shapes[1][0] = shapes[0][0]; shapes[1][1] = shapes[0][1];
-        shapes[0][0] = 64; shapes[0][1] = 4;
+        prefer_64x4(shapes);
     }
     // uint8 outputs on the integer window tile read host-built geometry tables (vpp_bilinear.hip): with workgroups 64 thread tiles
     // wide a wave's lanes share their output rows and the row records are scalar loads -- measured (profiles/r02_geo_ab.txt)
     // 1080p -> 720p planar 0.545 -> 0.570, merged 0.481 -> 0.506, 4K -> 1080p 0.706 -> 0.717 against 32 x 8
     if (two_tap && !f32_out && d.bil_int == 2 && d.geo_pref && d.dma && (d.pitch_y & 15) == 0 && (d.pitch_uv & 15) == 0 && d.dst_w >= 256) {
-        shapes[3][0] = shapes[2][0]; shapes[3][1] = shapes[2][1];
-        shapes[2][0] = shapes[1][0]; shapes[2][1] = shapes[1][1];
-        shapes[1][0] = shapes[0][0]; shapes[1][1] = shapes[0][1];
-        shapes[0][0] = 64; shapes[0][1] = 4;
+        prefer_64x4(shapes);
     }
     if (d.shape_tx > 0 && d.shape_ty > 0 && (d.shape_tx & (d.shape_tx - 1)) == 0 && d.shape_tx * d.shape_ty <= MAX_THREADS &&
         d.shape_tx * d.shape_ty >= 64) {
@@ -560,7 +554,7 @@ static void sel_bicubic_cols(Mode mode, OutKind out, bool vec, int stream_r32, L
         auto wave_bytes_of = [&](int r) { return ring_bytes + 64 * (col_stride(r) + r + r / 2); };
         // the uint8 merged flavour's output side (r32_store_tile, vpp_r32_store.h) carries a STATIC exchange slab of MAX_THREADS x 24 bytes on top of the dynamic LDS,
         // whether or not bc_u8x is chosen at run time: part of the workgroup's LDS for both budgets below and for info->lds_bytes
-        const int static_lds = out == O_U8_MERGED ? MAX_THREADS * 24 : 0;
+        const int static_lds = out == O_U8_MERGED ? (int)out_side_static_lds(out) : 0;
         // Tile height, measured (profiles/r03_bicubic_cols_ab*.txt): 32 rows for up-scales (few source rows per tile: the seams cost
         // most there; 720p -> 1080p 0.519 against 0.502 at 16), 16 rows while the launch still has 8 waves per SIMD (1080p -> 640^2 0.620
         // against 0.609 at 8, 4K -> 1080p 0.651 against 0.624), else 8 (1080p -> 224^2 0.748 against 0.642, -> 300^2 0.404 against 0.367)
@@ -601,6 +595,47 @@ static void sel_bicubic_cols(Mode mode, OutKind out, bool vec, int stream_r32, L
     }
 }
 
+// 9. the kernel family, from what the steps above left in the descriptor: first match wins.  The ONLY place that reads those flags as a choice -- launch_mode
+// (vpp_kernels.hip) launches what this returns.  `staged`: FusedSel::staged as launch_fused leaves it (for M_NONE: the colour-only fast path is eligible).
+static FusedKernel sel_kernel(Mode mode, OutKind out, bool vec, bool staged, const LaunchDesc &d) {
+    const bool nbb = mode == M_NEAREST || mode == M_BILINEAR || mode == M_BICUBIC; // the modes a point sampler can come from
+    if (out_stream_only(out)) return FK_STREAM_TAP22; // (launch_fused has checked d.r32; the launcher checks that it is one of ITS kinds)
+    if (d.r32 == 10) return FK_UP2;
+    if (nbb && d.r32 >= 100) return FK_POINT_RN;
+    if ((mode == M_NEAREST || mode == M_AREA_UP) && d.r32 == 20) return FK_REP2;
+    if (nbb && d.bil_rows && (mode == M_BILINEAR || d.point_kind != PK_NONE)) return FK_BILINEAR_ROWS; // sparse BILINEAR, and (round 6) the point samplers at sparse ratios
+    if (nbb && staged && d.point_kind != PK_NONE) return FK_POINT;
+    if ((mode == M_BILINEAR || mode == M_AREA_DOWN || mode == M_NEAREST) && d.r32 >= 1 && d.r32 <= 6) return FK_STREAM_TAP22;
+    switch (mode) {
+    case M_BILINEAR: // (a second `d.bil_rows` test stood here: the row-segment line above takes every BILINEAR request with d.bil_rows)
+    case M_AREA_UP:
+        if (staged) return FK_TAP22;
+        break;
+    case M_BICUBIC:
+        if (d.r32 >= 7) return FK_STREAM_BICUBIC;
+        if (d.bicubic_cols) return FK_BICUBIC_COLS;
+        if (staged && d.bicubic_int) return FK_BICUBIC_INT;
+        break;
+    case M_AREA_DOWN: {
+        const bool direct = vec && !d.force_gather; // (sel_area sets area_direct only under both; asked again as before)
+        if (d.area_stream) return FK_AREA_STREAM;
+        if (direct && d.area_direct == 1 && d.area_box) return FK_AREA_BOX;
+        if (direct && d.area_direct == 1 && d.qx && d.qy) return FK_AREA_DIRECT;
+        if (direct && d.area_direct == 2 && d.area_cols) return FK_AREA_COLS;
+        if (direct && d.area_direct == 2) return FK_AREA_DIRECT_FLOAT;
+        if (staged && d.qx && d.qy) return FK_AREA_DYADIC;
+        if (staged && d.area2) return FK_AREAF;
+        break;
+    }
+    case M_NONE:
+        if (staged && d.copy16 && (out == O_Y800_U8 || out == O_NV12_U8)) return FK_COPY16;
+        if (staged) return FK_COLOR; // colour-only fast path ("staged" = eligible)
+        break;
+    default: break; // M_NEAREST: a point sampler above, or gathers
+    }
+    return FK_GATHER;
+}
+
 hipError_t launch_fused(Mode mode, OutKind out, bool vec, const LaunchDesc &din, const FrameTable &t, hipStream_t stream, LaunchInfo *info) {
     LaunchDesc d = din;
     d.rpt = 1;
@@ -609,9 +644,9 @@ hipError_t launch_fused(Mode mode, OutKind out, bool vec, const LaunchDesc &din,
     const Mode mode_in = mode;
     sel_tap22(mode, out, vec, d);
     sel_two_tap_forms(mode, d);
-    d.luma_only = (out == O_Y800_U8 || out == O_Y800_F32) ? 1 : 0;
+    d.luma_only = out_luma_only(out) ? 1 : 0;
     sel_store_policy(mode, out, vec, d);
-    S.f32_out = (out == O_F32_PLANAR || out == O_F32_MERGED || out == O_NV12_F32 || out == O_Y800_F32 || out == O_HSV_F32);
+    S.f32_out = out_f32(out) && !out_stream_only(out);
     S.two_tap = (mode == M_BILINEAR || mode == M_AREA_UP);
     S.lds_budget = (size_t)(d.lds_budget_kb > 0 ? d.lds_budget_kb : 40) * 1024; // TSVPP_LDS_KB
     sel_shapes(mode, out, d, S);
@@ -726,13 +761,9 @@ hipError_t launch_fused(Mode mode, OutKind out, bool vec, const LaunchDesc &din,
     } else if (g_launch_rec && g_launch_rec->count == 0) {
         g_launch_rec->staged = staged ? 1 : 0; // (tsvpp_debug_last_launch)
     }
-    auto dispatch = [&](bool v, bool st, LaunchDesc &dd, size_t lds, LaunchInfo *inf) { return launch_mode(mode, out, v, st, dd, t, lds, stream, inf); };
-    if (out >= O_COUNT) { // flavours of the streaming kernel alone (O_UYVY_U8, O_YUV444_U8): the caller falls back to two passes
-        if (!d.r32) return hipErrorNotSupported;
-        return launch_bilinear_r32(out, d, t, stream, info);
-    }
-    if (d.r32 == 10) return launch_bilinear_up2(out, d, t, stream, info); // (its launcher is not vpp_kernels.hip's business: vpp_up2.h)
-    hipError_t e = dispatch(vec, staged, d, lds_bytes, info);
+    if (out_stream_only(out) && !d.r32) return hipErrorNotSupported; // (O_UYVY_U8, O_YUV444_U8, O_UYVY_F32 behind another kernel: the caller falls back to two passes)
+    hipError_t e = launch_mode(sel_kernel(mode, out, vec, staged, d), mode, out, vec, d, t, lds_bytes, stream, info);
+    // (the streaming kernels never get here with a row tail: d.r32 implies dst_w % 8 == 0)
     if (e != hipSuccess || !vec || (d.dst_w & 3) == 0 || d.last_col0 > 0) return e;
     // dst_w = 4 k + 2 without the shifted tile column: the vector-store kernels left the last two columns of every row alone (is_row_tail); one
     // more, tiny launch of the element-wise gather kernel converts them: workgroup = 1 x 64 thread tiles of 2 columns x 2 rows
@@ -761,7 +792,7 @@ hipError_t launch_fused(Mode mode, OutKind out, bool vec, const LaunchDesc &din,
         const long G = 1L << (td.tile_order - 2);
         td.blocks_per_xcd = (int)(((rows + G * NUM_XCD - 1) / (G * NUM_XCD)) * G);
     }
-    return dispatch(false, false, td, 0, nullptr);
+    return launch_mode(FK_GATHER, mode, out, false, td, t, 0, stream, nullptr);
 }
 
 } // namespace tsvpp

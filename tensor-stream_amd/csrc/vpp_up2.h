@@ -1,4 +1,4 @@
-// vpp_up2.h -- launcher of the streaming 1 : 2 up-scale kernel (vpp_bilinear_up2.hip), shared with the launch selection (vpp_select.hip) only.
+// vpp_up2.h -- launcher of the streaming 1 : 2 up-scale kernel (vpp_bilinear_up2.hip), shared with launch_mode (vpp_kernels.hip) only.
 #pragma once
 #include "vpp_kernels.h"
 

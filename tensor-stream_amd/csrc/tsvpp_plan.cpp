@@ -1,0 +1,252 @@
+// tsvpp_plan.cpp -- a request resolved on the host alone: tsvpp_params (+ frame geometry, + boxes) -> Plan / RoiPlan.  No HIP runtime call.
+// The order in which make_plan and rois_plan return their statuses is part of the ABI (tests/test_plan_cpu.py, test_rois_cpu.py, test_abi_cpu.py).
+#include <cmath>
+
+#include "tsvpp_host.h"
+#include "vpp_rois.h"
+
+using namespace tsvpp;
+
+namespace {
+
+// Per-thread memo of a geometry predicate: a consumer thread converts thousands of frames with a handful of geometries (a
+// full scan of a dyadic request costs dst_w + dst_h coordinate evaluations, ~20 us -- several single-frame conversions).
+struct GeomMemo {
+    struct Entry { int cls, dw, dh, sw, sh; bool res; };
+    Entry e[16];
+    int n = 0, next = 0;
+    const bool *find(int cls, int dw, int dh, int sw, int sh) const {
+        for (int i = 0; i < n; i++)
+            if (e[i].cls == cls && e[i].dw == dw && e[i].dh == dh && e[i].sw == sw && e[i].sh == sh) return &e[i].res;
+        return nullptr;
+    }
+    bool put(int cls, int dw, int dh, int sw, int sh, bool res) {
+        e[next] = Entry{ cls, dw, dh, sw, sh, res };
+        next = (next + 1) % 16;
+        if (n < 16) n++;
+        return res;
+    }
+};
+
+// Is every interpolation weight of this request zero?  (odd integer ratios; then BILINEAR and
+// BICUBIC reduce exactly to their centre tap, src/Resize.cu:17-23, 45-50 with w = 0)
+bool all_weights_zero(Mode m, int dst_w, int dst_h, float xr, float yr, int src_w, int src_h) {
+    static thread_local GeomMemo memo;
+    if (const bool *hit = memo.find((int)m, dst_w, dst_h, src_w, src_h)) return *hit;
+    auto remember = [&](bool r) { return memo.put((int)m, dst_w, dst_h, src_w, src_h, r); };
+    for (int axis = 0; axis < 2; axis++) {
+        const int n = axis ? dst_h : dst_w, lim = axis ? src_h : src_w;
+        const float r = axis ? yr : xr;
+        for (int o = 0; o < n; o++) { // the chroma grid uses indices 0 .. n/2-1, a subset
+            int p;
+            if (m == M_BILINEAR) {
+                float w;
+                bilinear_axis(o, r, lim, p, w);
+                if (w != 0.0f) return remember(false);
+            } else {
+                double w;
+                bicubic_axis(o, r, lim, p, w);
+                if (w != 0.0) return remember(false);
+            }
+        }
+    }
+    return remember(true);
+}
+
+// BILINEAR: is every weight of ONE axis zero (an odd integer ratio on that axis only -- BASELINE config C3: 1280 -> 256 columns, ratio 5, rows at
+// 2.8125)?  The taps that a zero weight multiplies need not be fetched (sample_luma / sample_chroma: LaunchDesc::wx_zero / wy_zero).
+bool axis_weights_zero(int axis, int n, int lim, float r) {
+    static thread_local GeomMemo memo;
+    if (const bool *hit = memo.find(axis, n, 0, lim, 0)) return *hit;
+    for (int o = 0; o < n; o++) {
+        int p;
+        float w;
+        bilinear_axis(o, r, lim, p, w);
+        if (w != 0.0f) return memo.put(axis, n, 0, lim, 0, false);
+    }
+    return memo.put(axis, n, 0, lim, 0, true);
+}
+
+// Is every interpolation weight of this request a multiple of 1/16?  (ratios 1.5, 2, 2.5, 4, 0.5, 1.25, 2.25 ...: then the
+// reference's float / double evaluation is exact and the integer kernels -- vpp_bicubic_int.hip, the integer thread tile of
+// the 2x2-tap kernel -- reproduce it bit for bit.)  BILINEAR and BICUBIC share one coordinate formula (src/Resize.cu:276-303,
+// 321-347); the AREA up-scale variant has its own (:221-234).
+bool weights_dyadic(Mode m, int dst_w, int dst_h, float xr, float yr, int src_w, int src_h) {
+    static thread_local GeomMemo memo;
+    const int cls = (m == M_AREA_UP) ? 1 : 0;
+    if (const bool *hit = memo.find(cls, dst_w, dst_h, src_w, src_h)) return *hit;
+    auto remember = [&](bool r) { return memo.put(cls, dst_w, dst_h, src_w, src_h, r); };
+    for (int axis = 0; axis < 2; axis++) {
+        const int n = axis ? dst_h : dst_w, lim = axis ? src_h : src_w;
+        const float r = axis ? yr : xr;
+        for (int o = 0; o < n; o++) { // the chroma grid uses indices 0 .. n/2-1, a subset
+            int p;
+            float w;
+            if (m == M_AREA_UP) areaup_axis(o, r, p, w);
+            else bilinear_axis(o, r, lim, p, w); // bicubic_axis: the same fp32 coordinate, widened afterwards
+            const float s = w * 16.0f;
+            if (s != std::floor(s)) return remember(false);
+        }
+    }
+    return remember(true);
+}
+
+// resize_type -> Mode.  AREA answers M_AREA_DOWN: make_plan splits it by the ratios, rois_plan refuses it.  False: unknown (the reference launches nothing and
+// returns garbage).
+bool resize_mode(int resize_type, Mode &m) {
+    switch (resize_type) {
+    case TSVPP_NEAREST: m = M_NEAREST; return true;
+    case TSVPP_BILINEAR: m = M_BILINEAR; return true;
+    case TSVPP_BICUBIC: m = M_BICUBIC; return true;
+    case TSVPP_AREA: m = M_AREA_DOWN; return true;
+    default: return false;
+    }
+}
+
+// The colour and luma flavours of the fused kernels: RGB24 / BGR24 by layout and element type, Y800 by element type.  False: another FourCC (make_plan's own).
+bool color_flavour(int fourcc, int planes, bool f32, OutKind &out, int &swap_rb) {
+    switch (fourcc) {
+    case TSVPP_RGB24: case TSVPP_BGR24:
+        swap_rb = fourcc == TSVPP_BGR24 ? 1 : 0;
+        out = f32 ? (planes == TSVPP_PLANAR ? O_F32_PLANAR : O_F32_MERGED) : (planes == TSVPP_PLANAR ? O_U8_PLANAR : O_U8_MERGED);
+        return true;
+    case TSVPP_Y800:
+        swap_rb = 0;
+        out = f32 ? O_Y800_F32 : O_Y800_U8;
+        return true;
+    default: return false;
+    }
+}
+
+} // namespace
+
+namespace tsvpp {
+
+// Stage selection of VideoProcessor::Convert (reference src/VideoProcessor.cpp:106-142).
+int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl) {
+    if (!p || in_w <= 0 || in_h <= 0) return TSVPP_ERROR;
+    if ((in_w | in_h) & 1) return TSVPP_UNSUPPORTED; // NV12 needs even sizes (reference: undefined)
+    const int cw = p->crop_right - p->crop_left, ch = p->crop_bottom - p->crop_top;
+    // crop only if the box is strictly smaller in BOTH dimensions (src/VideoProcessor.cpp:109)
+    const bool crop = cw > 0 && ch > 0 && cw < in_w && ch < in_h;
+    pl.src_w = in_w;
+    pl.src_h = in_h;
+    pl.off_x = pl.off_y = 0;
+    if (crop) {
+        if (p->crop_left < 0 || p->crop_top < 0 || p->crop_right > in_w || p->crop_bottom > in_h) return TSVPP_ERROR;
+        if ((cw | ch) & 1) return TSVPP_UNSUPPORTED; // reference writes chroma out of bounds here
+        pl.src_w = cw;
+        pl.src_h = ch;
+        pl.off_x = p->crop_left;
+        pl.off_y = p->crop_top;
+    }
+    pl.dst_w = pl.src_w;
+    pl.dst_h = pl.src_h;
+    pl.mode = M_NONE;
+    pl.xr = pl.yr = 1.0f;
+    if (p->dst_width < 0 || p->dst_height < 0) return TSVPP_ERROR;
+    if (p->dst_width && p->dst_height && (p->dst_width != pl.src_w || p->dst_height != pl.src_h)) {
+        if ((p->dst_width | p->dst_height) & 1) return TSVPP_UNSUPPORTED; // reference leaves chroma unwritten
+        pl.dst_w = p->dst_width;
+        pl.dst_h = p->dst_height;
+        pl.xr = (float)pl.src_w / (float)pl.dst_w; // src/Resize.cu:418-419
+        pl.yr = (float)pl.src_h / (float)pl.dst_h;
+        if (!resize_mode(p->resize_type, pl.mode)) return TSVPP_UNSUPPORTED;
+        if (pl.mode == M_AREA_DOWN && !(pl.xr > 1.0f && pl.yr > 1.0f)) pl.mode = M_AREA_UP; // src/Resize.cu:435
+    }
+    pl.point_kind = PK_NONE;
+    if (pl.mode == M_NEAREST) pl.point_kind = PK_NEAREST;
+    else if ((pl.mode == M_BILINEAR || pl.mode == M_BICUBIC) && all_weights_zero(pl.mode, pl.dst_w, pl.dst_h, pl.xr, pl.yr, pl.src_w, pl.src_h))
+        pl.point_kind = pl.mode == M_BILINEAR ? PK_BILINEAR0 : PK_BICUBIC0;
+    pl.wx_zero = pl.wy_zero = 0;
+    if (pl.mode == M_BILINEAR && pl.point_kind == PK_NONE) {
+        pl.wx_zero = axis_weights_zero(0, pl.dst_w, pl.src_w, pl.xr) ? 1 : 0;
+        pl.wy_zero = (!pl.wx_zero && axis_weights_zero(1, pl.dst_h, pl.src_h, pl.yr)) ? 1 : 0;
+    }
+    pl.w_dyadic = ((pl.mode == M_BICUBIC || pl.mode == M_BILINEAR || pl.mode == M_AREA_UP) && pl.point_kind == PK_NONE &&
+                   weights_dyadic(pl.mode, pl.dst_w, pl.dst_h, pl.xr, pl.yr, pl.src_w, pl.src_h)) ? 1 : 0;
+    pl.fourcc = p->fourcc;
+    switch (p->fourcc) {
+    case TSVPP_RGB24: case TSVPP_BGR24: case TSVPP_Y800: case TSVPP_NV12: case TSVPP_HSV: break; // output flavours of the fused kernels
+    case TSVPP_UYVY: case TSVPP_YUV444: break;                                                    // second pass over the (resized) NV12
+    default: return TSVPP_UNSUPPORTED;
+    }
+    if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
+    // element type: src/VideoProcessor.cpp:139-142; HSV always runs the float kernels (src/ColorConversion.cu:357-370)
+    const bool f32 = p->normalization != 0 || p->fourcc == TSVPP_HSV;
+    pl.f32 = f32;
+    if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) {
+        if (p->fourcc == TSVPP_NV12) pl.out = f32 ? O_NV12_F32 : O_NV12_U8;
+        else if (p->fourcc == TSVPP_HSV) pl.out = O_HSV_F32;
+        else pl.out = O_NV12_U8; // UYVY / YUV444: pass 1
+    }
+    // channelsByFourCC: 1.5 for NV12 (src/VideoProcessor.cpp:4-14)
+    const size_t elems = p->fourcc == TSVPP_NV12 ? (size_t)pl.dst_w * pl.dst_h * 3 / 2
+                                                 : (size_t)(tsvpp_channels(p->fourcc) * (float)pl.dst_w) * (size_t)pl.dst_h;
+    pl.out_bytes = elems * (f32 ? sizeof(float) : 1);
+    if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside a frame
+    return TSVPP_OK;
+}
+
+int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl) {
+    // TSVPP_ERROR: arguments that describe no request at all
+    if (!p || !frames || !rois || n_frames <= 0 || n_rois <= 0) return TSVPP_ERROR;
+    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the boxes are the crops
+    if (p->dst_width <= 0 || p->dst_height <= 0) return TSVPP_ERROR;
+    for (int f = 0; f < n_frames; f++) {
+        const tsvpp_nv12 &fr = frames[f];
+        if (fr.width <= 0 || fr.height <= 0) return TSVPP_ERROR;
+        if (pitch_or_width(fr.pitch_y, fr.width) < fr.width || pitch_or_width(fr.pitch_uv, fr.width) < fr.width) return TSVPP_ERROR;
+    }
+    for (int i = 0; i < n_rois; i++) {
+        const tsvpp_roi &b = rois[i];
+        if (b.frame < 0 || b.frame >= n_frames) return TSVPP_ERROR;
+        const tsvpp_nv12 &fr = frames[b.frame];
+        if (b.left < 0 || b.top < 0 || b.right <= b.left || b.bottom <= b.top || b.right > fr.width || b.bottom > fr.height) return TSVPP_ERROR;
+    }
+    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
+    if ((p->dst_width | p->dst_height) & 1) return TSVPP_UNSUPPORTED;
+    for (int f = 0; f < n_frames; f++)
+        if ((frames[f].width | frames[f].height) & 1) return TSVPP_UNSUPPORTED;
+    for (int i = 0; i < n_rois; i++)
+        if (((rois[i].right - rois[i].left) | (rois[i].bottom - rois[i].top)) & 1) return TSVPP_UNSUPPORTED;
+    if (!resize_mode(p->resize_type, pl.mode) || pl.mode == M_AREA_DOWN) return TSVPP_UNSUPPORTED; // AREA: a weight table per distinct ratio (not yet)
+    if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
+    const bool f32 = p->normalization != 0;
+    if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV: not yet
+    const int channels = p->fourcc == TSVPP_Y800 ? 1 : 3;
+    pl.dst_w = p->dst_width;
+    pl.dst_h = p->dst_height;
+    pl.out_bytes = (size_t)channels * (size_t)pl.dst_w * (size_t)pl.dst_h * (f32 ? sizeof(float) : 1);
+    if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
+    if ((long)((pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * TSVPP_MAX_ROIS >= (1L << 31)) return TSVPP_UNSUPPORTED;
+    return TSVPP_OK;
+}
+
+} // namespace tsvpp
+
+extern "C" {
+
+float tsvpp_channels(int fourcc) {
+    if (fourcc == TSVPP_Y800) return 1.0f;
+    if (fourcc == TSVPP_UYVY) return 2.0f;
+    if (fourcc == TSVPP_NV12) return 1.5f;
+    return 3.0f;
+}
+
+int tsvpp_out_dims(const tsvpp_params *p, int in_width, int in_height, int *out_width, int *out_height) {
+    Plan pl;
+    int sts = make_plan(p, in_width, in_height, pl);
+    if (sts != TSVPP_OK) return sts;
+    if (out_width) *out_width = pl.dst_w;
+    if (out_height) *out_height = pl.dst_h;
+    return TSVPP_OK;
+}
+
+size_t tsvpp_out_bytes(const tsvpp_params *p, int in_width, int in_height) {
+    Plan pl;
+    if (make_plan(p, in_width, in_height, pl) != TSVPP_OK) return 0;
+    return pl.out_bytes;
+}
+
+} // extern "C"

@@ -183,6 +183,111 @@ def representative(sig):
     return min(reqs, key=lambda r: (oracle_bytes(r), r[7], repr(r)))
 
 
+# ---- launches of more than TSVPP_MAX_BATCH frames out of a frame table (tests/test_gpu_dispatch_cover.py: test_table_launches_past_128_frames...) -------------
+MAX_BATCH = 128          # include/tsvpp.h: TSVPP_MAX_BATCH (tests/test_dispatch_cover_cpu.py compares both with the header)
+MAX_TABLE_LAUNCH = 1024  # include/tsvpp.h: TSVPP_MAX_TABLE_LAUNCH
+TABLE_POOL = 7           # distinct source frames behind a big table: coprime to the 8 XCDs and to 128, so a wrapped or permuted frame index reads another frame
+TABLE_PER_FAMILY = 4
+TABLE_N_WANTED = MAX_TABLE_LAUNCH + 1  # two launch groups: 1024 + 1
+TABLE_N_MIN = MAX_BATCH + 3            # the least that is still a launch the batch path cannot make
+
+
+def out_kind(sig):
+    return re.search(r"\bout=(\S+)", sig).group(1)
+
+
+def pool_bytes(req):
+    """device bytes of TABLE_POOL source frames, each plane in its own 256-byte aligned slot (test_gpu_dispatch_cover._fill_inputs)"""
+    w, h, py, puv = req[0]
+    return TABLE_POOL * ((h * py + 255) // 256 * 256 + ((h // 2) * puv + 255) // 256 * 256)
+
+
+def table_launch_cap(dst_w, dst_h):
+    """frames per launch out of a table for a single-pass request (tsvpp_api.cpp: convert_impl): TSVPP_MAX_TABLE_LAUNCH, less where the grid of the smallest
+    tile (64 x 4 output pixels per workgroup of 256) would outgrow 2^31 threads, and never less than TSVPP_MAX_BATCH"""
+    wg = ((dst_w + 63) // 64) * ((dst_h + 3) // 4)
+    cap = min(((1 << 31) // 256) // max(wg, 1), MAX_TABLE_LAUNCH)
+    return cap if cap > MAX_BATCH else MAX_BATCH
+
+
+def table_candidates():
+    """{family: [(signature, n_big, launch_cap)]}: up to TABLE_PER_FAMILY signatures per family of FAMILIES (all but "(none)") whose representative is converted out
+    of a table of n_big entries.  Deterministic host logic.  A signature qualifies if
+      * it is a single pass (no pass2=: the two-pass formats go through the table's host mirror in kernarg launches of <= 128 frames, which the table leg of
+        every signature already runs -- they cannot make the launch this is about);
+      * n_big outputs + TABLE_POOL source frames fit MAX_DEVICE_BYTES, n_big = TABLE_N_WANTED if that fits, else the largest count that does, >= TABLE_N_MIN;
+      * one launch takes TABLE_N_MIN frames (table_launch_cap), and describe still answers with the family at the 128 frames it clamps to (the selection
+        reads the frame count; the launch itself is checked on the GPU).
+    Distinct out= kinds first, the fewest output bytes first among them; a family with fewer kinds than TABLE_PER_FAMILY fills up with its next smallest signatures."""
+    if "table" in _CACHE:
+        return _CACHE["table"]
+    desc = _Describer()
+    by_family = {}
+    for sig in sorted(signatures()):
+        fam = family(sig)
+        if fam == "(none)" or " pass2=" in f" {sig}":
+            continue
+        req = representative(sig)
+        ob = out_bytes(req)
+        room = MAX_DEVICE_BYTES - pool_bytes(req)
+        n_big = min(TABLE_N_WANTED, room // ob if room > 0 else 0)
+        if n_big < TABLE_N_MIN:
+            continue
+        a = desc(req[:7] + (MAX_BATCH, req[8]))
+        if a is None or family(signature_of(a, req[8])) != fam:
+            continue
+        dw, dh = (int(v) for v in a["dst"].split("x"))
+        cap = table_launch_cap(dw, dh)
+        if cap < TABLE_N_MIN:
+            continue
+        by_family.setdefault(fam, []).append((ob, sig, n_big, cap))
+    out = {}
+    for fam in FAMILIES:
+        if fam == "(none)":
+            continue
+        ranked = sorted(by_family.get(fam, []))  # fewest output bytes, then the signature's own order
+        first_of_kind, rest, kinds = [], [], set()
+        for c in ranked:
+            if out_kind(c[1]) in kinds:
+                rest.append(c)
+            else:
+                kinds.add(out_kind(c[1]))
+                first_of_kind.append(c)
+        out[fam] = [(sig, n_big, cap) for ob, sig, n_big, cap in (first_of_kind + rest)[:TABLE_PER_FAMILY]]
+    _CACHE["table"] = out
+    return out
+
+
+def table_unaligned_case():
+    """(signature, request, kernel describe names for the same request with outputs that are NOT 16-byte aligned): the fp32 planar signature of a vector-store
+    kernel -- one whose kernel differs between the two alignment classes -- with the fewest output bytes, for a full launch group of MAX_TABLE_LAUNCH frames
+    followed by a second group of MAX_BATCH.  Under A/B knobs that leave no such signature (TSVPP_FORCE_GATHER=1: every request takes the element-wise
+    kernel, whatever the alignment) the smallest fp32 planar signature whose two kernels are the same: the GPU test then still runs and still asserts the
+    aligned=0 kernel and the bits.  None only if no single-pass fp32 planar signature fits at all."""
+    desc = _Describer()
+    differs, same = None, None
+    for sig in sorted(signatures()):
+        if out_kind(sig) != "f32_planar" or not sig.endswith(" aligned=1") or " pass2=" in f" {sig}":
+            continue
+        req = representative(sig)
+        ob = out_bytes(req)
+        if (MAX_TABLE_LAUNCH + MAX_BATCH) * (ob + 4) + pool_bytes(req) > MAX_DEVICE_BYTES:
+            continue
+        a1, a0 = desc(req[:7] + (MAX_BATCH, 1)), desc(req[:7] + (MAX_BATCH, 0))
+        if a1 is None or a0 is None or a1["kernel"] != kernel_name(sig):
+            continue
+        dw, dh = (int(v) for v in a1["dst"].split("x"))
+        if table_launch_cap(dw, dh) < MAX_TABLE_LAUNCH:
+            continue
+        if a1["kernel"] != a0["kernel"]:
+            if differs is None or ob < differs[0]:
+                differs = (ob, sig, req, a0["kernel"])
+        elif same is None or ob < same[0]:
+            same = (ob, sig, req, a0["kernel"])
+    best = differs or same
+    return None if best is None else best[1:]
+
+
 def kernel_literals():
     """every kernel name the launchers report, as describe spells it (no blanks): the "vpp_..._kernel<...>" literals of csrc/*.hip"""
     names = set()

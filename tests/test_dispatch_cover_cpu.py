@@ -80,3 +80,59 @@ def test_signature_drops_only_size_keys():
 def test_enumeration_is_fast_enough(sigs):
     """the grid is enumerated once per process by both tests' fixtures (the module caches it): it must stay cheap -- ~9 s when this bound was set"""
     assert G._CACHE["seconds"] < 20, G._CACHE["seconds"]
+
+
+def test_table_constants_are_the_headers():
+    import os
+    import re
+    text = open(os.path.join(G.ROOT, "include", "tsvpp.h")).read()
+    assert int(re.search(r"#define\s+TSVPP_MAX_BATCH\s+(\d+)", text).group(1)) == G.MAX_BATCH
+    assert int(re.search(r"#define\s+TSVPP_MAX_TABLE_LAUNCH\s+(\d+)", text).group(1)) == G.MAX_TABLE_LAUNCH
+    assert G.TABLE_N_WANTED == G.MAX_TABLE_LAUNCH + 1 and G.TABLE_N_MIN == G.MAX_BATCH + 3
+    # the pool's period shares no factor with the XCD count or the kernarg table's length: a wrapped or permuted frame index reads another frame
+    assert G.TABLE_POOL % 2 == 1 and G.MAX_BATCH % G.TABLE_POOL != 0 and 8 % G.TABLE_POOL != 0
+
+
+def test_every_family_has_table_candidates_and_the_choice_is_deterministic(sigs):
+    """the signatures tests/test_gpu_dispatch_cover.py converts out of tables of more than TSVPP_MAX_BATCH entries: every family but "(none)" has some"""
+    cands = G.table_candidates()
+    assert set(cands) == set(G.FAMILIES) - {"(none)"}
+    G._CACHE.pop("table")
+    again = G.table_candidates()
+    assert again == cands and [list(v) for v in again.values()] == [list(v) for v in cands.values()]
+    reached = {G.family(s) for s in sigs}
+    empty = [f for f in cands if not cands[f] and not (knob_run() and f not in reached)]  # (under A/B knobs a family the grid no longer reaches has none)
+    assert not empty, f"families without a signature that fits a table launch of {G.TABLE_N_MIN}+ frames into {G.MAX_DEVICE_BYTES} bytes: {empty}"
+    for fam, lst in cands.items():
+        assert len(lst) <= G.TABLE_PER_FAMILY and len({s for s, _, _ in lst}) == len(lst)
+        kinds = [G.out_kind(s) for s, _, _ in lst]
+        fresh = [k not in kinds[:i] for i, k in enumerate(kinds)]
+        assert fresh == sorted(fresh, reverse=True), (fam, kinds)  # distinct out= kinds first, repeats only behind them
+        sizes = [G.out_bytes(G.representative(s)) for (s, _, _), f in zip(lst, fresh) if f]
+        assert sizes == sorted(sizes), (fam, kinds, sizes)         # ... the fewest output bytes first
+        for sig, n_big, cap in lst:
+            req = G.representative(sig)
+            assert sig in sigs and G.family(sig) == fam and " pass2=" not in sig
+            assert G.TABLE_N_MIN <= n_big <= G.TABLE_N_WANTED and cap >= G.TABLE_N_MIN, (sig, n_big, cap)
+            assert n_big * G.out_bytes(req) + G.pool_bytes(req) <= G.MAX_DEVICE_BYTES, (sig, n_big)
+            # n_big is the largest count that fits, up to the wanted one
+            assert n_big == G.TABLE_N_WANTED or (n_big + 1) * G.out_bytes(req) + G.pool_bytes(req) > G.MAX_DEVICE_BYTES, (sig, n_big)
+
+
+def test_table_launch_cap_is_convert_impls():
+    assert G.table_launch_cap(1280, 720) == 1024 and G.table_launch_cap(1920, 1080) == 1024   # 3 600 / 8 100 workgroups a frame
+    assert G.table_launch_cap(2560, 1440) == (1 << 23) // (40 * 360) == 582
+    assert G.table_launch_cap(3840, 2160) == 258 and G.table_launch_cap(5760, 3240) == 128   # (115 would be less than a kernarg launch takes)
+
+
+def test_the_misaligned_table_case_exists(sigs):
+    """with the default knobs and under every A/B knob: the GPU test never stands down for want of a case"""
+    case = G.table_unaligned_case()
+    assert case is not None, "no single-pass fp32 planar signature fits a table launch of 1024 + 128 frames"
+    sig, req, unaligned_kernel = case
+    assert sig in sigs and req == G.representative(sig) and " pass2=" not in sig
+    assert G.out_kind(sig) == "f32_planar" and sig.endswith(" aligned=1") and unaligned_kernel.startswith("vpp_")
+    assert (G.MAX_TABLE_LAUNCH + G.MAX_BATCH) * (G.out_bytes(req) + 4) + G.pool_bytes(req) <= G.MAX_DEVICE_BYTES
+    if not knob_run():  # (a knob may leave one kernel for both alignment classes, TSVPP_FORCE_GATHER=1: the defaults do not)
+        assert unaligned_kernel != G.kernel_name(sig), f"no fp32 planar signature whose kernel depends on the output alignment: {sig}"
+    assert G.table_unaligned_case() == case

@@ -172,8 +172,8 @@ int tsvpp_convert_table(tsvpp_ctx *ctx, const tsvpp_table *table, int first, int
  * chroma rows [top / 2, top / 2 + height / 2) x BYTE columns [left, right): the crop rule of Convert, an odd `left` swaps U and V as it does there), resized
  * with xr = (float)width / dst_width, yr = (float)height / dst_height; for a box Convert's crop stage accepts it equals tsvpp_convert(crop = box).  A box of
  * exactly dst_width x dst_height is a plain colour conversion (every interpolation weight is zero).
- * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  NOT YET supported (TSVPP_UNSUPPORTED): AREA (its down-scale
- * needs a weight table per distinct ratio), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes, rotated boxes,
+ * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  TSVPP_UNSUPPORTED here: AREA (it has an entry point
+ * of its own, tsvpp_convert_rois_area below), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes, rotated boxes,
  * fp16 outputs.
  * `frames`, `rois`, `outs` are HOST arrays and may be freed on return: the per-box records (plane origins, pitches, size, ratios, output pointer: 48 bytes)
  * travel BY VALUE in the kernarg segment of their launch -- no staging buffer, no copy, no allocation, no host synchronisation -- which is what bounds a
@@ -198,6 +198,41 @@ int tsvpp_convert_rois(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, i
  * tsvpp_describe (2: shifted last tile column; 0). */
 int tsvpp_describe_rois(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
                         size_t buf_len);
+
+/* ---- regions of interest, AREA ---------------------------------------------------------------------------------------------------------------------------
+ * tsvpp_convert_rois with p->resize_type == TSVPP_AREA -- the filter a cascade wants when it shrinks a 300-500 pixel box to 112 x 112 or 224 x 224: the only one
+ * of the four that averages every source pixel.  Arguments, box rules, output layout, launch splitting (TSVPP_MAX_ROIS_AREA boxes per launch), the order of the
+ * statuses and "decided before any device is touched" are tsvpp_convert_rois's, word for word; so is the contract: the result of a box is, bit for bit, what
+ * tsvpp_convert returns for a frame that consists of the box alone, resized with TSVPP_AREA, and for a box Convert's crop stage accepts it equals
+ * tsvpp_convert(crop = box, AREA).  The differences:
+ *   resize type   p->resize_type must be TSVPP_AREA; anything else is TSVPP_UNSUPPORTED (and tsvpp_convert_rois keeps answering TSVPP_UNSUPPORTED for AREA).
+ *   per box       as Convert decides per request (reference src/Resize.cu:435): a box with xr > 1 AND yr > 1 runs the AREA down-scale (the weighted box); any
+ *                 other box -- up-scaled on either axis, or exactly the output size -- runs the AREA up-scale rule (the 2 x 2 blend).  One launch may mix both.
+ *   no tables     tsvpp_convert builds a device weight table per distinct scale (one allocation and one synchronous copy per axis the first time a scale is seen,
+ *                 kept until tsvpp_destroy); boxes behind a detector have a new scale each.  Here the kernel generates the weight rows a tile reads inside the
+ *                 tile (csrc/vpp_rois_area.hip): no allocation, no copy, no host synchronisation, nothing cached in the context, records by value in the kernarg
+ *                 segment -- legal while `stream` is being captured, like tsvpp_convert_rois.
+ *   limits        TSVPP_UNSUPPORTED for a down-scale box that needs more than 40 taps on an axis (taps = ceil(ratio): 1920 columns to 112 need 18, 1080 rows
+ *                 to 30 need 36), and for dst_width or dst_height above 65536.
+ *   cost          a tile of a down-scale box first waits for one lane to generate the weight rows of every output column / row in front of it (~75 ns each,
+ *                 once per tile: ~17 us for the last tile column of a 224-wide output), so a launch with a down-scale box takes 25-50 us where the BILINEAR
+ *                 launch takes 5-16 (profiles/rois_area_ab.txt).  Linear in the output size: meant for NN-input sizes, not for outputs thousands of pixels wide.
+ *   deviation     tsvpp_convert refuses (TSVPP_UNSUPPORTED) a ratio whose weight pattern does not close within 65536 rows.  This call never needs more than
+ *                 dst_width / dst_height rows and answers such a box with the generator's rows (the rows tsvpp_convert's table would begin with).
+ * Why a second entry point instead of one more resize type of tsvpp_convert_rois: that call's answer to AREA (TSVPP_UNSUPPORTED, from tsvpp_describe_rois,
+ * tsvpp_convert_rois and the Python / C++ facades alike) is pinned by its tests; folding the two entry points into one is a later change that edits those tests.
+ * tsvpp_describe_rois_area prints tsvpp_describe_rois's keys (mode=area, kernel=vpp_rois_area<...>, limit=64; lds= includes the weight rows) and then
+ * "down=<boxes on the down-scale path> taps=<largest taps_x>x<largest taps_y>" (0x0 without a down-scale box). */
+#define TSVPP_MAX_ROIS_AREA 64 /* boxes per launch; more are split (the per-box record is tsvpp_convert_rois's: nothing had to grow) */
+int tsvpp_convert_rois_area(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
+                            void *stream);
+int tsvpp_describe_rois_area(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
+                             size_t buf_len);
+/* DEBUG ONLY (tests), host only: the weight rows tsvpp_convert_rois_area's kernel generates for output indices first .. first + n - 1 of an axis with ratio
+ * `scale` (> 1) -- the same generator, evaluated on the host -- as n rows of *taps = ceil(scale) floats in `out` (max_floats entries).  Row j equals row
+ * j % rows of tsvpp_area_pattern(scale).  Returns n; TSVPP_UNSUPPORTED for scale <= 1, more than 40 taps or first + n > 65536; TSVPP_ERROR for null / negative
+ * arguments or a buffer that is too small. */
+int tsvpp_roi_area_rows(float scale, int first, int n, float *out, int max_floats, int *taps);
 
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them
@@ -271,6 +306,9 @@ void tsvpp_default_coeffs(tsvpp_coeffs *out);
  * src/Resize.cu:359-386) as this library builds it: writes rows*taps floats
  * (taps = ceil(scale)) to `out` if it fits `max_floats`; returns rows or <0. */
 int tsvpp_area_pattern(float scale, float *out, int max_floats, int *taps);
+/* DEBUG ONLY (tests): the number of AREA tables the context has cached so far -- one per distinct scale tsvpp_convert* has seen, plus the divisor tables per
+ * pair of scales; they stay until tsvpp_destroy.  tsvpp_convert_rois_area never adds one.  TSVPP_ERROR for a null context. */
+int tsvpp_debug_area_tables(tsvpp_ctx *ctx);
 
 /* What tsvpp_convert_batch WOULD launch for this request -- stage selection (reference
  * src/VideoProcessor.cpp:106-151) plus this library's kernel / workgroup-shape / LDS choice -- as one line of

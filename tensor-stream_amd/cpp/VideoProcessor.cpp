@@ -175,8 +175,9 @@ int VideoProcessor::ConvertInto(AVFrame *input, void *deviceOut, FrameParameters
     return VREADER_OK;
 }
 
-int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
-                                std::string consumerName) {
+// ConvertRois and ConvertRoisArea differ in the entry point of the C ABI they end in
+static int convertRois(bool area, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts,
+                       FrameParameters &options, const std::string &consumerName) {
     if (isClosed || !inputs || nInputs <= 0 || !rois || nRois <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
     void *stream = nullptr;
     CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
@@ -187,8 +188,18 @@ int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp
         frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
     }
     const tsvpp_params p = flatten(options); // options.crop must be empty: the boxes are the crops
-    CHECK_STATUS(tsvpp_convert_rois(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
+    CHECK_STATUS((area ? tsvpp_convert_rois_area : tsvpp_convert_rois)(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
     return VREADER_OK;
+}
+
+int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                std::string consumerName) {
+    return convertRois(false, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+}
+
+int VideoProcessor::ConvertRoisArea(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                    std::string consumerName) {
+    return convertRois(true, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
 }
 
 int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &options, std::string consumerName) {

@@ -120,6 +120,9 @@ public:
     // channels * width * height elements), one kernel launch per TSVPP_MAX_ROIS boxes on the consumer's stream.  options.crop must be empty; the inputs are NOT
     // consumed (no av_frame_unref: a frame usually serves several calls).  Same status convention as ConvertInto.
     int ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    // The same for options.resize.type == AREA (tsvpp_convert_rois_area: every box with both ratios above 1 is averaged, any other takes AREA's up-scale rule; no
+    // weight table is built or cached).  ConvertRois refuses AREA and this refuses everything else: two entry points until the C ABI folds them.
+    int ConvertRoisArea(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

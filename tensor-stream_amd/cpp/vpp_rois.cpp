@@ -1,12 +1,14 @@
 // vpp_rois -- converts a handful of boxes of one NV12 frame through the C++ class (VideoProcessor::ConvertRois) and prints a CRC-32 per box
 // (libavutil's AV_CRC_32_IEEE, as vpp_goldens computes it); tests/test_cpp_rois_gpu.py compares each with the oracle's.
-//   vpp_rois frame.nv12 W H PITCH  DW DH TYPE  FOURCC PLANES NORM  L T R B [L T R B ...]
+//   vpp_rois [--area] frame.nv12 W H PITCH  DW DH TYPE  FOURCC PLANES NORM  L T R B [L T R B ...]
+// --area: through VideoProcessor::ConvertRoisArea (TYPE must then be 3, AREA; tests/test_cpp_rois_area_gpu.py).
 // The file holds H rows of PITCH bytes of luma, then H / 2 rows of PITCH bytes of chroma.  Prints "<index> <crc> <bytes>" per box; exit code 0 = converted.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "VideoProcessor.h"
@@ -21,7 +23,12 @@ static uint32_t crc32_av(const uint8_t *buf, size_t n) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 15 || (argc - 11) % 4 != 0) { fprintf(stderr, "usage: vpp_rois frame.nv12 W H PITCH DW DH TYPE FOURCC PLANES NORM L T R B [L T R B ...]\n"); return 200; }
+    const bool area = argc > 1 && strcmp(argv[1], "--area") == 0;
+    if (area) {
+        argv++;
+        argc--;
+    }
+    if (argc < 15 || (argc - 11) % 4 != 0) { fprintf(stderr, "usage: vpp_rois [--area] frame.nv12 W H PITCH DW DH TYPE FOURCC PLANES NORM L T R B [L T R B ...]\n"); return 200; }
     const int W = atoi(argv[2]), H = atoi(argv[3]), P = atoi(argv[4]);
     const int DW = atoi(argv[5]), DH = atoi(argv[6]), type = atoi(argv[7]);
     const int fcc = atoi(argv[8]), planes = atoi(argv[9]), norm = atoi(argv[10]);
@@ -57,7 +64,8 @@ int main(int argc, char **argv) {
     std::vector<void *> outs(rois.size());
     for (size_t i = 0; i < rois.size(); i++) outs[i] = dOut + i * stride;
     AVFrame *inputs[1] = { input };
-    const int sts = vpp.ConvertRois(inputs, 1, rois.data(), (int)rois.size(), outs.data(), options, "rois");
+    const int sts = area ? vpp.ConvertRoisArea(inputs, 1, rois.data(), (int)rois.size(), outs.data(), options, "rois")
+                         : vpp.ConvertRois(inputs, 1, rois.data(), (int)rois.size(), outs.data(), options, "rois");
     if (sts != 0) return 210;
     if (tsvpp_consumer_synchronize(vpp.context(), "rois") != 0) return 211; // the conversion is asynchronous, on the consumer's stream
     std::vector<uint8_t> result(bytes);
@@ -68,7 +76,7 @@ int main(int argc, char **argv) {
     // a box outside its frame is refused with the reference's status convention, and nothing is launched
     tsvpp_roi bad{ 0, 0, 0, W + 2, 2 };
     void *one[1] = { dOut };
-    if (vpp.ConvertRois(inputs, 1, &bad, 1, one, options, "rois") != VREADER_ERROR) return 213;
+    if ((area ? vpp.ConvertRoisArea(inputs, 1, &bad, 1, one, options, "rois") : vpp.ConvertRois(inputs, 1, &bad, 1, one, options, "rois")) != VREADER_ERROR) return 213;
     av_frame_free(&input);
     vpp.Close();
     (void)hipFree(dOut);

@@ -272,3 +272,10 @@ extern "C" int tsvpp_area_pattern(float scale, float *out, int max_floats, int *
     if (out && (long)tab.size() <= (long)max_floats) std::memcpy(out, tab.data(), tab.size() * sizeof(float));
     return rows;
 }
+
+// DEBUG ONLY (tests): how many AREA tables the context has cached (weight tables per scale + divisor tables per pair of scales)
+extern "C" int tsvpp_debug_area_tables(tsvpp_ctx *ctx) {
+    if (!ctx) return TSVPP_ERROR;
+    std::lock_guard<std::mutex> lk(ctx->area_mu);
+    return (int)(ctx->area.size() + ctx->area_div.size());
+}

@@ -3,7 +3,7 @@
 //   tsvpp_area.cpp   AREA weight tables, their device cache, the AREA fields of a launch descriptor
 //   tsvpp_api.cpp    contexts, streams, knobs, the conversion itself and its replay cache, tsvpp_describe
 //   tsvpp_table.cpp  persistent frame tables
-//   tsvpp_rois.cpp   regions of interest
+//   tsvpp_rois.cpp   regions of interest (both entry points: NEAREST / BILINEAR / BICUBIC and AREA)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,12 +55,13 @@ struct Plan {
     bool f32 = false;
 };
 
-// The request of tsvpp_convert_rois / tsvpp_describe_rois, checked and resolved on the host alone.
+// The request of tsvpp_convert_rois / tsvpp_describe_rois and of their AREA counterparts, checked and resolved on the host alone.
 struct RoiPlan {
-    Mode mode = M_NONE;
+    Mode mode = M_NONE; // M_AREA_DOWN: the AREA entry point -- every box chooses between the down-scale and the up-scale rule (roi_area_mode, vpp_rois.h)
     OutKind out = O_U8_MERGED;
     int dst_w = 0, dst_h = 0, swap_rb = 0;
     size_t out_bytes = 0;
+    int down = 0, taps_x = 0, taps_y = 0; // AREA: boxes on the down-scale path, their largest tap counts
 };
 
 // Everything of a context that the launch descriptor is filled from (fill_desc): the tuning knobs (read_env_knobs) and the two options the API sets that
@@ -234,7 +235,7 @@ inline constexpr const char *out_names[O_COUNT_ALL] = { "u8_planar", "u8_merged"
 // ---- functions that cross files ----------------------------------------------------------------------------------------------------------------------
 // tsvpp_plan.cpp
 int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl);
-int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl);
+int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl, bool area = false);
 // tsvpp_area.cpp: the AREA down-scale fields of a descriptor (nothing for any other mode), out of the context's tables or -- a dry run -- with stand-in pointers
 int area_desc(tsvpp_ctx *ctx, const Plan &pl, hipStream_t stream, LaunchDesc &d);
 int area_desc(const Knobs &kn, const Plan &pl, LaunchDesc &d);

@@ -91,7 +91,7 @@ bool weights_dyadic(Mode m, int dst_w, int dst_h, float xr, float yr, int src_w,
     return remember(true);
 }
 
-// resize_type -> Mode.  AREA answers M_AREA_DOWN: make_plan splits it by the ratios, rois_plan refuses it.  False: unknown (the reference launches nothing and
+// resize_type -> Mode.  AREA answers M_AREA_DOWN: make_plan splits it by the ratios, rois_plan per box (and only for the AREA entry point).  False: unknown (the reference launches nothing and
 // returns garbage).
 bool resize_mode(int resize_type, Mode &m) {
     switch (resize_type) {
@@ -188,7 +188,7 @@ int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl) {
     return TSVPP_OK;
 }
 
-int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl) {
+int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl, bool area) {
     // TSVPP_ERROR: arguments that describe no request at all
     if (!p || !frames || !rois || n_frames <= 0 || n_rois <= 0) return TSVPP_ERROR;
     if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the boxes are the crops
@@ -210,7 +210,8 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
         if ((frames[f].width | frames[f].height) & 1) return TSVPP_UNSUPPORTED;
     for (int i = 0; i < n_rois; i++)
         if (((rois[i].right - rois[i].left) | (rois[i].bottom - rois[i].top)) & 1) return TSVPP_UNSUPPORTED;
-    if (!resize_mode(p->resize_type, pl.mode) || pl.mode == M_AREA_DOWN) return TSVPP_UNSUPPORTED; // AREA: a weight table per distinct ratio (not yet)
+    // AREA has an entry point of its own (tsvpp_convert_rois_area: its down-scale generates weight rows per tile), which answers nothing else
+    if (!resize_mode(p->resize_type, pl.mode) || (pl.mode == M_AREA_DOWN) != area) return TSVPP_UNSUPPORTED;
     if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
     const bool f32 = p->normalization != 0;
     if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV: not yet
@@ -220,6 +221,19 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
     pl.out_bytes = (size_t)channels * (size_t)pl.dst_w * (size_t)pl.dst_h * (f32 ? sizeof(float) : 1);
     if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
     if ((long)((pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * TSVPP_MAX_ROIS >= (1L << 31)) return TSVPP_UNSUPPORTED;
+    pl.down = pl.taps_x = pl.taps_y = 0;
+    if (area) {
+        if (pl.dst_w > ROI_AREA_MAX_DST || pl.dst_h > ROI_AREA_MAX_DST) return TSVPP_UNSUPPORTED;
+        for (int i = 0; i < n_rois; i++) {
+            const float xr = (float)(rois[i].right - rois[i].left) / (float)pl.dst_w, yr = (float)(rois[i].bottom - rois[i].top) / (float)pl.dst_h;
+            if (roi_area_mode(xr, yr) != M_AREA_DOWN) continue;
+            const int tx = roi_area_taps(xr), ty = roi_area_taps(yr);
+            if (tx > ROI_AREA_MAX_TAPS || ty > ROI_AREA_MAX_TAPS) return TSVPP_UNSUPPORTED;
+            pl.down++;
+            pl.taps_x = tx > pl.taps_x ? tx : pl.taps_x;
+            pl.taps_y = ty > pl.taps_y ? ty : pl.taps_y;
+        }
+    }
     return TSVPP_OK;
 }
 

@@ -1,4 +1,6 @@
-// tsvpp_rois.cpp -- regions of interest (include/tsvpp.h; kernel: vpp_rois.hip): many boxes of a few frames to one size, TSVPP_MAX_ROIS per launch.
+// tsvpp_rois.cpp -- regions of interest (include/tsvpp.h): many boxes of a few frames to one size, TSVPP_MAX_ROIS per launch.  Two pairs of entry points over one
+// body: tsvpp_convert_rois / tsvpp_describe_rois (NEAREST, BILINEAR, BICUBIC; kernel vpp_rois.hip) and tsvpp_convert_rois_area / tsvpp_describe_rois_area (AREA;
+// kernel vpp_rois_area.hip).  What differs is which resize types rois_plan lets through (`area`), the mode of a box (AREA: per box) and the launcher.
 #include <algorithm>
 #include <cstdio>
 
@@ -9,9 +11,12 @@ using namespace tsvpp;
 
 // 4 k + 2 columns, narrower than a tile: no tile column to shift, so no vector stores
 static bool narrow_tail(const RoiPlan &pl) { return (pl.dst_w & 3) != 0 && pl.dst_w < ROI_TILE_W; }
+static bool is_area(const RoiPlan &pl) { return pl.mode == M_AREA_DOWN; }
+static int launch_limit(const RoiPlan &pl) { return is_area(pl) ? (int)TSVPP_MAX_ROIS_AREA : (int)TSVPP_MAX_ROIS; }
 
-// One launch group: boxes [base, base + cnt) as a RoiLaunch.  `frames` may carry null planes (tsvpp_describe_rois): then the records hold the bare crop offsets.
-// Returns how many of the group's boxes stage EVERY tile in LDS; L.lds_bytes = the dynamic LDS the launch needs for them (0: the gather kernel).
+// One launch group: boxes [base, base + cnt) as a RoiLaunch.  `frames` may carry null planes (the describe calls): then the records hold the bare crop offsets.
+// Returns how many of the group's boxes stage EVERY tile in LDS; L.lds_bytes = the dynamic LDS the launch needs for them (0: the gather kernel), L.area_lds = the
+// bytes of the AREA kernel's weight rows in front of it (the largest tap counts among the group's down-scale boxes; they count against the LDS budget).
 static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frames, const tsvpp_roi *rois, void *const *outs, int base, int cnt, bool vec, RoiLaunch &L) {
     L.dst_w = pl.dst_w;
     L.dst_h = pl.dst_h;
@@ -26,10 +31,7 @@ static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frame
     // outputs 4 k + 2 columns wide: the last tile column is shifted to the right edge so that every thread tile has its four columns (tile_col0, vpp_device.h)
     L.last_col0 = (vec && (pl.dst_w & 3) != 0 && pl.dst_w >= ROI_TILE_W) ? pl.dst_w - ROI_TILE_W : 0;
     L.u8_xchg = kn.u8_xchg;
-    L.pad = 0;
-    const bool luma_only = pl.out == O_Y800_U8 || pl.out == O_Y800_F32;
-    const int budget = kn.force_gather ? 0 : kn.lds_budget_kb * 1024 - roi_static_lds(pl.out, vec);
-    int staged = 0, lds = 0;
+    L.area_lds = 0;
     for (int i = 0; i < cnt; i++) {
         const tsvpp_roi &b = rois[base + i];
         const tsvpp_nv12 &fr = frames[b.frame];
@@ -44,16 +46,25 @@ static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frame
         r.src_h = b.bottom - b.top;
         r.xr = (float)r.src_w / (float)pl.dst_w; // src/Resize.cu:418-419
         r.yr = (float)r.src_h / (float)pl.dst_h;
+        if (is_area(pl) && roi_area_mode(r.xr, r.yr) == M_AREA_DOWN) L.area_lds = std::max(L.area_lds, roi_area_lds(roi_area_taps(r.xr), roi_area_taps(r.yr)));
+    }
+    for (int i = cnt; i < TSVPP_MAX_ROIS; i++) L.r[i] = RoiRec{};
+    const bool luma_only = pl.out == O_Y800_U8 || pl.out == O_Y800_F32;
+    const int budget = kn.force_gather ? 0 : kn.lds_budget_kb * 1024 - roi_static_lds(pl.out, vec) - L.area_lds;
+    int staged = 0, lds = 0;
+    for (int i = 0; i < cnt; i++) {
+        const RoiRec &r = L.r[i];
+        const int mode = is_area(pl) ? roi_area_mode(r.xr, r.yr) : (int)pl.mode;
         // the box's largest tile footprint, from the numbers the kernel computes (columns and rows are independent: the maximum over tiles is the maximum of each)
         RoiFootprint f;
         int cy = 0, cuv = 0, ny = 0, nuv = 0;
         for (int tx = 0; tx < L.tiles_x; tx++) {
-            roi_span_x(pl.mode, roi_tile_col0(tx, pl.dst_w, L.last_col0), pl.dst_w, r.src_w, r.xr, f);
+            roi_span_x(mode, roi_tile_col0(tx, pl.dst_w, L.last_col0), pl.dst_w, r.src_w, r.xr, f);
             cy = std::max(cy, roi_chunks(f.xhi - f.xlo + 1));
             cuv = std::max(cuv, roi_chunks(2 * (f.cxhi - f.cxlo + 1)));
         }
         for (int ty = 0; ty < L.tiles_y; ty++) {
-            roi_span_y(pl.mode, ty * ROI_TILE_H, pl.dst_h, r.src_h, r.yr, f);
+            roi_span_y(mode, ty * ROI_TILE_H, pl.dst_h, r.src_h, r.yr, f);
             ny = std::max(ny, f.yhi - f.ylo + 1);
             nuv = std::max(nuv, luma_only ? 0 : f.cyhi - f.cylo + 1);
         }
@@ -64,18 +75,22 @@ static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frame
             lds = std::max(lds, (int)need);
         }
     }
-    for (int i = cnt; i < TSVPP_MAX_ROIS; i++) L.r[i] = RoiRec{};
     L.lds_bytes = lds;
     return staged;
 }
 
-extern "C" {
+// (vpp_rois.hip / vpp_rois_area.hip) one launch group, or only its kernel's name
+static hipError_t launch_group(const RoiPlan &pl, bool vec, bool staged, const RoiLaunch &L, hipStream_t stream, char *name, size_t name_len, bool dry_run) {
+    const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n_rois);
+    if (is_area(pl)) return launch_rois_area(pl.out, vec, staged, L, grid, (size_t)(L.area_lds + L.lds_bytes), stream, name, name_len, dry_run);
+    return launch_rois(pl.mode, pl.out, vec, staged, L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
+}
 
-int tsvpp_convert_rois(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
-                       void *stream) {
+static int convert_rois(bool area, tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
+                        void *stream) {
     clear_last_launch();
     RoiPlan pl;
-    int sts = rois_plan(p, n_frames, frames, n_rois, rois, pl); // the request first: the same status tsvpp_describe_rois answers, context or not
+    int sts = rois_plan(p, n_frames, frames, n_rois, rois, pl, area); // the request first: the same status the describe call answers, context or not
     if (sts != TSVPP_OK) return sts;
     if (!ctx || !outs) return TSVPP_ERROR;
     for (int f = 0; f < n_frames; f++)
@@ -87,27 +102,27 @@ int tsvpp_convert_rois(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, i
     char label[96] = "";
     const bool markers = ctx->markers != 0;
     if (markers)
-        std::snprintf(label, sizeof(label), "tsvpp_convert_rois n=%d frames=%d ->%dx%d mode=%d fourcc=%d stream=%p", n_rois, n_frames, pl.dst_w, pl.dst_h, (int)pl.mode,
-                      p->fourcc, stream);
+        std::snprintf(label, sizeof(label), "tsvpp_convert_rois%s n=%d frames=%d ->%dx%d mode=%d fourcc=%d stream=%p", area ? "_area" : "", n_rois, n_frames, pl.dst_w,
+                      pl.dst_h, (int)pl.mode, p->fourcc, stream);
     RangeGuard range(markers, label);
-    for (int base = 0; base < n_rois; base += TSVPP_MAX_ROIS) {
-        const int cnt = std::min(n_rois - base, (int)TSVPP_MAX_ROIS);
+    const int limit = launch_limit(pl);
+    for (int base = 0; base < n_rois; base += limit) {
+        const int cnt = std::min(n_rois - base, limit);
         const bool vec = outs_aligned16(outs + base, cnt) && !narrow_tail(pl); // per launch group, as tsvpp_convert_batch
         RoiLaunch L;
         const int staged = rois_fill(ctx->knobs, pl, frames, rois, outs, base, cnt, vec, L);
-        const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * cnt);
-        const hipError_t e = launch_rois(pl.mode, pl.out, vec, staged > 0, L, grid, (size_t)L.lds_bytes, (hipStream_t)stream, nullptr, 0, false);
+        const hipError_t e = launch_group(pl, vec, staged > 0, L, (hipStream_t)stream, nullptr, 0, false);
         if (e != hipSuccess) return (int)e;
     }
     return TSVPP_OK;
 }
 
-int tsvpp_describe_rois(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
-                        size_t buf_len) {
+static int describe_rois(bool area, const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
+                         size_t buf_len) {
     if (!buf || buf_len == 0) return TSVPP_ERROR;
     buf[0] = 0;
     RoiPlan pl;
-    const int sts = rois_plan(p, n_frames, frames, n_rois, rois, pl);
+    const int sts = rois_plan(p, n_frames, frames, n_rois, rois, pl, area);
     if (sts != TSVPP_OK) return sts;
     Knobs kn; // no context: no device, no streams
     read_env_knobs(kn);
@@ -117,21 +132,61 @@ int tsvpp_describe_rois(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *f
     int staged = 0, lds0 = 0, grid0 = 0, launches = 0;
     char kname[128] = "(none)";
     RoiLaunch L;
-    for (int base = 0; base < n_rois; base += TSVPP_MAX_ROIS, launches++) {
-        const int cnt = std::min(n_rois - base, (int)TSVPP_MAX_ROIS);
+    const int limit = launch_limit(pl);
+    for (int base = 0; base < n_rois; base += limit, launches++) {
+        const int cnt = std::min(n_rois - base, limit);
         const int s = rois_fill(kn, pl, fr.data(), rois, nullptr, base, cnt, vec, L);
         staged += s;
         if (base == 0) {
-            lds0 = L.lds_bytes;
+            lds0 = L.area_lds + L.lds_bytes;
             grid0 = L.tiles_x * L.tiles_y * cnt;
-            const hipError_t e = launch_rois(pl.mode, pl.out, vec, s > 0, L, (unsigned)grid0, (size_t)lds0, nullptr, kname, sizeof(kname), true);
+            const hipError_t e = launch_group(pl, vec, s > 0, L, nullptr, kname, sizeof(kname), true);
             if (e != hipSuccess) return (int)e;
         }
     }
-    std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d rois=%d frames=%d launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d staged=%d tail=%d nt=%d limit=%d",
-                  mode_names[pl.mode], out_names[pl.out], pl.dst_w, pl.dst_h, n_rois, n_frames, launches, kname, ROI_TX, ROI_TY, lds0 + roi_static_lds(pl.out, vec), grid0,
-                  L.tiles_x, L.tiles_y, staged, L.last_col0 > 0 ? 2 : 0, L.nt_stores, (int)TSVPP_MAX_ROIS);
+    const int n = std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d rois=%d frames=%d launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d staged=%d tail=%d nt=%d limit=%d",
+                                area ? "area" : mode_names[pl.mode], out_names[pl.out], pl.dst_w, pl.dst_h, n_rois, n_frames, launches, kname, ROI_TX, ROI_TY,
+                                lds0 + roi_static_lds(pl.out, vec), grid0, L.tiles_x, L.tiles_y, staged, L.last_col0 > 0 ? 2 : 0, L.nt_stores, limit);
+    if (area && n > 0 && (size_t)n < buf_len) std::snprintf(buf + n, buf_len - (size_t)n, " down=%d taps=%dx%d", pl.down, pl.taps_x, pl.taps_y);
     return TSVPP_OK;
+}
+
+extern "C" {
+
+int tsvpp_convert_rois(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
+                       void *stream) {
+    return convert_rois(false, ctx, n_frames, frames, n_rois, rois, p, outs, stream);
+}
+
+int tsvpp_describe_rois(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
+                        size_t buf_len) {
+    return describe_rois(false, p, n_frames, frames, n_rois, rois, aligned_outputs, buf, buf_len);
+}
+
+int tsvpp_convert_rois_area(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
+                            void *stream) {
+    return convert_rois(true, ctx, n_frames, frames, n_rois, rois, p, outs, stream);
+}
+
+int tsvpp_describe_rois_area(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
+                             size_t buf_len) {
+    return describe_rois(true, p, n_frames, frames, n_rois, rois, aligned_outputs, buf, buf_len);
+}
+
+// The generator of vpp_rois_area.hip's weight rows (roi_area_step, vpp_rois.h), evaluated on the host: rows of output indices first .. first + n - 1.
+int tsvpp_roi_area_rows(float scale, int first, int n, float *out, int max_floats, int *taps) {
+    if (!out || first < 0 || n <= 0) return TSVPP_ERROR;
+    if (!(scale > 1.0f) || (long)first + n > ROI_AREA_MAX_DST) return TSVPP_UNSUPPORTED;
+    const int t = roi_area_taps(scale);
+    if (t > ROI_AREA_MAX_TAPS) return TSVPP_UNSUPPORTED;
+    if (taps) *taps = t;
+    if ((long)n * t > (long)max_floats) return TSVPP_ERROR;
+    RoiAreaGen g;
+    for (int k = 0; k < first + n; k++) {
+        const RoiAreaRow r = roi_area_step(scale, g);
+        for (int e = 0; k >= first && e < t; e++) out[(long)(k - first) * t + e] = roi_area_weight(r, e);
+    }
+    return n;
 }
 
 } // extern "C"

@@ -10,6 +10,7 @@ LIB_PATH = os.path.normpath(os.path.join(_PKG, "..", "lib", "libtsvpp.so"))
 
 TSVPP_MAX_BATCH = 128
 TSVPP_MAX_ROIS = 64  # boxes per launch of tsvpp_convert_rois (their records travel in the kernarg segment)
+TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
 TSVPP_OPT_UNSAFE_COEFFS = 3
@@ -47,7 +48,7 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_channels", "tsvpp_convert", "tsvpp_convert_batch", "tsvpp_prepare", "tsvpp_prepare_batch", "tsvpp_enable_markers", "tsvpp_get_coeffs",
            "tsvpp_set_coeffs", "tsvpp_default_coeffs", "tsvpp_area_pattern", "tsvpp_describe", "tsvpp_strerror", "tsvpp_version",
            "tsvpp_table_create", "tsvpp_table_destroy", "tsvpp_table_set", "tsvpp_convert_table", "tsvpp_trim", "tsvpp_set_option", "tsvpp_get_option", "tsvpp_consumer_next_stream", "tsvpp_consumer_synchronize",
-           "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois"]
+           "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables"]
 
 _lib = None
 
@@ -103,6 +104,14 @@ def lib():
     L.tsvpp_convert_rois.restype = i32
     L.tsvpp_describe_rois.argtypes = [pp, i32, pn, i32, pr, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_describe_rois.restype = i32
+    L.tsvpp_convert_rois_area.argtypes = L.tsvpp_convert_rois.argtypes
+    L.tsvpp_convert_rois_area.restype = i32
+    L.tsvpp_describe_rois_area.argtypes = L.tsvpp_describe_rois.argtypes
+    L.tsvpp_describe_rois_area.restype = i32
+    L.tsvpp_roi_area_rows.argtypes = [ctypes.c_float, i32, i32, vp, i32, ctypes.POINTER(i32)]
+    L.tsvpp_roi_area_rows.restype = i32
+    L.tsvpp_debug_area_tables.argtypes = [vp]
+    L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_debug_last_launch.restype = i32
     L.tsvpp_strerror.argtypes = [i32]

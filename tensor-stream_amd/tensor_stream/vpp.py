@@ -222,7 +222,16 @@ class VideoProcessor:
         tensors: rows x pitch) or lists of them -- the frames may differ in size and pitch; rois: (left, top, right, bottom) boxes of frame 0 or
         (frame, left, top, right, bottom); width / height: the frames' picture size (an int for all frames or one per frame; default: the planes'
         own).  Returns (or fills `out`, indexed out[i]) a tensor of shape (n, ...frame shape) with the padded frame stride of convert_batch
-        (every box starts 16-byte aligned), on torch's current stream."""
+        (every box starts 16-byte aligned), on torch's current stream.  AREA has its own method, convert_rois_area; this one refuses it."""
+        return self._convert_rois(self._lib.tsvpp_convert_rois, ys, uvs, rois, params, out, width, height)
+
+    def convert_rois_area(self, ys, uvs, rois, params, out=None, width=None, height=None):
+        """convert_rois for ResizeType.AREA (tsvpp_convert_rois_area), same arguments and result: every box with both ratios above 1 is averaged with the AREA
+        down-scale, any other box takes AREA's up-scale rule; the weight rows are generated inside the kernel, so the call allocates and caches nothing however
+        many distinct box sizes it sees.  Any other resize type is refused."""
+        return self._convert_rois(self._lib.tsvpp_convert_rois_area, ys, uvs, rois, params, out, width, height)
+
+    def _convert_rois(self, entry, ys, uvs, rois, params, out, width, height):
         p = params.parameters if isinstance(params, FrameParameters) else params
         ys, uvs, boxes = _normalize_rois(ys, uvs, rois)
         widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
@@ -237,7 +246,7 @@ class VideoProcessor:
         recs = (N.Roi * n)(*[N.Roi(*b) for b in boxes])
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(self._lib.tsvpp_convert_rois(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), outs, stream))
+        N.check(entry(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), outs, stream))
         return out
 
     def make_batch(self, ys, uvs, params, out=None, width=None, height=None):
@@ -377,6 +386,15 @@ def _normalize_rois(ys, uvs, rois):
 def describe_rois(params, frames, rois, aligned_outputs=True):
     """What a convert_rois of this request would launch, as a dict (tsvpp_describe_rois: mode, out, rois, launches, kernel, grid, lds, staged, ...) -- host logic
     only, works without a GPU.  frames: (width, height) or (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list; rois as for convert_rois."""
+    return _describe_rois(N.lib().tsvpp_describe_rois, params, frames, rois, aligned_outputs)
+
+
+def describe_rois_area(params, frames, rois, aligned_outputs=True):
+    """describe_rois for convert_rois_area (tsvpp_describe_rois_area): the same keys, then down (boxes on the down-scale path) and taps ("<x>x<y>", the largest)."""
+    return _describe_rois(N.lib().tsvpp_describe_rois_area, params, frames, rois, aligned_outputs)
+
+
+def _describe_rois(entry, params, frames, rois, aligned_outputs):
     p = params.parameters if isinstance(params, FrameParameters) else params
     if frames and isinstance(frames[0], int):
         frames = [frames]
@@ -391,7 +409,7 @@ def describe_rois(params, frames, rois, aligned_outputs=True):
     fr = (N.NV12 * len(recs))(*recs)
     bx = (N.Roi * max(len(boxes), 1))(*[N.Roi(*b) for b in boxes])
     buf = ctypes.create_string_buffer(512)
-    N.check(N.lib().tsvpp_describe_rois(ctypes.byref(p), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
+    N.check(entry(ctypes.byref(p), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

@@ -3,6 +3,7 @@
 before tsvpp_convert_rois) against (b) ONE tsvpp_convert_rois -- on one stream, timed with HIP events.
 
     python tools/rois_ab.py [--out profiles/rois_ab.txt] [--repeats 20] [--iters 50] [--ns 1,4,16,32,64]
+    python tools/rois_ab.py --area [--out profiles/rois_area_ab.txt]      the AREA leg: tsvpp_convert_rois_area (see area_main)
 
 Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the
 MEDIAN block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next frame of a pool of 96 distinct 1080p frames
@@ -64,15 +65,145 @@ def timed(fn, stream, repeats, iters, warm):
     return blocks, k - 1
 
 
+AREA_CONFIGS = [("224x224 AREA BGR24 planar fp32", (224, 224), 2, 0, True),
+                ("112x112 AREA RGB24 merged uint8", (112, 112), 1, 1, False)]
+
+
+def area_main(a):
+    """The AREA leg, same protocol (seeded boxes with sides 64 .. 512, one stream, frames and outputs rotating through more than 256 MiB, median of the blocks):
+      (roi)  one tsvpp_convert_rois_area call
+      (warm) one tsvpp_convert(crop = box, AREA) per box in the context that has already built every box's tables
+      (cold) the same loop in a FRESH context per timed block: the first pass pays the table builds (one block of `iters` iterations, so the build cost is spread
+             over `iters` passes; the per-box figure of the first pass alone is printed beside it as `first`)
+      (bil)  one tsvpp_convert_rois BILINEAR call on the same boxes, for scale.
+    (roi) and (warm) are parity-checked against each other and against the CPU oracle on the last output set they wrote."""
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    base_y = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev, generator=gen)
+    base_uv = torch.randint(0, 256, (H // 2, W), dtype=torch.uint8, device=dev, generator=gen)
+    ys = [base_y + (37 * k) % 256 for k in range(a.frames)]
+    uvs = [base_uv + (37 * k) % 256 for k in range(a.frames)]
+    frames = [N.NV12(ys[k].data_ptr(), uvs[k].data_ptr(), W, W, W, H) for k in range(a.frames)]
+    lines = [f"# tools/rois_ab.py --area: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {a.frames} x 1080p "
+             f"({a.frames * W * H * 3 // 2 >> 20} MiB), median of {a.repeats} blocks of {a.iters} iterations, one stream",
+             "# (roi) = 1 x tsvpp_convert_rois_area   (warm) / (cold) = n x tsvpp_convert(crop = box, AREA), tables built / a fresh context per block   "
+             "(bil) = 1 x tsvpp_convert_rois BILINEAR", "# us per call, [min .. max of the blocks]; roofline = moved bytes / time / 8 TB/s of (roi); first = us per box of a fresh context's first pass"]
+    ok = True
+    for name, dst, fcc, planes, norm in AREA_CONFIGS:
+        mk = lambda rt, crop=(0, 0, 0, 0): ts.FrameParameters(width=dst[0], height=dst[1], crop_coords=crop, resize_type=rt, pixel_format=fcc, planes_pos=planes,
+                                                              normalization=norm).parameters
+        p_area, p_bil = mk(3), mk(1)
+        out_bytes = 3 * dst[0] * dst[1] * (4 if norm else 1)
+        lines += ["", f"## {name}",
+                  f"{'n':>3} | {'(roi) us':>9} {'spread':>15} {'roofline':>8} | {'(warm) us':>9} {'spread':>15} | {'(cold) us':>9} {'first/box':>9} | {'(bil) us':>8} | {'warm/roi':>8} {'roi/bil':>7}"]
+        for n in [int(v) for v in a.ns.split(",")]:
+            boxes = boxes_for(n, seed=100 + n)
+            sets = max(2, min(64, (300 << 20) // (n * out_bytes) + 1))
+            pool = [vpp._alloc(p_area, dst[0], dst[1], n) for _ in range(sets)]
+            moved = sum(out_bytes + (b[2] - b[0]) * (b[3] - b[1]) * 3 // 2 for b in boxes)
+            crops = [mk(3, b) for b in boxes]
+            crop_refs = [ctypes.byref(c) for c in crops]
+            frame_refs = [ctypes.byref(f) for f in frames]
+            out_ptrs = [[pool[s][i].data_ptr() for i in range(n)] for s in range(sets)]
+            conv = L.tsvpp_convert
+            recs = (N.Roi * n)(*[N.Roi(0, *b) for b in boxes])
+            out_arrs = [(ctypes.c_void_p * n)(*out_ptrs[s]) for s in range(sets)]
+            frame_arrs = [(N.NV12 * 1)(frames[k]) for k in range(a.frames)]
+            ra, rb, roi_area, roi_bil = ctypes.byref(p_area), ctypes.byref(p_bil), L.tsvpp_convert_rois_area, L.tsvpp_convert_rois
+
+            def loop_in(ctx):
+                def fn(k):
+                    fr, ptrs = frame_refs[k % a.frames], out_ptrs[k % sets]
+                    for i in range(n):
+                        if conv(ctx, fr, crop_refs[i], ptrs[i], raw) != 0:
+                            raise RuntimeError("tsvpp_convert failed")
+                return fn
+
+            def leg_roi(k):
+                if roi_area(vpp._ctx, 1, frame_arrs[k % a.frames], n, recs, ra, out_arrs[k % sets], raw) != 0:
+                    raise RuntimeError("tsvpp_convert_rois_area failed")
+
+            def leg_bil(k):
+                if roi_bil(vpp._ctx, 1, frame_arrs[k % a.frames], n, recs, rb, out_arrs[k % sets], raw) != 0:
+                    raise RuntimeError("tsvpp_convert_rois failed")
+
+            res, last_bits = {}, {}
+            for leg, fn in (("roi", leg_roi), ("warm", loop_in(vpp._ctx)), ("bil", leg_bil)):
+                for t in pool:
+                    t.zero_()
+                torch.cuda.synchronize()
+                blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(10, a.iters // 2))
+                res[leg] = blocks
+                if leg == "bil":
+                    continue
+                y, uv = ys[last % a.frames].cpu().numpy(), uvs[last % a.frames].cpu().numpy()
+                got = pool[last % sets]
+                for i, (l, t, r, b) in enumerate(boxes):
+                    ref = O.convert(y[t:b, l:r], uv[t // 2:t // 2 + (b - t) // 2, l:r], dst=dst, resize_type=3, fourcc=fcc, planes=planes, normalization=norm, nthreads=8)[0]
+                    if not np.array_equal(got[i].contiguous().cpu().numpy().ravel().view(np.uint8), ref.view(np.uint8).ravel()):
+                        raise SystemExit(f"PARITY FAILURE: leg ({leg}) {name} n={n} box {i} {(l, t, r, b)}")
+                # ... and the two legs against each other, on one frame and one output set
+                fn(0)
+                torch.cuda.synchronize()
+                last_bits[leg] = [pool[0][i].contiguous().cpu().numpy().ravel().view(np.uint8).copy() for i in range(n)]
+            if not all(np.array_equal(x, y) for x, y in zip(last_bits["roi"], last_bits["warm"])):
+                raise SystemExit(f"PARITY FAILURE: (roi) against (warm) {name} n={n}")
+            # cold: a fresh context per block; the block's first pass builds every box's tables
+            cold, first = [], []
+            for _ in range(min(a.repeats, 5)):
+                fresh = ts.VideoProcessor(device=0)
+                fn = loop_in(fresh._ctx)
+                torch.cuda.synchronize()
+                e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                e0.record(stream)
+                fn(0)
+                e1.record(stream)
+                for k in range(1, a.iters):
+                    fn(k)
+                e2.record(stream)
+                e2.synchronize()
+                first.append(e0.elapsed_time(e1) * 1e3 / n)
+                cold.append(e0.elapsed_time(e2) * 1e3 / a.iters)
+                fresh.Close()
+            m = {k: statistics.median(v) for k, v in res.items()}
+            sp = lambda v: f"{min(v):7.2f}..{max(v):<6.2f}"
+            lines.append(f"{n:>3} | {m['roi']:9.2f} {sp(res['roi'])} {moved / (m['roi'] * 1e-6) / HBM:8.4f} | {m['warm']:9.2f} {sp(res['warm'])} | "
+                         f"{statistics.median(cold):9.2f} {statistics.median(first):9.2f} | {m['bil']:8.2f} | {m['warm'] / m['roi']:8.2f} {m['roi'] / m['bil']:7.2f}")
+            print(lines[-1], flush=True)
+            if n >= 16 and not m["roi"] < m["warm"]:
+                ok = False
+            del pool
+            torch.cuda.empty_cache()
+    lines += ["", "# parity: (roi) and (warm) bit-exact against the CPU oracle on the last output set of every row, and against each other",
+              f"# condition (the ROI call faster than the warm loop at n = 16, 32, 64): {'met' if ok else 'NOT MET'}"]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rois_ab.txt"))
+    ap.add_argument("--area", action="store_true", help="the AREA leg (tsvpp_convert_rois_area); default output profiles/rois_area_ab.txt")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--ns", default="1,4,16,32,64")
     ap.add_argument("--frames", type=int, default=96)
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "rois_area_ab.txt" if a.area else "rois_ab.txt")
+    if a.area:
+        return area_main(a)
     O.build()
     L = N.lib()
     vpp = ts.VideoProcessor(device=0)

@@ -234,6 +234,55 @@ int tsvpp_describe_rois_area(const tsvpp_params *p, int n_frames, const tsvpp_nv
  * arguments or a buffer that is too small. */
 int tsvpp_roi_area_rows(float scale, int first, int n, float *out, int max_floats, int *taps);
 
+/* ---- letterbox (not in the reference: Convert stretches the frame to dst_width x dst_height) ----------------------------------------------------------------
+ * The frame in front of a detector: `n` NV12 frames, each resized WITH ITS ASPECT KEPT into an inner rectangle of one canvas of p->dst_width x p->dst_height, the
+ * rest of the canvas filled with a constant, in ceil(n / TSVPP_MAX_LETTERBOX) kernel launches (a Convert to the inner size into a temporary, a fill of the canvas
+ * and a strided copy are three launches and an extra write and read of the output).
+ *   in[k]       may differ in size and pitch from frame to frame, as in tsvpp_convert_rois.
+ *   outs[k]     device memory of canvas k, tight: channels * dst_width * dst_height elements of uint8 (p->normalization == 0) or float, laid out as
+ *               tsvpp_convert's output for a dst_width x dst_height frame.
+ *   rects       NULL: every frame gets the rectangle of tsvpp_letterbox_rect (below).  Else n rectangles, one per frame: left, top, width, height all even,
+ *               width and height > 0, inside the canvas.  The rectangle need not keep the aspect and may be larger than the frame (up-scaling).
+ *   pad_y/u/v   the pad, as one NV12 sample, each 0..255: (114, 128, 128) is gray 114 and (16, 128, 128) is black under the default coefficients.
+ *   p           dst_width / dst_height (the canvas: > 0, even), resize_type, fourcc, planes, normalization; p->crop_* must be zero.
+ * For frame k the canvas is, bit for bit:
+ *   inner rectangle   origin (left, top), size (width, height): what tsvpp_convert returns for that frame with dst = (width, height) and the same resize type,
+ *                     fourcc, planes and normalization -- the contract of tsvpp_convert_rois with the whole frame as the box, xr = (float)in_w / width,
+ *                     yr = (float)in_h / height.  A frame of exactly the inner size is the plain colour conversion.
+ *   pad               every pixel outside it: what the colour back end makes of the constant sample (pad_y, pad_u, pad_v), i.e. the value tsvpp_convert without a
+ *                     resize returns for a frame of that constant.  The pad is given in YUV because it then runs through the one colour back end the library has,
+ *                     in every flavour (uint8 and fp32, planar and merged, swapped channels, Y800 -- which keeps pad_y alone --, the TSVPP_OPT_COLOR_G_TERM
+ *                     variants), and needs no store code of its own.
+ * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  Not: AREA (its down-scale needs weight rows), NV12 / UYVY / YUV444 /
+ * HSV outputs, crops, frames out of a tsvpp_table, an RGB pad colour.
+ * `in`, `rects`, `outs` are HOST arrays and may be freed on return: the per-frame records (planes, pitches, size, ratios, rectangle, canvas pointer: 64 bytes)
+ * travel BY VALUE in the kernarg segment of their launch -- no allocation, no copy, no host synchronisation, nothing cached in the context, no replay cache --
+ * which is what bounds a launch to TSVPP_MAX_LETTERBOX frames.  The call is therefore legal while `stream` is being captured into a hipGraph.  Always an ordinary
+ * in-order launch (TSVPP_OPT_INPUTS_READY does not apply); TSVPP_OPT_COLOR_G_TERM and the context's coefficient block are honoured.
+ * Status, decided before any device is touched (tsvpp_describe_letterbox returns the same one), in this order:
+ *   TSVPP_ERROR        null arguments, n <= 0, a frame without size or with a pitch below its width, dst_width / dst_height <= 0, non-zero crop_* in `p`, a
+ *                      rectangle that is empty or not inside the canvas, a pad component outside 0..255 (and, converting: a null context, plane or output)
+ *   TSVPP_UNSUPPORTED  odd dst_*, an odd frame size, an odd rectangle field, AREA or an unknown resize type, an unknown `planes` value, an output format outside
+ *                      the list above, an output of 4 GiB or more. */
+#define TSVPP_MAX_LETTERBOX 32 /* frames per launch; more are split */
+typedef struct tsvpp_rect {
+    int32_t left, top, width, height;
+} tsvpp_rect;
+/* The default inner rectangle of an in_w x in_h frame in a dst_w x dst_h canvas: the largest even-sized rectangle of the frame's aspect (to the nearest even
+ * number), centred on an even origin.  64-bit integers only, so host, tests and callers agree:
+ *   in_w * dst_h >= in_h * dst_w:  width = dst_w,  height = 2 * ((in_h * dst_w + in_w) / (2 * in_w)) clamped to [2, dst_h]
+ *   otherwise:                     height = dst_h, width  = 2 * ((in_w * dst_h + in_h) / (2 * in_h)) clamped to [2, dst_w]
+ *   left = ((dst_w - width) / 2) & ~1, top = ((dst_h - height) / 2) & ~1.
+ * 1920 x 1080 into 640 x 640 gives 640 x 360 at (0, 140).  TSVPP_ERROR for a null `out` or a size <= 0, TSVPP_UNSUPPORTED for an odd dst_w / dst_h. */
+int tsvpp_letterbox_rect(int in_w, int in_h, int dst_w, int dst_h, tsvpp_rect *out);
+int tsvpp_convert_letterbox(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v,
+                            void *const *outs, void *stream);
+/* What tsvpp_convert_letterbox WOULD launch, as one line of key=value text with tsvpp_describe_rois's keys: "mode=bilinear out=f32_planar dst=640x640 frames=2
+ * launches=1 kernel=vpp_letterbox<...> shape=8x16 lds=.. grid=.. tiles=20x20 staged=.. tail=.. nt=.. limit=32", then "inner=WxH+left+top", the first frame's
+ * rectangle.  Host only: needs no context and no GPU, the plane pointers in `in` are not read; TSVPP_* knobs are honoured.  lds= / grid= are the first launch's;
+ * staged= is the number of frames whose every tile stages its source footprint in LDS (the others gather from global memory). */
+int tsvpp_describe_letterbox(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int aligned_outputs, char *buf, size_t buf_len);
+
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them
  * per frame, src/Resize.cu:389-406,436-452) and, for UYVY / YUV444 behind a resize, the resized-NV12 scratch of

@@ -202,6 +202,22 @@ int VideoProcessor::ConvertRoisArea(AVFrame *const *inputs, int nInputs, const t
     return convertRois(true, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
 }
 
+int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                                     std::string consumerName) {
+    if (isClosed || !inputs || n <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
+    void *stream = nullptr;
+    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    std::vector<tsvpp_nv12> frames((size_t)n);
+    for (int f = 0; f < n; f++) {
+        const AVFrame *in = inputs[f];
+        if (!in) CHECK_STATUS(VREADER_ERROR);
+        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
+    }
+    const tsvpp_params p = flatten(options); // options.resize is the canvas; options.crop must be empty
+    CHECK_STATUS(tsvpp_convert_letterbox(ctx, n, frames.data(), &p, rects, padY, padU, padV, deviceOuts, stream));
+    return VREADER_OK;
+}
+
 int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &options, std::string consumerName) {
     if (isClosed || !input || !output) CHECK_STATUS(VREADER_ERROR);
     const tsvpp_params p = flatten(options);

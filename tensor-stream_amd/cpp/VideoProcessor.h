@@ -123,6 +123,12 @@ public:
     // The same for options.resize.type == AREA (tsvpp_convert_rois_area: every box with both ratios above 1 is averaged, any other takes AREA's up-scale rule; no
     // weight table is built or cached).  ConvertRois refuses AREA and this refuses everything else: two entry points until the C ABI folds them.
     int ConvertRoisArea(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    // The frame in front of a detector (tsvpp_convert_letterbox, include/tsvpp.h; not in the reference): inputs[k] -- the frames may differ in size and pitch -- is
+    // resized with its aspect kept into rects[k] (null: the rectangle of tsvpp_letterbox_rect) of a canvas of options.resize.width x height, the rest of the canvas is
+    // the colour conversion of the sample (padY, padU, padV), written to deviceOuts[k] (caller-owned device memory of channels * width * height elements), one kernel
+    // launch per TSVPP_MAX_LETTERBOX frames on the consumer's stream.  options.crop must be empty; the inputs are NOT consumed.  Same status convention as ConvertInto.
+    int ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                         std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

@@ -4,6 +4,7 @@
 //   tsvpp_api.cpp    contexts, streams, knobs, the conversion itself and its replay cache, tsvpp_describe
 //   tsvpp_table.cpp  persistent frame tables
 //   tsvpp_rois.cpp   regions of interest (both entry points: NEAREST / BILINEAR / BICUBIC and AREA)
+//   tsvpp_letterbox.cpp  aspect-preserving resize into a padded canvas
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -236,6 +237,9 @@ inline constexpr const char *out_names[O_COUNT_ALL] = { "u8_planar", "u8_merged"
 // tsvpp_plan.cpp
 int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl);
 int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl, bool area = false);
+// (tsvpp_convert_letterbox / tsvpp_describe_letterbox; RoiPlan: the canvas is its dst_w x dst_h).  letterbox_rect_of: frame k's rectangle, the caller's or the default
+int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);
+tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int k, int dst_w, int dst_h);
 // tsvpp_area.cpp: the AREA down-scale fields of a descriptor (nothing for any other mode), out of the context's tables or -- a dry run -- with stand-in pointers
 int area_desc(tsvpp_ctx *ctx, const Plan &pl, hipStream_t stream, LaunchDesc &d);
 int area_desc(const Knobs &kn, const Plan &pl, LaunchDesc &d);

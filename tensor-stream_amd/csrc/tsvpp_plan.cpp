@@ -1,5 +1,6 @@
 // tsvpp_plan.cpp -- a request resolved on the host alone: tsvpp_params (+ frame geometry, + boxes) -> Plan / RoiPlan.  No HIP runtime call.
-// The order in which make_plan and rois_plan return their statuses is part of the ABI (tests/test_plan_cpu.py, test_rois_cpu.py, test_abi_cpu.py).
+// The order in which make_plan, rois_plan and letterbox_plan return their statuses is part of the ABI (tests/test_plan_cpu.py, test_rois_cpu.py, test_abi_cpu.py,
+// test_letterbox_cpu.py).
 #include <cmath>
 
 #include "tsvpp_host.h"
@@ -234,6 +235,52 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
             pl.taps_y = ty > pl.taps_y ? ty : pl.taps_y;
         }
     }
+    return TSVPP_OK;
+}
+
+// The rectangle of frame k: the caller's, or the default one (tsvpp_letterbox_rect; sizes are positive and the canvas even by the time this is asked)
+tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int k, int dst_w, int dst_h) {
+    if (rects) return rects[k];
+    tsvpp_rect r = {};
+    (void)tsvpp_letterbox_rect(in[k].width, in[k].height, dst_w, dst_h, &r);
+    return r;
+}
+
+int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl) {
+    // TSVPP_ERROR: arguments that describe no request at all
+    if (!p || !in || n <= 0) return TSVPP_ERROR;
+    for (int f = 0; f < n; f++) {
+        const tsvpp_nv12 &fr = in[f];
+        if (fr.width <= 0 || fr.height <= 0) return TSVPP_ERROR;
+        if (pitch_or_width(fr.pitch_y, fr.width) < fr.width || pitch_or_width(fr.pitch_uv, fr.width) < fr.width) return TSVPP_ERROR;
+    }
+    if (p->dst_width <= 0 || p->dst_height <= 0) return TSVPP_ERROR;
+    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the whole frame goes into the rectangle
+    for (int f = 0; rects && f < n; f++) {
+        const tsvpp_rect &r = rects[f];
+        if (r.width <= 0 || r.height <= 0 || r.left < 0 || r.top < 0) return TSVPP_ERROR;
+        if ((long)r.left + r.width > p->dst_width || (long)r.top + r.height > p->dst_height) return TSVPP_ERROR;
+    }
+    if (pad_y < 0 || pad_y > 255 || pad_u < 0 || pad_u > 255 || pad_v < 0 || pad_v > 255) return TSVPP_ERROR;
+    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
+    if ((p->dst_width | p->dst_height) & 1) return TSVPP_UNSUPPORTED;
+    for (int f = 0; f < n; f++)
+        if ((in[f].width | in[f].height) & 1) return TSVPP_UNSUPPORTED;
+    for (int f = 0; rects && f < n; f++) // (the default rectangle of an even canvas is even)
+        if ((rects[f].left | rects[f].top | rects[f].width | rects[f].height) & 1) return TSVPP_UNSUPPORTED;
+    // AREA: its down-scale needs weight rows (vpp_rois_area.hip generates them per tile); not in this kernel yet
+    if (!resize_mode(p->resize_type, pl.mode) || pl.mode == M_AREA_DOWN) return TSVPP_UNSUPPORTED;
+    if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
+    const bool f32 = p->normalization != 0;
+    if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV
+    const int channels = p->fourcc == TSVPP_Y800 ? 1 : 3;
+    pl.dst_w = p->dst_width;
+    pl.dst_h = p->dst_height;
+    pl.out_bytes = (size_t)channels * (size_t)pl.dst_w * (size_t)pl.dst_h * (f32 ? sizeof(float) : 1);
+    if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
+    // (the rectangle travels in 32-bit fields: a canvas side has no limit of its own.  The grid does: one workgroup per canvas tile and frame)
+    if ((long)((pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * TSVPP_MAX_LETTERBOX >= (1L << 31)) return TSVPP_UNSUPPORTED;
+    pl.down = pl.taps_x = pl.taps_y = 0;
     return TSVPP_OK;
 }
 

@@ -11,6 +11,7 @@ LIB_PATH = os.path.normpath(os.path.join(_PKG, "..", "lib", "libtsvpp.so"))
 TSVPP_MAX_BATCH = 128
 TSVPP_MAX_ROIS = 64  # boxes per launch of tsvpp_convert_rois (their records travel in the kernarg segment)
 TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
+TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
 TSVPP_OPT_UNSAFE_COEFFS = 3
@@ -38,6 +39,11 @@ class Roi(ctypes.Structure):
                 ("right", ctypes.c_int32), ("bottom", ctypes.c_int32)]
 
 
+class Rect(ctypes.Structure):
+    """struct tsvpp_rect: the inner rectangle of a letterboxed canvas (tsvpp_convert_letterbox)."""
+    _fields_ = [("left", ctypes.c_int32), ("top", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
 class Coeffs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in
                 ("y_scale", "v_to_r", "u_to_b", "v_to_g", "u_to_g", "round_bias", "y_offset", "c_offset")]
@@ -48,7 +54,8 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_channels", "tsvpp_convert", "tsvpp_convert_batch", "tsvpp_prepare", "tsvpp_prepare_batch", "tsvpp_enable_markers", "tsvpp_get_coeffs",
            "tsvpp_set_coeffs", "tsvpp_default_coeffs", "tsvpp_area_pattern", "tsvpp_describe", "tsvpp_strerror", "tsvpp_version",
            "tsvpp_table_create", "tsvpp_table_destroy", "tsvpp_table_set", "tsvpp_convert_table", "tsvpp_trim", "tsvpp_set_option", "tsvpp_get_option", "tsvpp_consumer_next_stream", "tsvpp_consumer_synchronize",
-           "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables"]
+           "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables",
+           "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox"]
 
 _lib = None
 
@@ -110,6 +117,13 @@ def lib():
     L.tsvpp_describe_rois_area.restype = i32
     L.tsvpp_roi_area_rows.argtypes = [ctypes.c_float, i32, i32, vp, i32, ctypes.POINTER(i32)]
     L.tsvpp_roi_area_rows.restype = i32
+    pc = ctypes.POINTER(Rect)
+    L.tsvpp_letterbox_rect.argtypes = [i32, i32, i32, i32, pc]
+    L.tsvpp_letterbox_rect.restype = i32
+    L.tsvpp_convert_letterbox.argtypes = [vp, i32, pn, pp, pc, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_letterbox.restype = i32
+    L.tsvpp_describe_letterbox.argtypes = [pp, i32, pn, pc, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_letterbox.restype = i32
     L.tsvpp_debug_area_tables.argtypes = [vp]
     L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

@@ -249,6 +249,33 @@ class VideoProcessor:
         N.check(entry(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), outs, stream))
         return out
 
+    def convert_letterbox(self, ys, uvs, params, pad=(114, 128, 128), rects=None, out=None, width=None, height=None):
+        """The frame in front of a detector (tsvpp_convert_letterbox): every frame is resized with its aspect kept into an inner rectangle of ONE canvas of params'
+        width x height, the rest of the canvas is `pad`, one launch per 32 frames.  ys / uvs: 3-D uint8 tensors (n, rows, pitch) or lists of 2-D tensors -- the
+        frames may differ in size and pitch; pad: (Y, U, V), each 0..255 ((114, 128, 128): gray 114, (16, 128, 128): black); rects: one (left, top, width,
+        height) per frame, all even and inside the canvas, or None for letterbox_rect's; width / height: the frames' picture size (an int for all frames or one per
+        frame; default: the planes' own).  Returns (out, rects): `out` (filled, or allocated with convert_batch's padded frame stride) has shape (n, ...frame shape),
+        on torch's current stream; `rects` is the list of (left, top, width, height) that was used, to map detections back."""
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        n = len(ys)
+        if n == 0:
+            raise RuntimeError("-3: convert_letterbox needs at least one frame")
+        widths, heights = _per_frame(width, n), _per_frame(height, n)
+        frames = (N.NV12 * n)(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(n)])
+        if out is None:
+            if p.dst_width <= 0 or p.dst_height <= 0 or (p.dst_width | p.dst_height) & 1:
+                raise RuntimeError("-3: convert_letterbox needs an even, positive canvas size (width / height of the parameters)")
+            out = self._alloc(p, p.dst_width, p.dst_height, n)  # (a frame of the canvas size: no stage changes it)
+        recs = None if rects is None else _rects(rects, n)
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        N.check(self._lib.tsvpp_convert_letterbox(self._ctx, n, frames, ctypes.byref(p), recs, int(pad[0]), int(pad[1]), int(pad[2]), outs, stream))
+        if recs is None:  # (the request was accepted: sizes are positive, the canvas is even)
+            used = [letterbox_rect(frames[i].width, frames[i].height, p.dst_width, p.dst_height) for i in range(n)]
+        else:
+            used = [(r.left, r.top, r.width, r.height) for r in recs]
+        return out, used
+
     def make_batch(self, ys, uvs, params, out=None, width=None, height=None):
         """Pre-builds the descriptor arrays of a batch (the per-frame structs are built once, not per
         call): returns a handle for run_batch().  Keeps the tensors alive."""
@@ -410,6 +437,38 @@ def _describe_rois(entry, params, frames, rois, aligned_outputs):
     bx = (N.Roi * max(len(boxes), 1))(*[N.Roi(*b) for b in boxes])
     buf = ctypes.create_string_buffer(512)
     N.check(entry(ctypes.byref(p), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def _rects(rects, n):
+    rects = [tuple(int(v) for v in r) for r in rects]
+    if len(rects) != n or any(len(r) != 4 for r in rects):
+        raise ValueError(f"{n} frames need {n} rectangles (left, top, width, height)")
+    return (N.Rect * n)(*[N.Rect(*r) for r in rects])
+
+
+def letterbox_rect(in_w, in_h, dst_w, dst_h):
+    """The default inner rectangle (left, top, width, height) of an in_w x in_h frame in a dst_w x dst_h canvas (tsvpp_letterbox_rect): integer arithmetic only."""
+    r = N.Rect()
+    N.check(N.lib().tsvpp_letterbox_rect(int(in_w), int(in_h), int(dst_w), int(dst_h), ctypes.byref(r)))
+    return (r.left, r.top, r.width, r.height)
+
+
+def describe_letterbox(params, frames, rects=None, aligned_outputs=True):
+    """What a convert_letterbox of this request would launch, as a dict (tsvpp_describe_letterbox: describe_rois's keys, then inner = "WxH+left+top" of the first
+    frame) -- host logic only, works without a GPU.  frames: (width, height) or (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    if frames and isinstance(frames[0], int):
+        frames = [frames]
+    recs = []
+    for f in frames:
+        f = tuple(int(v) for v in f)
+        py = f[2] if len(f) > 2 else 0
+        recs.append(N.NV12(None, None, py, f[3] if len(f) > 3 else py, f[0], f[1]))
+    fr = (N.NV12 * max(len(recs), 1))(*recs)
+    rc = None if rects is None else _rects(rects, len(recs))
+    buf = ctypes.create_string_buffer(512)
+    N.check(N.lib().tsvpp_describe_letterbox(ctypes.byref(p), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

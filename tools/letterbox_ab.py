@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""A/B: n 1080p frames (pitch 2048) letterboxed into 640 x 640 canvases -- (loop) the three steps the library offered before tsvpp_convert_letterbox: one
+tsvpp_convert_batch to 640 x 360 into a temporary, a fill of the canvases, a strided copy of the temporary into them -- against (fused) ONE
+tsvpp_convert_letterbox -- on one stream, timed with HIP events.
+
+    python tools/letterbox_ab.py [--out profiles/letterbox_ab.txt] [--repeats 20] [--iters 30] [--ns 1,8,32]
+
+Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the MEDIAN
+block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next n frames of a pool of 96 distinct frames (316 MB) and the next
+canvas set of a pool of more than 256 MiB, so that neither the 256 MiB last-level cache nor L2 serves a second pass over the same bytes.  Before a number is
+printed both legs are parity-checked against the CPU oracle on the last canvas set they wrote (every canvas, bit for bit: pad from the oracle's conversion of a
+constant frame, the inner block from the oracle's resize of the frame to 640 x 360).  The fill and the copy of (loop) are torch's (one kernel each); the pad is gray
+114, whose three channels are equal, so one fill serves every layout.
+"bytes" = what a frame moves at the least: its source planes (1920 x 1080 x 1.5) + its canvas; "roofline" = bytes / time as a fraction of 8 TB/s."""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tensor-stream_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import tensor_stream as ts  # noqa: E402
+from oracle import oracle as O  # noqa: E402
+from tensor_stream import _native as N  # noqa: E402
+
+W, H, PITCH = 1920, 1080, 2048
+CW, CH = 640, 640
+PAD = (114, 128, 128)
+HBM = 8e12
+CONFIGS = [("640x640 BILINEAR BGR24 planar fp32", 1, 2, 0, True),
+           ("640x640 BILINEAR RGB24 merged uint8", 1, 1, 1, False)]
+
+
+def timed(fn, stream, repeats, iters, warm):
+    for k in range(warm):
+        fn(k)
+    stream.synchronize()
+    blocks = []
+    k = warm
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(iters):
+            fn(k)
+            k += 1
+        e1.record(stream)
+        e1.synchronize()
+        blocks.append(e0.elapsed_time(e1) * 1e3 / iters)  # us per iteration
+    return blocks, k - 1
+
+
+def expected(y, uv, rect, rt, fcc, planes, norm):
+    """the canvas of one frame from the oracle alone, as bytes"""
+    left, top, iw, ih = rect
+    pref = O.convert(np.full((2, 2), PAD[0], np.uint8), np.array([[PAD[1], PAD[2]]], np.uint8), fourcc=fcc, planes=planes, normalization=norm)[0]
+    inner = O.convert(y[:, :W], uv[:, :W], dst=(iw, ih), resize_type=rt, fourcc=fcc, planes=planes, normalization=norm, nthreads=8)[0]
+    if planes == 0:
+        out = np.empty((3, CH, CW), pref.dtype)
+        out[:] = pref.reshape(3, 2, 2)[:, 0, 0][:, None, None]
+        out[:, top:top + ih, left:left + iw] = inner.reshape(3, ih, iw)
+    else:
+        out = np.empty((CH, CW, 3), pref.dtype)
+        out[:] = pref.reshape(2, 2, 3)[0, 0]
+        out[top:top + ih, left:left + iw, :] = inner.reshape(ih, iw, 3)
+    return out.ravel().view(np.uint8)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "letterbox_ab.txt"))
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--ns", default="1,8,32")
+    ap.add_argument("--frames", type=int, default=96)
+    a = ap.parse_args()
+    assert a.repeats >= 1 and a.iters >= 1
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    base_y = torch.randint(0, 256, (H, PITCH), dtype=torch.uint8, device=dev, generator=gen)
+    base_uv = torch.randint(0, 256, (H // 2, PITCH), dtype=torch.uint8, device=dev, generator=gen)
+    ys = [base_y + (37 * k) % 256 for k in range(a.frames)]  # distinct frames: every byte + 37 k (mod 256)
+    uvs = [base_uv + (37 * k) % 256 for k in range(a.frames)]
+    frames = [N.NV12(ys[k].data_ptr(), uvs[k].data_ptr(), PITCH, PITCH, W, H) for k in range(a.frames)]
+    rect = ts.letterbox_rect(W, H, CW, CH)
+    left, top, iw, ih = rect
+    assert rect == (0, 140, 640, 360)
+    lines = [f"# tools/letterbox_ab.py: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {a.frames} x 1080p pitch {PITCH} "
+             f"({a.frames * PITCH * H * 3 // 2 >> 20} MiB), median of {a.repeats} blocks of {a.iters} iterations, one stream",
+             f"# (loop) = tsvpp_convert_batch to {iw}x{ih} into a temporary + fill of the canvases + strided copy   (fused) = 1 x tsvpp_convert_letterbox   "
+             "spread = min .. max of the blocks   roofline = (source planes + canvas) / time / 8 TB/s"]
+    ok = True
+    for name, rt, fcc, planes, norm in CONFIGS:
+        mk = lambda w, h: ts.FrameParameters(width=w, height=h, resize_type=rt, pixel_format=fcc, planes_pos=planes, normalization=norm).parameters
+        p_canvas, p_inner = mk(CW, CH), mk(iw, ih)
+        esz = 4 if norm else 1
+        canvas_bytes = 3 * CW * CH * esz
+        moved_frame = W * H * 3 // 2 + canvas_bytes
+        pad_value = float(expected_pad(fcc, planes, norm))
+        lines += ["", f"## {name}",
+                  f"{'n':>3} | {'(loop) us':>10} {'us/frame':>8} {'spread':>17} {'roofline':>8} | {'(fused) us':>10} {'us/frame':>8} {'spread':>17} {'roofline':>8} | {'loop/fused':>10}"]
+        for n in [int(v) for v in a.ns.split(",")]:
+            sets = max(2, (300 << 20) // (n * canvas_bytes) + 1)
+            pool = [vpp._alloc(p_canvas, CW, CH, n) for _ in range(sets)]
+            tmp = vpp._alloc(p_inner, iw, ih, n)
+            groups = max(1, a.frames // n)  # iteration k converts frames [g n, g n + n), g = k mod groups
+            frame_arrs = [(N.NV12 * n)(*[frames[(g * n + i) % a.frames] for i in range(n)]) for g in range(groups)]
+            out_arrs = [(ctypes.c_void_p * n)(*[pool[s][i].data_ptr() for i in range(n)]) for s in range(sets)]
+            tmp_arr = (ctypes.c_void_p * n)(*[tmp[i].data_ptr() for i in range(n)])
+            inner_views = [(t[:, :, top:top + ih, left:left + iw] if planes == 0 else t[:, top:top + ih, left:left + iw, :]) for t in pool]
+            ctx, rc, ri = vpp._ctx, ctypes.byref(p_canvas), ctypes.byref(p_inner)
+            batch, fused = L.tsvpp_convert_batch, L.tsvpp_convert_letterbox
+
+            def leg_loop(k):
+                if batch(ctx, n, frame_arrs[k % groups], ri, tmp_arr, raw) != 0:
+                    raise RuntimeError("tsvpp_convert_batch failed")
+                pool[k % sets].fill_(pad_value)
+                inner_views[k % sets].copy_(tmp)
+
+            def leg_fused(k):
+                if fused(ctx, n, frame_arrs[k % groups], rc, None, PAD[0], PAD[1], PAD[2], out_arrs[k % sets], raw) != 0:
+                    raise RuntimeError("tsvpp_convert_letterbox failed")
+
+            res = {}
+            with torch.cuda.stream(stream):
+                for leg, fn in (("loop", leg_loop), ("fused", leg_fused)):
+                    for t in pool:
+                        t.zero_()
+                    torch.cuda.synchronize()
+                    blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(5, a.iters // 2))
+                    got = pool[last % sets]
+                    for i in range(n):
+                        f = ((last % groups) * n + i) % a.frames
+                        ref = expected(ys[f].cpu().numpy(), uvs[f].cpu().numpy(), rect, rt, fcc, planes, norm)
+                        if not np.array_equal(got[i].contiguous().cpu().numpy().ravel().view(np.uint8), ref):
+                            raise SystemExit(f"PARITY FAILURE: leg ({leg}) {name} n={n} canvas {i}")
+                    res[leg] = blocks
+            ml, mf = statistics.median(res["loop"]), statistics.median(res["fused"])
+            cols = []
+            for m, blocks in ((ml, res["loop"]), (mf, res["fused"])):
+                cols.append(f"{m:10.2f} {m / n:8.2f} {min(blocks):8.2f}..{max(blocks):<7.2f} {n * moved_frame / (m * 1e-6) / HBM:8.4f}")
+            lines.append(f"{n:>3} | {cols[0]} | {cols[1]} | {ml / mf:10.2f}")
+            print(lines[-1], flush=True)
+            if n >= 8 and not mf <= ml:
+                ok = False
+            del pool, tmp, inner_views
+            torch.cuda.empty_cache()
+    lines += ["", "# parity: both legs bit-exact against the CPU oracle on the last canvas set of every row",
+              f"# condition (the fused call not slower than the loop at n = 8 and n = 32): {'met' if ok else 'NOT MET'}"]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
+def expected_pad(fcc, planes, norm):
+    """the pad of PAD in this flavour: one value, because gray's channels are equal"""
+    px = O.convert(np.full((2, 2), PAD[0], np.uint8), np.array([[PAD[1], PAD[2]]], np.uint8), fourcc=fcc, planes=planes, normalization=norm)[0]
+    assert np.all(px == px[0])
+    return px[0]
+
+
+if __name__ == "__main__":
+    main()

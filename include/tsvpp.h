@@ -173,8 +173,8 @@ int tsvpp_convert_table(tsvpp_ctx *ctx, const tsvpp_table *table, int first, int
  * with xr = (float)width / dst_width, yr = (float)height / dst_height; for a box Convert's crop stage accepts it equals tsvpp_convert(crop = box).  A box of
  * exactly dst_width x dst_height is a plain colour conversion (every interpolation weight is zero).
  * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  TSVPP_UNSUPPORTED here: AREA (it has an entry point
- * of its own, tsvpp_convert_rois_area below), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes, rotated boxes,
- * fp16 outputs.
+ * of its own, tsvpp_convert_rois_area below), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes, rotated boxes.
+ * fp16 / bf16 outputs and a per-channel mean / scale are tsvpp_convert_rois_tensor's (below), not this call's.
  * `frames`, `rois`, `outs` are HOST arrays and may be freed on return: the per-box records (plane origins, pitches, size, ratios, output pointer: 48 bytes)
  * travel BY VALUE in the kernarg segment of their launch -- no staging buffer, no copy, no allocation, no host synchronisation -- which is what bounds a
  * launch to TSVPP_MAX_ROIS boxes.  The call is therefore legal while `stream` is being captured into a hipGraph: the graph replays the records (the pointers
@@ -220,7 +220,7 @@ int tsvpp_describe_rois(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *f
  *   deviation     tsvpp_convert refuses (TSVPP_UNSUPPORTED) a ratio whose weight pattern does not close within 65536 rows.  This call never needs more than
  *                 dst_width / dst_height rows and answers such a box with the generator's rows (the rows tsvpp_convert's table would begin with).
  * Why a second entry point instead of one more resize type of tsvpp_convert_rois: that call's answer to AREA (TSVPP_UNSUPPORTED, from tsvpp_describe_rois,
- * tsvpp_convert_rois and the Python / C++ facades alike) is pinned by its tests; folding the two entry points into one is a later change that edits those tests.
+ * tsvpp_convert_rois and the Python / C++ facades alike) is pinned by its tests.  tsvpp_convert_rois_tensor (below) is the folded form: it takes all four resize types.
  * tsvpp_describe_rois_area prints tsvpp_describe_rois's keys (mode=area, kernel=vpp_rois_area<...>, limit=64; lds= includes the weight rows) and then
  * "down=<boxes on the down-scale path> taps=<largest taps_x>x<largest taps_y>" (0x0 without a down-scale box). */
 #define TSVPP_MAX_ROIS_AREA 64 /* boxes per launch; more are split (the per-box record is tsvpp_convert_rois's: nothing had to grow) */
@@ -282,6 +282,50 @@ int tsvpp_convert_letterbox(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const t
  * rectangle.  Host only: needs no context and no GPU, the plane pointers in `in` are not read; TSVPP_* knobs are honoured.  lds= / grid= are the first launch's;
  * staged= is the number of frames whose every tile stages its source footprint in LDS (the others gather from global memory). */
 int tsvpp_describe_letterbox(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- tensors for a network: fp16 / bf16 / fp32 elements, per-channel mean and scale (not in the reference) ---------------------------------------------------
+ * tsvpp_convert_rois / tsvpp_convert_rois_area / tsvpp_convert_letterbox stop one step short of what a network takes: they hand over fp32 x / 255, and the caller
+ * runs a second element-wise pass for (x / 255 - mean[c]) / std[c], usually into half precision.  These entry points store that value themselves.
+ * Contract.  Let q be the fp32 value the existing entry point stores for an element with p->normalization != 0: k / 255 correctly rounded, k the clamped colour
+ * byte or the Y800 sample.  The element of stored channel c is
+ *     cvt(dtype, (q - mean[c]) * scale[c])
+ *   - two fp32 operations, a subtraction and then a multiplication, each rounded once, nothing fused;
+ *   - TSVPP_F16 / TSVPP_BF16: converted ONCE, round to nearest even, IEEE: fp16 subnormals are kept, a magnitude beyond the type's range becomes infinity;
+ *   - c indexes the channel AS STORED: plane 0, 1, 2 after the RGB / BGR choice (BGR24: mean[0] belongs to blue); Y800 uses mean[0] and scale[0] alone;
+ *   - the caller passes scale = 1 / std: the library never divides;
+ *   - dtype = TSVPP_F32, mean = 0, scale = 1 gives exactly the bits of the existing entry point;
+ *   - in a letterbox canvas the pad pixel goes through the same expression as every sample.
+ * Everything else is the existing entry point's, word for word: box and rectangle rules, output layout (planar: NCHW), splitting at TSVPP_MAX_ROIS (all four
+ * resize types) / TSVPP_MAX_LETTERBOX, records by value in the kernarg segment, no allocation, no copy, no host synchronisation, legal under stream capture.
+ * tsvpp_convert_rois_tensor accepts all four resize types: TSVPP_AREA runs tsvpp_convert_rois_area's kernel with that call's rules and limits (per box down-scale or
+ * up-scale rule, at most 40 taps per axis, dst_width / dst_height up to 65536).
+ * Supported outputs: RGB24 / BGR24 with TSVPP_PLANAR, and Y800, in all three dtypes.  MERGED (interleaved) tensor output is out of scope: TSVPP_UNSUPPORTED.
+ *   outs[i]     tsvpp_tensor_bytes(p, spec) bytes, aligned to the element (2 or 4 bytes; TSVPP_ERROR otherwise).  16-byte aligned outputs take the vector stores,
+ *               any other the element-wise kernel, as in the existing entry points.
+ * Status, decided before any device is touched (the describe call returns the same one), in this order:
+ *   1. the status of the existing entry point for the request (tsvpp_convert_rois's rules, tsvpp_convert_rois_area's for TSVPP_AREA, tsvpp_convert_letterbox's), if
+ *      it is not TSVPP_OK;
+ *   2. TSVPP_ERROR for a null `spec`, or a mean or scale that is not finite, or a scale of zero, in a channel the format uses (Y800: channel 0);
+ *   3. TSVPP_UNSUPPORTED for an unknown dtype, p->normalization == 0, TSVPP_MERGED with RGB24 / BGR24, a fourcc outside RGB24 / BGR24 / Y800.
+ * The describe calls print the existing keys; out= is f16_planar / bf16_planar / f32n_planar (Y800: f16_y800 / bf16_y800 / f32n_y800), kernel= names the tensor
+ * instantiation (vpp_rois_tensor<...>, vpp_rois_area_tensor<...>, vpp_letterbox_tensor<...>; fp16 and bf16 share one, EL_HALF, that branches on the launch's dtype). */
+enum tsvpp_dtype { TSVPP_F32 = 0, TSVPP_F16 = 1, TSVPP_BF16 = 2 };
+typedef struct tsvpp_tensor_spec {
+    int32_t dtype;  /* tsvpp_dtype */
+    float mean[3];  /* per stored channel, in units of q (0..1) */
+    float scale[3]; /* 1 / std */
+} tsvpp_tensor_spec; /* 28 bytes */
+/* channels * dst_width * dst_height * element size of one output; 0 for a (p, spec) pair the tensor entry points refuse (rules 2 and 3 above, a null `p`,
+ * dst_width / dst_height that are not positive and even, an output of 4 GiB or more as fp32) */
+size_t tsvpp_tensor_bytes(const tsvpp_params *p, const tsvpp_tensor_spec *spec);
+int tsvpp_convert_rois_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
+                              const tsvpp_tensor_spec *spec, void *const *outs, void *stream);
+int tsvpp_describe_rois_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois,
+                               int aligned_outputs, char *buf, size_t buf_len);
+int tsvpp_convert_letterbox_tensor(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec, const tsvpp_rect *rects,
+                                   int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
+int tsvpp_describe_letterbox_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
+                                    int aligned_outputs, char *buf, size_t buf_len);
 
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them

@@ -175,8 +175,11 @@ int VideoProcessor::ConvertInto(AVFrame *input, void *deviceOut, FrameParameters
     return VREADER_OK;
 }
 
-// ConvertRois and ConvertRoisArea differ in the entry point of the C ABI they end in
-static int convertRois(bool area, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts,
+static int convertLetterbox(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY,
+                            int padU, int padV, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName);
+
+// ConvertRois, ConvertRoisArea and the tensor overload differ in the entry point of the C ABI they end in (`tensor`: tsvpp_convert_rois_tensor with `spec`)
+static int convertRois(bool area, bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts,
                        FrameParameters &options, const std::string &consumerName) {
     if (isClosed || !inputs || nInputs <= 0 || !rois || nRois <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
     void *stream = nullptr;
@@ -188,22 +191,38 @@ static int convertRois(bool area, tsvpp_ctx *ctx, bool isClosed, AVFrame *const 
         frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
     }
     const tsvpp_params p = flatten(options); // options.crop must be empty: the boxes are the crops
-    CHECK_STATUS((area ? tsvpp_convert_rois_area : tsvpp_convert_rois)(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
+    if (tensor) CHECK_STATUS(tsvpp_convert_rois_tensor(ctx, nInputs, frames.data(), nRois, rois, &p, spec, deviceOuts, stream));
+    else CHECK_STATUS((area ? tsvpp_convert_rois_area : tsvpp_convert_rois)(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
     return VREADER_OK;
 }
 
 int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                 std::string consumerName) {
-    return convertRois(false, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+    return convertRois(false, false, nullptr, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
 }
 
 int VideoProcessor::ConvertRoisArea(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                     std::string consumerName) {
-    return convertRois(true, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+    return convertRois(true, false, nullptr, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+}
+
+int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertRois(false, true, spec, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
 }
 
 int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                                      std::string consumerName) {
+    return convertLetterbox(false, nullptr, ctx, isClosed, inputs, n, rects, padY, padU, padV, deviceOuts, options, consumerName);
+}
+
+int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                                     const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertLetterbox(true, spec, ctx, isClosed, inputs, n, rects, padY, padU, padV, deviceOuts, options, consumerName);
+}
+
+static int convertLetterbox(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY,
+                            int padU, int padV, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName) {
     if (isClosed || !inputs || n <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
     void *stream = nullptr;
     CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
@@ -214,7 +233,8 @@ int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_
         frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
     }
     const tsvpp_params p = flatten(options); // options.resize is the canvas; options.crop must be empty
-    CHECK_STATUS(tsvpp_convert_letterbox(ctx, n, frames.data(), &p, rects, padY, padU, padV, deviceOuts, stream));
+    if (tensor) CHECK_STATUS(tsvpp_convert_letterbox_tensor(ctx, n, frames.data(), &p, spec, rects, padY, padU, padV, deviceOuts, stream));
+    else CHECK_STATUS(tsvpp_convert_letterbox(ctx, n, frames.data(), &p, rects, padY, padU, padV, deviceOuts, stream));
     return VREADER_OK;
 }
 

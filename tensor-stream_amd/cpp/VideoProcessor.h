@@ -129,6 +129,13 @@ public:
     // launch per TSVPP_MAX_LETTERBOX frames on the consumer's stream.  options.crop must be empty; the inputs are NOT consumed.  Same status convention as ConvertInto.
     int ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                          std::string consumerName);
+    // What a network takes (tsvpp_convert_rois_tensor / tsvpp_convert_letterbox_tensor, include/tsvpp.h): the same calls with a tensor spec -- element type
+    // (TSVPP_F16 / TSVPP_BF16 / TSVPP_F32), mean and scale (= 1 / std) per stored channel; every element is cvt((x / 255 - mean[c]) * scale[c]).  options.color:
+    // RGB24 / BGR24 PLANAR or Y800, normalization = true; deviceOuts[k] holds tsvpp_tensor_bytes bytes.  This ConvertRois takes all four resize types, AREA included.
+    int ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                    const tsvpp_tensor_spec *spec, std::string consumerName);
+    int ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                         const tsvpp_tensor_spec *spec, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

@@ -1,6 +1,8 @@
 // vpp_letterbox -- letterboxes a few NV12 frames into canvases of one size through the C++ class (VideoProcessor::ConvertLetterbox) and prints a CRC-32 per canvas
 // (the zlib / IEEE 802.3 one: reflected 0xEDB88320, as Python's zlib.crc32); tests/test_cpp_letterbox_gpu.py compares each with the CRC of the expected canvas.
-//   vpp_letterbox DW DH TYPE FOURCC PLANES NORM PADY PADU PADV  frame.nv12 W H PITCH [frame.nv12 W H PITCH ...]
+//   vpp_letterbox [--dtype f16|bf16|f32] [--mean a,b,c] [--scale a,b,c] DW DH TYPE FOURCC PLANES NORM PADY PADU PADV  frame.nv12 W H PITCH [frame.nv12 W H PITCH ...]
+// --dtype / --mean / --scale: through the ConvertLetterbox overload that takes a tsvpp_tensor_spec (tests/test_cpp_tensor_gpu.py); without them the output is byte
+// for byte what it was.
 // A file holds H rows of PITCH bytes of luma, then H / 2 rows of PITCH bytes of chroma.  Every frame gets the default rectangle (tsvpp_letterbox_rect).  Prints
 // "<index> <crc> <bytes> <left> <top> <width> <height>" per canvas; exit code 0 = converted.
 #include <hip/hip_runtime.h>
@@ -8,9 +10,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "VideoProcessor.h"
+#include "tensor_flags.h"
 
 static uint32_t crc32_zlib(const uint8_t *buf, size_t n) {
     uint32_t c = 0xFFFFFFFFu;
@@ -22,8 +26,10 @@ static uint32_t crc32_zlib(const uint8_t *buf, size_t n) {
 }
 
 int main(int argc, char **argv) {
+    tsvpp_tensor_spec spec;
+    const bool tensor = tensor_flags(argc, argv, spec);
     if (argc < 14 || (argc - 10) % 4 != 0) {
-        fprintf(stderr, "usage: vpp_letterbox DW DH TYPE FOURCC PLANES NORM PADY PADU PADV frame.nv12 W H PITCH [frame.nv12 W H PITCH ...]\n");
+        fprintf(stderr, "usage: vpp_letterbox " TENSOR_FLAGS_USAGE " DW DH TYPE FOURCC PLANES NORM PADY PADU PADV frame.nv12 W H PITCH [frame.nv12 W H PITCH ...]\n");
         return 200;
     }
     const int DW = atoi(argv[1]), DH = atoi(argv[2]), type = atoi(argv[3]);
@@ -62,13 +68,20 @@ int main(int argc, char **argv) {
     ResizeOptions resize(DW, DH);
     resize.type = (ResizeType)type;
     FrameParameters options(resize, color);
-    const size_t bytes = (size_t)(channelsByFourCC((FourCC)fcc) * (float)DW) * (size_t)DH * (norm ? sizeof(float) : 1);
+    size_t bytes = (size_t)(channelsByFourCC((FourCC)fcc) * (float)DW) * (size_t)DH * (norm ? sizeof(float) : 1);
+    if (tensor) {
+        const tsvpp_params flat{ 0, 0, 0, 0, DW, DH, type, fcc, planes, norm };
+        bytes = tsvpp_tensor_bytes(&flat, &spec);
+        if (bytes == 0) return 205; // a (parameters, spec) pair the tensor entry points refuse
+    }
     const size_t stride = (bytes + 255) & ~(size_t)255;
     uint8_t *dOut = nullptr;
     if (hipMalloc(&dOut, stride * (size_t)n) != hipSuccess) return 204;
     std::vector<void *> outs((size_t)n);
     for (int k = 0; k < n; k++) outs[(size_t)k] = dOut + (size_t)k * stride;
-    if (vpp.ConvertLetterbox(inputs.data(), n, nullptr, padY, padU, padV, outs.data(), options, "letterbox") != 0) return 210;
+    const int sts = tensor ? vpp.ConvertLetterbox(inputs.data(), n, nullptr, padY, padU, padV, outs.data(), options, &spec, "letterbox")
+                           : vpp.ConvertLetterbox(inputs.data(), n, nullptr, padY, padU, padV, outs.data(), options, "letterbox");
+    if (sts != 0) return 210;
     if (tsvpp_consumer_synchronize(vpp.context(), "letterbox") != 0) return 211; // the conversion is asynchronous, on the consumer's stream
     std::vector<uint8_t> result(bytes);
     for (int k = 0; k < n; k++) {
@@ -79,7 +92,9 @@ int main(int argc, char **argv) {
     }
     // a rectangle outside the canvas is refused with the reference's status convention, and nothing is launched
     const tsvpp_rect bad{ 0, 0, DW + 2, 2 };
-    if (vpp.ConvertLetterbox(inputs.data(), 1, &bad, padY, padU, padV, outs.data(), options, "letterbox") != VREADER_ERROR) return 214;
+    const int refused = tensor ? vpp.ConvertLetterbox(inputs.data(), 1, &bad, padY, padU, padV, outs.data(), options, &spec, "letterbox")
+                               : vpp.ConvertLetterbox(inputs.data(), 1, &bad, padY, padU, padV, outs.data(), options, "letterbox");
+    if (refused != VREADER_ERROR) return 214;
     for (AVFrame *f : inputs) av_frame_free(&f);
     vpp.Close();
     (void)hipFree(dOut);

@@ -5,6 +5,7 @@
 //   tsvpp_table.cpp  persistent frame tables
 //   tsvpp_rois.cpp   regions of interest (both entry points: NEAREST / BILINEAR / BICUBIC and AREA)
 //   tsvpp_letterbox.cpp  aspect-preserving resize into a padded canvas
+// (the tensor entry points -- fp16 / bf16 / fp32 with mean and scale -- live with the path they extend: tsvpp_rois.cpp, tsvpp_letterbox.cpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -240,6 +241,21 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
 // (tsvpp_convert_letterbox / tsvpp_describe_letterbox; RoiPlan: the canvas is its dst_w x dst_h).  letterbox_rect_of: frame k's rectangle, the caller's or the default
 int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);
 tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int k, int dst_w, int dst_h);
+// (the tensor entry points of both paths) the status of a (params, spec) pair whose plan was accepted: rules 2 and 3 of include/tsvpp.h, in that order
+int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec);
+inline size_t tensor_elem_bytes(int dtype) { return dtype == TSVPP_F32 ? 4 : 2; }
+// every output aligned to its element
+inline bool outs_aligned_to(void *const *outs, int n, size_t elem) {
+    for (int i = 0; i < n; i++)
+        if ((uintptr_t)outs[i] % elem) return false;
+    return true;
+}
+// out= of the tensor describe calls: `luma_only` for Y800
+inline const char *tensor_out_name(int dtype, bool luma_only) {
+    if (dtype == TSVPP_F16) return luma_only ? "f16_y800" : "f16_planar";
+    if (dtype == TSVPP_BF16) return luma_only ? "bf16_y800" : "bf16_planar";
+    return luma_only ? "f32n_y800" : "f32n_planar";
+}
 // tsvpp_area.cpp: the AREA down-scale fields of a descriptor (nothing for any other mode), out of the context's tables or -- a dry run -- with stand-in pointers
 int area_desc(tsvpp_ctx *ctx, const Plan &pl, hipStream_t stream, LaunchDesc &d);
 int area_desc(const Knobs &kn, const Plan &pl, LaunchDesc &d);

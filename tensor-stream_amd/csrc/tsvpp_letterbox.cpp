@@ -1,5 +1,6 @@
-// tsvpp_letterbox.cpp -- aspect-preserving resize into a padded canvas (include/tsvpp.h): tsvpp_letterbox_rect, tsvpp_convert_letterbox, tsvpp_describe_letterbox;
-// TSVPP_MAX_LETTERBOX frames per launch, kernel vpp_letterbox.hip.  The request rules are letterbox_plan's (tsvpp_plan.cpp).
+// tsvpp_letterbox.cpp -- aspect-preserving resize into a padded canvas (include/tsvpp.h): tsvpp_letterbox_rect, tsvpp_convert_letterbox, tsvpp_describe_letterbox and
+// their tensor forms (tsvpp_convert_letterbox_tensor / tsvpp_describe_letterbox_tensor: `spec`, null for the first pair; kernel vpp_letterbox_tensor.hip);
+// TSVPP_MAX_LETTERBOX frames per launch, kernel vpp_letterbox.hip.  The request rules are letterbox_plan's (tsvpp_plan.cpp), the spec's tensor_spec_status's.
 #include <algorithm>
 #include <cstdio>
 
@@ -14,7 +15,8 @@ static bool narrow_tail(const RoiPlan &pl) { return (pl.dst_w & 3) != 0 && pl.ds
 // One launch group: frames [base, base + cnt) as an LbLaunch.  `in` may carry null planes (the describe call).  Returns how many of the group's frames stage EVERY
 // tile in LDS; L.lds_bytes = the dynamic LDS the launch needs for them (0: the gather kernel).
 static int letterbox_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, int base,
-                          int cnt, bool vec, LbLaunch &L) {
+                          int cnt, bool vec, const tsvpp_tensor_spec *spec, LbLaunch &L) {
+    L.spec = spec ? *spec : tsvpp_tensor_spec{};
     L.dst_w = pl.dst_w;
     L.dst_h = pl.dst_h;
     L.swap_rb = pl.swap_rb;
@@ -85,9 +87,75 @@ static int letterbox_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *
     return staged;
 }
 
-static hipError_t launch_group(const RoiPlan &pl, bool vec, bool staged, const LbLaunch &L, hipStream_t stream, char *name, size_t name_len, bool dry_run) {
+static hipError_t launch_group(const RoiPlan &pl, bool vec, bool staged, bool tensor, const LbLaunch &L, hipStream_t stream, char *name, size_t name_len,
+                               bool dry_run) {
     const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n_frames);
+    if (tensor) return launch_letterbox_tensor(pl.mode, pl.out, vec, staged, L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
     return launch_letterbox(pl.mode, pl.out, vec, staged, L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
+}
+
+// `tensor`: tsvpp_convert_letterbox_tensor (then `spec` is checked behind the plan, and may be null: that is its TSVPP_ERROR)
+static int convert_letterbox(bool tensor, tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec, const tsvpp_rect *rects,
+                             int pad_y, int pad_u, int pad_v, void *const *outs, void *stream) {
+    clear_last_launch();
+    RoiPlan pl;
+    int sts = letterbox_plan(p, n, in, rects, pad_y, pad_u, pad_v, pl); // the request first: the same status the describe call answers, context or not
+    if (sts == TSVPP_OK && tensor) sts = tensor_spec_status(p, spec);
+    if (sts != TSVPP_OK) return sts;
+    if (!ctx || !outs) return TSVPP_ERROR;
+    for (int f = 0; f < n; f++)
+        if (!in[f].y || !in[f].uv || !outs[f]) return TSVPP_ERROR;
+    if (tensor && !outs_aligned_to(outs, n, tensor_elem_bytes(spec->dtype))) return TSVPP_ERROR;
+    DeviceGuard guard(ctx);
+    if (guard.status != TSVPP_OK) return guard.status;
+    char label[96] = "";
+    const bool markers = ctx->markers != 0;
+    if (markers)
+        std::snprintf(label, sizeof(label), "tsvpp_convert_letterbox%s n=%d ->%dx%d mode=%d fourcc=%d stream=%p", tensor ? "_tensor" : "", n, pl.dst_w, pl.dst_h, (int)pl.mode, p->fourcc, stream);
+    RangeGuard range(markers, label);
+    for (int base = 0; base < n; base += TSVPP_MAX_LETTERBOX) {
+        const int cnt = std::min(n - base, (int)TSVPP_MAX_LETTERBOX);
+        const bool vec = outs_aligned16(outs + base, cnt) && !narrow_tail(pl); // per launch group, as tsvpp_convert_batch
+        LbLaunch L;
+        const int staged = letterbox_fill(ctx->knobs, pl, in, rects, pad_y, pad_u, pad_v, outs, base, cnt, vec, tensor ? spec : nullptr, L);
+        const hipError_t e = launch_group(pl, vec, staged > 0, tensor, L, (hipStream_t)stream, nullptr, 0, false);
+        if (e != hipSuccess) return (int)e;
+    }
+    return TSVPP_OK;
+}
+
+static int describe_letterbox(bool tensor, const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
+                              int aligned_outputs, char *buf, size_t buf_len) {
+    if (!buf || buf_len == 0) return TSVPP_ERROR;
+    buf[0] = 0;
+    RoiPlan pl;
+    int sts = letterbox_plan(p, n, in, rects, 0, 0, 0, pl); // (the pad is no part of what is launched)
+    if (sts == TSVPP_OK && tensor) sts = tensor_spec_status(p, spec);
+    if (sts != TSVPP_OK) return sts;
+    Knobs kn; // no context: no device, no streams
+    read_env_knobs(kn);
+    std::vector<tsvpp_nv12> fr(in, in + n); // the geometry only: plane pointers are not read
+    for (tsvpp_nv12 &f : fr) f.y = f.uv = nullptr;
+    const bool vec = aligned_outputs != 0 && !narrow_tail(pl);
+    int staged = 0, lds0 = 0, grid0 = 0, launches = 0;
+    char kname[128] = "(none)";
+    LbLaunch L;
+    for (int base = 0; base < n; base += TSVPP_MAX_LETTERBOX, launches++) {
+        const int cnt = std::min(n - base, (int)TSVPP_MAX_LETTERBOX);
+        const int s = letterbox_fill(kn, pl, fr.data(), rects, 0, 0, 0, nullptr, base, cnt, vec, tensor ? spec : nullptr, L);
+        staged += s;
+        if (base == 0) {
+            lds0 = L.lds_bytes;
+            grid0 = L.tiles_x * L.tiles_y * cnt;
+            const hipError_t e = launch_group(pl, vec, s > 0, tensor, L, nullptr, kname, sizeof(kname), true);
+            if (e != hipSuccess) return (int)e;
+        }
+    }
+    const tsvpp_rect r0 = letterbox_rect_of(in, rects, 0, pl.dst_w, pl.dst_h);
+    std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d frames=%d launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d staged=%d tail=%d nt=%d limit=%d inner=%dx%d+%d+%d",
+                  mode_names[pl.mode], tensor ? tensor_out_name(spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w, pl.dst_h, n, launches, kname, ROI_TX, ROI_TY, lds0 + roi_static_lds(pl.out, vec), grid0, L.tiles_x,
+                  L.tiles_y, staged, L.last_col0 > 0 ? 2 : 0, L.nt_stores, (int)TSVPP_MAX_LETTERBOX, r0.width, r0.height, r0.left, r0.top);
+    return TSVPP_OK;
 }
 
 extern "C" {
@@ -113,61 +181,21 @@ int tsvpp_letterbox_rect(int in_w, int in_h, int dst_w, int dst_h, tsvpp_rect *o
 
 int tsvpp_convert_letterbox(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v,
                             void *const *outs, void *stream) {
-    clear_last_launch();
-    RoiPlan pl;
-    const int sts = letterbox_plan(p, n, in, rects, pad_y, pad_u, pad_v, pl); // the request first: the same status the describe call answers, context or not
-    if (sts != TSVPP_OK) return sts;
-    if (!ctx || !outs) return TSVPP_ERROR;
-    for (int f = 0; f < n; f++)
-        if (!in[f].y || !in[f].uv || !outs[f]) return TSVPP_ERROR;
-    DeviceGuard guard(ctx);
-    if (guard.status != TSVPP_OK) return guard.status;
-    char label[96] = "";
-    const bool markers = ctx->markers != 0;
-    if (markers)
-        std::snprintf(label, sizeof(label), "tsvpp_convert_letterbox n=%d ->%dx%d mode=%d fourcc=%d stream=%p", n, pl.dst_w, pl.dst_h, (int)pl.mode, p->fourcc, stream);
-    RangeGuard range(markers, label);
-    for (int base = 0; base < n; base += TSVPP_MAX_LETTERBOX) {
-        const int cnt = std::min(n - base, (int)TSVPP_MAX_LETTERBOX);
-        const bool vec = outs_aligned16(outs + base, cnt) && !narrow_tail(pl); // per launch group, as tsvpp_convert_batch
-        LbLaunch L;
-        const int staged = letterbox_fill(ctx->knobs, pl, in, rects, pad_y, pad_u, pad_v, outs, base, cnt, vec, L);
-        const hipError_t e = launch_group(pl, vec, staged > 0, L, (hipStream_t)stream, nullptr, 0, false);
-        if (e != hipSuccess) return (int)e;
-    }
-    return TSVPP_OK;
+    return convert_letterbox(false, ctx, n, in, p, nullptr, rects, pad_y, pad_u, pad_v, outs, stream);
 }
 
 int tsvpp_describe_letterbox(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int aligned_outputs, char *buf, size_t buf_len) {
-    if (!buf || buf_len == 0) return TSVPP_ERROR;
-    buf[0] = 0;
-    RoiPlan pl;
-    const int sts = letterbox_plan(p, n, in, rects, 0, 0, 0, pl); // (the pad is no part of what is launched)
-    if (sts != TSVPP_OK) return sts;
-    Knobs kn; // no context: no device, no streams
-    read_env_knobs(kn);
-    std::vector<tsvpp_nv12> fr(in, in + n); // the geometry only: plane pointers are not read
-    for (tsvpp_nv12 &f : fr) f.y = f.uv = nullptr;
-    const bool vec = aligned_outputs != 0 && !narrow_tail(pl);
-    int staged = 0, lds0 = 0, grid0 = 0, launches = 0;
-    char kname[128] = "(none)";
-    LbLaunch L;
-    for (int base = 0; base < n; base += TSVPP_MAX_LETTERBOX, launches++) {
-        const int cnt = std::min(n - base, (int)TSVPP_MAX_LETTERBOX);
-        const int s = letterbox_fill(kn, pl, fr.data(), rects, 0, 0, 0, nullptr, base, cnt, vec, L);
-        staged += s;
-        if (base == 0) {
-            lds0 = L.lds_bytes;
-            grid0 = L.tiles_x * L.tiles_y * cnt;
-            const hipError_t e = launch_group(pl, vec, s > 0, L, nullptr, kname, sizeof(kname), true);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-    const tsvpp_rect r0 = letterbox_rect_of(in, rects, 0, pl.dst_w, pl.dst_h);
-    std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d frames=%d launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d staged=%d tail=%d nt=%d limit=%d inner=%dx%d+%d+%d",
-                  mode_names[pl.mode], out_names[pl.out], pl.dst_w, pl.dst_h, n, launches, kname, ROI_TX, ROI_TY, lds0 + roi_static_lds(pl.out, vec), grid0, L.tiles_x,
-                  L.tiles_y, staged, L.last_col0 > 0 ? 2 : 0, L.nt_stores, (int)TSVPP_MAX_LETTERBOX, r0.width, r0.height, r0.left, r0.top);
-    return TSVPP_OK;
+    return describe_letterbox(false, p, nullptr, n, in, rects, aligned_outputs, buf, buf_len);
+}
+
+int tsvpp_convert_letterbox_tensor(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec, const tsvpp_rect *rects,
+                                   int pad_y, int pad_u, int pad_v, void *const *outs, void *stream) {
+    return convert_letterbox(true, ctx, n, in, p, spec, rects, pad_y, pad_u, pad_v, outs, stream);
+}
+
+int tsvpp_describe_letterbox_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
+                                    int aligned_outputs, char *buf, size_t buf_len) {
+    return describe_letterbox(true, p, spec, n, in, rects, aligned_outputs, buf, buf_len);
 }
 
 } // extern "C"

@@ -284,9 +284,30 @@ int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsv
     return TSVPP_OK;
 }
 
+// One spec check for both tensor paths.  The caller has the plan's status already (it wins); what is left is about the spec and about what the tensor stores cover.
+int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec) {
+    if (!p || !spec) return TSVPP_ERROR;
+    const int used = p->fourcc == TSVPP_Y800 ? 1 : 3; // channels the format reads mean / scale of (a fourcc outside the list: all three, then rule 3)
+    for (int c = 0; c < used; c++)
+        if (!std::isfinite(spec->mean[c]) || !std::isfinite(spec->scale[c]) || spec->scale[c] == 0.0f) return TSVPP_ERROR;
+    if (spec->dtype != TSVPP_F32 && spec->dtype != TSVPP_F16 && spec->dtype != TSVPP_BF16) return TSVPP_UNSUPPORTED;
+    if (p->normalization == 0) return TSVPP_UNSUPPORTED; // the contract is stated on q = k / 255
+    if (p->fourcc == TSVPP_Y800) return TSVPP_OK;
+    if (p->fourcc != TSVPP_RGB24 && p->fourcc != TSVPP_BGR24) return TSVPP_UNSUPPORTED;
+    return p->planes == TSVPP_PLANAR ? TSVPP_OK : TSVPP_UNSUPPORTED; // merged half-precision output: out of scope
+}
+
 } // namespace tsvpp
 
 extern "C" {
+
+size_t tsvpp_tensor_bytes(const tsvpp_params *p, const tsvpp_tensor_spec *spec) {
+    if (tensor_spec_status(p, spec) != TSVPP_OK) return 0;
+    if (p->dst_width <= 0 || p->dst_height <= 0 || ((p->dst_width | p->dst_height) & 1)) return 0;
+    const size_t elems = (size_t)(p->fourcc == TSVPP_Y800 ? 1 : 3) * (size_t)p->dst_width * (size_t)p->dst_height;
+    if (elems * sizeof(float) >= ((size_t)1 << 32)) return 0; // the plans' limit, which is stated on fp32
+    return elems * tensor_elem_bytes(spec->dtype);
+}
 
 float tsvpp_channels(int fourcc) {
     if (fourcc == TSVPP_Y800) return 1.0f;

@@ -1,6 +1,8 @@
-// tsvpp_rois.cpp -- regions of interest (include/tsvpp.h): many boxes of a few frames to one size, TSVPP_MAX_ROIS per launch.  Two pairs of entry points over one
-// body: tsvpp_convert_rois / tsvpp_describe_rois (NEAREST, BILINEAR, BICUBIC; kernel vpp_rois.hip) and tsvpp_convert_rois_area / tsvpp_describe_rois_area (AREA;
-// kernel vpp_rois_area.hip).  What differs is which resize types rois_plan lets through (`area`), the mode of a box (AREA: per box) and the launcher.
+// tsvpp_rois.cpp -- regions of interest (include/tsvpp.h): many boxes of a few frames to one size, TSVPP_MAX_ROIS per launch.  Three pairs of entry points over one
+// body: tsvpp_convert_rois / tsvpp_describe_rois (NEAREST, BILINEAR, BICUBIC; kernel vpp_rois.hip), tsvpp_convert_rois_area / tsvpp_describe_rois_area (AREA;
+// kernel vpp_rois_area.hip) and tsvpp_convert_rois_tensor / tsvpp_describe_rois_tensor (all four; the tensor instantiations of both kernels, vpp_rois_tensor.hip /
+// vpp_rois_area_tensor.hip).  What differs is which resize types rois_plan lets through (`area`), the mode of a box (AREA: per box), and -- `spec`, null for the
+// first two pairs -- the launcher, the element size and the spec check behind the plan.
 #include <algorithm>
 #include <cstdio>
 
@@ -17,7 +19,9 @@ static int launch_limit(const RoiPlan &pl) { return is_area(pl) ? (int)TSVPP_MAX
 // One launch group: boxes [base, base + cnt) as a RoiLaunch.  `frames` may carry null planes (the describe calls): then the records hold the bare crop offsets.
 // Returns how many of the group's boxes stage EVERY tile in LDS; L.lds_bytes = the dynamic LDS the launch needs for them (0: the gather kernel), L.area_lds = the
 // bytes of the AREA kernel's weight rows in front of it (the largest tap counts among the group's down-scale boxes; they count against the LDS budget).
-static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frames, const tsvpp_roi *rois, void *const *outs, int base, int cnt, bool vec, RoiLaunch &L) {
+static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frames, const tsvpp_roi *rois, void *const *outs, int base, int cnt, bool vec,
+                     const tsvpp_tensor_spec *spec, RoiLaunch &L) {
+    L.spec = spec ? *spec : tsvpp_tensor_spec{};
     L.dst_w = pl.dst_w;
     L.dst_h = pl.dst_h;
     L.swap_rb = pl.swap_rb;
@@ -26,7 +30,8 @@ static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frame
     L.tiles_x = (pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W;
     L.tiles_y = (pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H;
     L.n_rois = cnt;
-    // store policy as launch_fused's for a resize kernel: non-temporal, except the element-wise merged fp32 stores (partial lines: L2 combines them)
+    // store policy as launch_fused's for a resize kernel: non-temporal, except the element-wise merged fp32 stores (partial lines: L2 combines them).  The tensor
+    // stores take the fp32 planar choice (profiles/tensor_ab.txt)
     L.nt_stores = kn.nt_stores >= 0 ? kn.nt_stores : ((!vec && pl.out == O_F32_MERGED) ? 0 : 1);
     // outputs 4 k + 2 columns wide: the last tile column is shifted to the right edge so that every thread tile has its four columns (tile_col0, vpp_device.h)
     L.last_col0 = (vec && (pl.dst_w & 3) != 0 && pl.dst_w >= ROI_TILE_W) ? pl.dst_w - ROI_TILE_W : 0;
@@ -80,29 +85,37 @@ static int rois_fill(const Knobs &kn, const RoiPlan &pl, const tsvpp_nv12 *frame
 }
 
 // (vpp_rois.hip / vpp_rois_area.hip) one launch group, or only its kernel's name
-static hipError_t launch_group(const RoiPlan &pl, bool vec, bool staged, const RoiLaunch &L, hipStream_t stream, char *name, size_t name_len, bool dry_run) {
+static hipError_t launch_group(const RoiPlan &pl, bool vec, bool staged, bool tensor, const RoiLaunch &L, hipStream_t stream, char *name, size_t name_len,
+                               bool dry_run) {
     const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n_rois);
+    if (tensor) {
+        if (is_area(pl)) return launch_rois_area_tensor(pl.out, vec, staged, L, grid, (size_t)(L.area_lds + L.lds_bytes), stream, name, name_len, dry_run);
+        return launch_rois_tensor(pl.mode, pl.out, vec, staged, L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
+    }
     if (is_area(pl)) return launch_rois_area(pl.out, vec, staged, L, grid, (size_t)(L.area_lds + L.lds_bytes), stream, name, name_len, dry_run);
     return launch_rois(pl.mode, pl.out, vec, staged, L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
 }
 
-static int convert_rois(bool area, tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
-                        void *stream) {
+// `tensor`: tsvpp_convert_rois_tensor (then `spec` is checked behind the plan, and may be null: that is its TSVPP_ERROR)
+static int convert_rois(bool area, bool tensor, tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
+                        const tsvpp_tensor_spec *spec, void *const *outs, void *stream) {
     clear_last_launch();
     RoiPlan pl;
     int sts = rois_plan(p, n_frames, frames, n_rois, rois, pl, area); // the request first: the same status the describe call answers, context or not
+    if (sts == TSVPP_OK && tensor) sts = tensor_spec_status(p, spec);
     if (sts != TSVPP_OK) return sts;
     if (!ctx || !outs) return TSVPP_ERROR;
     for (int f = 0; f < n_frames; f++)
         if (!frames[f].y || !frames[f].uv) return TSVPP_ERROR;
     for (int i = 0; i < n_rois; i++)
         if (!outs[i]) return TSVPP_ERROR;
+    if (tensor && !outs_aligned_to(outs, n_rois, tensor_elem_bytes(spec->dtype))) return TSVPP_ERROR;
     DeviceGuard guard(ctx);
     if (guard.status != TSVPP_OK) return guard.status;
     char label[96] = "";
     const bool markers = ctx->markers != 0;
     if (markers)
-        std::snprintf(label, sizeof(label), "tsvpp_convert_rois%s n=%d frames=%d ->%dx%d mode=%d fourcc=%d stream=%p", area ? "_area" : "", n_rois, n_frames, pl.dst_w,
+        std::snprintf(label, sizeof(label), "tsvpp_convert_rois%s n=%d frames=%d ->%dx%d mode=%d fourcc=%d stream=%p", tensor ? "_tensor" : (area ? "_area" : ""), n_rois, n_frames, pl.dst_w,
                       pl.dst_h, (int)pl.mode, p->fourcc, stream);
     RangeGuard range(markers, label);
     const int limit = launch_limit(pl);
@@ -110,19 +123,20 @@ static int convert_rois(bool area, tsvpp_ctx *ctx, int n_frames, const tsvpp_nv1
         const int cnt = std::min(n_rois - base, limit);
         const bool vec = outs_aligned16(outs + base, cnt) && !narrow_tail(pl); // per launch group, as tsvpp_convert_batch
         RoiLaunch L;
-        const int staged = rois_fill(ctx->knobs, pl, frames, rois, outs, base, cnt, vec, L);
-        const hipError_t e = launch_group(pl, vec, staged > 0, L, (hipStream_t)stream, nullptr, 0, false);
+        const int staged = rois_fill(ctx->knobs, pl, frames, rois, outs, base, cnt, vec, tensor ? spec : nullptr, L);
+        const hipError_t e = launch_group(pl, vec, staged > 0, tensor, L, (hipStream_t)stream, nullptr, 0, false);
         if (e != hipSuccess) return (int)e;
     }
     return TSVPP_OK;
 }
 
-static int describe_rois(bool area, const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
-                         size_t buf_len) {
+static int describe_rois(bool area, bool tensor, const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_rois,
+                         const tsvpp_roi *rois, int aligned_outputs, char *buf, size_t buf_len) {
     if (!buf || buf_len == 0) return TSVPP_ERROR;
     buf[0] = 0;
     RoiPlan pl;
-    const int sts = rois_plan(p, n_frames, frames, n_rois, rois, pl, area);
+    int sts = rois_plan(p, n_frames, frames, n_rois, rois, pl, area);
+    if (sts == TSVPP_OK && tensor) sts = tensor_spec_status(p, spec);
     if (sts != TSVPP_OK) return sts;
     Knobs kn; // no context: no device, no streams
     read_env_knobs(kn);
@@ -135,17 +149,17 @@ static int describe_rois(bool area, const tsvpp_params *p, int n_frames, const t
     const int limit = launch_limit(pl);
     for (int base = 0; base < n_rois; base += limit, launches++) {
         const int cnt = std::min(n_rois - base, limit);
-        const int s = rois_fill(kn, pl, fr.data(), rois, nullptr, base, cnt, vec, L);
+        const int s = rois_fill(kn, pl, fr.data(), rois, nullptr, base, cnt, vec, tensor ? spec : nullptr, L);
         staged += s;
         if (base == 0) {
             lds0 = L.area_lds + L.lds_bytes;
             grid0 = L.tiles_x * L.tiles_y * cnt;
-            const hipError_t e = launch_group(pl, vec, s > 0, L, nullptr, kname, sizeof(kname), true);
+            const hipError_t e = launch_group(pl, vec, s > 0, tensor, L, nullptr, kname, sizeof(kname), true);
             if (e != hipSuccess) return (int)e;
         }
     }
     const int n = std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d rois=%d frames=%d launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d staged=%d tail=%d nt=%d limit=%d",
-                                area ? "area" : mode_names[pl.mode], out_names[pl.out], pl.dst_w, pl.dst_h, n_rois, n_frames, launches, kname, ROI_TX, ROI_TY,
+                                area ? "area" : mode_names[pl.mode], tensor ? tensor_out_name(spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w, pl.dst_h, n_rois, n_frames, launches, kname, ROI_TX, ROI_TY,
                                 lds0 + roi_static_lds(pl.out, vec), grid0, L.tiles_x, L.tiles_y, staged, L.last_col0 > 0 ? 2 : 0, L.nt_stores, limit);
     if (area && n > 0 && (size_t)n < buf_len) std::snprintf(buf + n, buf_len - (size_t)n, " down=%d taps=%dx%d", pl.down, pl.taps_x, pl.taps_y);
     return TSVPP_OK;
@@ -155,22 +169,33 @@ extern "C" {
 
 int tsvpp_convert_rois(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
                        void *stream) {
-    return convert_rois(false, ctx, n_frames, frames, n_rois, rois, p, outs, stream);
+    return convert_rois(false, false, ctx, n_frames, frames, n_rois, rois, p, nullptr, outs, stream);
 }
 
 int tsvpp_describe_rois(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
                         size_t buf_len) {
-    return describe_rois(false, p, n_frames, frames, n_rois, rois, aligned_outputs, buf, buf_len);
+    return describe_rois(false, false, p, nullptr, n_frames, frames, n_rois, rois, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_convert_rois_area(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p, void *const *outs,
                             void *stream) {
-    return convert_rois(true, ctx, n_frames, frames, n_rois, rois, p, outs, stream);
+    return convert_rois(true, false, ctx, n_frames, frames, n_rois, rois, p, nullptr, outs, stream);
 }
 
 int tsvpp_describe_rois_area(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, int aligned_outputs, char *buf,
                              size_t buf_len) {
-    return describe_rois(true, p, n_frames, frames, n_rois, rois, aligned_outputs, buf, buf_len);
+    return describe_rois(true, false, p, nullptr, n_frames, frames, n_rois, rois, aligned_outputs, buf, buf_len);
+}
+
+// All four resize types behind one name: AREA takes the AREA plan, kernel and launch limit, anything else tsvpp_convert_rois's.
+int tsvpp_convert_rois_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
+                              const tsvpp_tensor_spec *spec, void *const *outs, void *stream) {
+    return convert_rois(p && p->resize_type == TSVPP_AREA, true, ctx, n_frames, frames, n_rois, rois, p, spec, outs, stream);
+}
+
+int tsvpp_describe_rois_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois,
+                               int aligned_outputs, char *buf, size_t buf_len) {
+    return describe_rois(p && p->resize_type == TSVPP_AREA, true, p, spec, n_frames, frames, n_rois, rois, aligned_outputs, buf, buf_len);
 }
 
 // The generator of vpp_rois_area.hip's weight rows (roi_area_step, vpp_rois.h), evaluated on the host: rows of output indices first .. first + n - 1.

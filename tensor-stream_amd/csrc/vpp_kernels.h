@@ -25,6 +25,10 @@ constexpr int MAX_THREADS = 256; // threads of the largest workgroup (every kern
 // dispatch does (src/Resize.cu:435): weighted box if both ratios > 1, else the bilinear variant.
 enum Mode : int { M_NONE = 0, M_NEAREST, M_BILINEAR, M_BICUBIC, M_AREA_DOWN, M_AREA_UP, M_COUNT };
 
+// Output element of a kernel that also has tensor instantiations (vpp_rois*.hip, vpp_letterbox*.hip): EL_LIB is the library's colour back end (color_store_tile:
+// what the OutKind says); EL_F32 / EL_HALF store (q - mean) * scale as fp32 / as fp16 or bf16 (vpp_tensor_store.h; which of the two halves: the launch's dtype).
+enum : int { EL_LIB = 0, EL_F32 = 1, EL_HALF = 2 };
+
 // Per-launch pointer table.  Launches of up to TSVPP_MAX_BATCH frames carry it BY VALUE in the kernarg segment (3 KiB): the kernel reads its frame's three
 // pointers with scalar loads, no device-side descriptor buffer and no host->device copy per batch.  Launches out of a persistent, device-resident table
 // (tsvpp_table, round 5: up to TSVPP_MAX_TABLE_LAUNCH frames per launch) set `ext` instead: the same scalar loads, through the constant address space, off

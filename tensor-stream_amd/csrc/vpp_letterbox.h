@@ -29,6 +29,7 @@ struct LbLaunch {
     int32_t lds_bytes;                     // dynamic LDS of the launch's staged footprints: a tile whose footprint needs more gathers from global memory
     float pad_y, pad_u, pad_v;             // the pad sample, integer-valued (0..255): what the samplers would hand the colour back end
     LbRec r[TSVPP_MAX_LETTERBOX];
+    tsvpp_tensor_spec spec;                // the tensor instantiations' dtype, mean[3], scale[3], once per launch (vpp_tensor_store.h); behind the records, as RoiLaunch's
 };
 static_assert(sizeof(LbLaunch) + 256 <= 4096, "LbLaunch no longer fits the kernarg segment");
 
@@ -60,5 +61,8 @@ __host__ __device__ inline int lb_tile_last(int first, int tile, int dst) { retu
 // (vpp_letterbox.hip) launches -- or, with `dry_run`, only names -- the kernel of (mode, out, vec, staged); `name` receives the name tsvpp_describe_letterbox reports
 hipError_t launch_letterbox(Mode mode, OutKind out, bool vec, bool staged, const LbLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
                             size_t name_len, bool dry_run);
+// (vpp_letterbox_tensor.hip) the same for the tensor instantiations: `out` is O_F32_PLANAR or O_Y800_F32, the element is L.spec.dtype's
+hipError_t launch_letterbox_tensor(Mode mode, OutKind out, bool vec, bool staged, const LbLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
+                                   size_t name_len, bool dry_run);
 
 } // namespace tsvpp

@@ -36,6 +36,8 @@ struct RoiLaunch {
     int32_t lds_bytes;                     // dynamic LDS of the launch's staged footprints: a tile whose footprint needs more gathers from global memory
     int32_t area_lds;                      // vpp_rois_area.hip: bytes of the weight rows in front of the staged footprint (a multiple of 16); 0 in vpp_rois.hip
     RoiRec r[TSVPP_MAX_ROIS];
+    tsvpp_tensor_spec spec;                // the tensor instantiations' dtype, mean[3], scale[3], once per launch (vpp_tensor_store.h); behind the records: every offset the
+                                           // other instantiations read is what it was
 };
 static_assert(sizeof(RoiLaunch) + 256 <= 4096, "RoiLaunch no longer fits the kernarg segment");
 static_assert(TSVPP_MAX_ROIS_AREA <= TSVPP_MAX_ROIS, "the AREA entry point fills the same launch block");
@@ -180,5 +182,14 @@ hipError_t launch_rois(Mode mode, OutKind out, bool vec, bool staged, const RoiL
 // (vpp_rois_area.hip) the same for the AREA kernel; `lds_bytes` = L.area_lds + L.lds_bytes
 hipError_t launch_rois_area(OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name, size_t name_len,
                             bool dry_run);
+// (vpp_rois_tensor.hip / vpp_rois_area_tensor.hip) the same for the tensor instantiations: `out` is O_F32_PLANAR or O_Y800_F32 (three planes or one), the element is
+// L.spec.dtype's
+hipError_t launch_rois_tensor(Mode mode, OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
+                              size_t name_len, bool dry_run);
+hipError_t launch_rois_area_tensor(OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
+                                   size_t name_len, bool dry_run);
+// kernel element (vpp_kernels.h) and its name for a tensor dtype
+inline int tensor_el(int dtype) { return dtype == TSVPP_F32 ? EL_F32 : EL_HALF; }
+inline const char *tensor_el_name(int dtype) { return dtype == TSVPP_F32 ? "EL_F32" : "EL_HALF"; }
 
 } // namespace tsvpp

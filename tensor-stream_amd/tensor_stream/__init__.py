@@ -3,9 +3,9 @@
 Same package name as the reference's (`from tensor_stream import ...`), so user code switches by
 putting `tensor-stream_amd/` on sys.path.
 """
-from .vpp import FourCC, FrameParameters, Planes, ResizeType, VideoProcessor, default_coeffs, describe, describe_rois, describe_rois_area, describe_letterbox, letterbox_rect, output_shape  # noqa: F401
+from .vpp import FourCC, FrameParameters, Planes, ResizeType, VideoProcessor, default_coeffs, describe, describe_rois, describe_rois_area, describe_letterbox, letterbox_rect, output_shape, tensor_spec  # noqa: F401
 
-from ._native import Rect, Roi  # noqa: F401
+from ._native import Rect, Roi, TensorSpec  # noqa: F401
 from .tensor_stream import FrameRate, FrameRing, LogsLevel, LogsType, StatusLevel, TensorStreamConverter  # noqa: F401
 
 __version__ = "0.1.0"

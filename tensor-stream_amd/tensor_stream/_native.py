@@ -12,6 +12,7 @@ TSVPP_MAX_BATCH = 128
 TSVPP_MAX_ROIS = 64  # boxes per launch of tsvpp_convert_rois (their records travel in the kernarg segment)
 TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
 TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
+TSVPP_F32, TSVPP_F16, TSVPP_BF16 = 0, 1, 2  # enum tsvpp_dtype: the element of the tensor entry points
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
 TSVPP_OPT_UNSAFE_COEFFS = 3
@@ -44,6 +45,11 @@ class Rect(ctypes.Structure):
     _fields_ = [("left", ctypes.c_int32), ("top", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
+class TensorSpec(ctypes.Structure):
+    """struct tsvpp_tensor_spec: element type, per-channel mean and scale (= 1 / std) of the tensor entry points."""
+    _fields_ = [("dtype", ctypes.c_int32), ("mean", ctypes.c_float * 3), ("scale", ctypes.c_float * 3)]
+
+
 class Coeffs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in
                 ("y_scale", "v_to_r", "u_to_b", "v_to_g", "u_to_g", "round_bias", "y_offset", "c_offset")]
@@ -55,7 +61,8 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_set_coeffs", "tsvpp_default_coeffs", "tsvpp_area_pattern", "tsvpp_describe", "tsvpp_strerror", "tsvpp_version",
            "tsvpp_table_create", "tsvpp_table_destroy", "tsvpp_table_set", "tsvpp_convert_table", "tsvpp_trim", "tsvpp_set_option", "tsvpp_get_option", "tsvpp_consumer_next_stream", "tsvpp_consumer_synchronize",
            "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables",
-           "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox"]
+           "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox",
+           "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor"]
 
 _lib = None
 
@@ -124,6 +131,17 @@ def lib():
     L.tsvpp_convert_letterbox.restype = i32
     L.tsvpp_describe_letterbox.argtypes = [pp, i32, pn, pc, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_describe_letterbox.restype = i32
+    ps = ctypes.POINTER(TensorSpec)
+    L.tsvpp_tensor_bytes.argtypes = [pp, ps]
+    L.tsvpp_tensor_bytes.restype = ctypes.c_size_t
+    L.tsvpp_convert_rois_tensor.argtypes = [vp, i32, pn, i32, pr, pp, ps, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_rois_tensor.restype = i32
+    L.tsvpp_describe_rois_tensor.argtypes = [pp, ps, i32, pn, i32, pr, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_rois_tensor.restype = i32
+    L.tsvpp_convert_letterbox_tensor.argtypes = [vp, i32, pn, pp, ps, pc, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_letterbox_tensor.restype = i32
+    L.tsvpp_describe_letterbox_tensor.argtypes = [pp, ps, i32, pn, pc, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_letterbox_tensor.restype = i32
     L.tsvpp_debug_area_tables.argtypes = [vp]
     L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

@@ -7,6 +7,7 @@ PyTorch is plumbing here: it owns device memory and the current stream; all comp
 import ctypes
 from enum import Enum
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -60,6 +61,42 @@ class FrameParameters:
         return (f"FrameParameters(width={p.dst_width}, height={p.dst_height}, "
                 f"crop=({p.crop_left},{p.crop_top},{p.crop_right},{p.crop_bottom}), resize_type={p.resize_type}, "
                 f"pixel_format={p.fourcc}, planes_pos={p.planes}, normalization={bool(p.normalization)})")
+
+
+_TENSOR_DTYPES = {torch.float32: N.TSVPP_F32, torch.float16: N.TSVPP_F16, torch.bfloat16: N.TSVPP_BF16}
+
+
+def tensor_spec(dtype=None, mean=None, std=None):
+    """The tsvpp_tensor_spec of the keyword arguments dtype / mean / std that convert_rois, convert_rois_area, convert_letterbox and their describe functions
+    take, or None when all three are None (then those run the entry points they always ran).  dtype: torch.float16 / torch.bfloat16 / torch.float32 (default
+    float32); mean / std: a number for every channel or one per STORED channel (plane 0, 1, 2 after the RGB / BGR choice; Y800 reads the first), defaults 0 and 1.
+    The library multiplies, it never divides: the scale it is given is np.float32(1) / np.float32(std), rounded once, so an element is
+    cvt(dtype, (q - float32(mean)) * scale) with q the fp32 value the call stores without these arguments (k / 255) -- the bits of `(q - mean) * (1 / std)` in
+    float32, which can differ in the last bit from `(q - mean) / std`."""
+    if dtype is None and mean is None and std is None:
+        return None
+    dt = torch.float32 if dtype is None else dtype
+    if dt not in _TENSOR_DTYPES:
+        raise RuntimeError(f"-3: tensor outputs are torch.float16, torch.bfloat16 or torch.float32, not {dt}")
+
+    def three(v, default):
+        if v is None:
+            v = default
+        v = [v] * 3 if isinstance(v, (int, float, np.floating)) else list(v)
+        if len(v) == 1:
+            v = v * 3
+        if len(v) != 3:
+            raise ValueError(f"mean / std hold one value or three, not {len(v)}")
+        return [np.float32(x) for x in v]
+
+    m, sd = three(mean, 0.0), three(std, 1.0)
+    with np.errstate(divide="ignore", over="ignore"):
+        sc = [np.float32(1) / x for x in sd]  # (std = 0 gives an infinite scale: the library answers TSVPP_ERROR)
+    return N.TensorSpec(_TENSOR_DTYPES[dt], (ctypes.c_float * 3)(*m), (ctypes.c_float * 3)(*sc))
+
+
+def _torch_dtype(spec):
+    return {v: k for k, v in _TENSOR_DTYPES.items()}[spec.dtype]
 
 
 def output_shape(p, out_w, out_h):
@@ -153,10 +190,11 @@ class VideoProcessor:
         N.check(self._lib.tsvpp_get_option(self._ctx, int(option), ctypes.byref(v)))
         return v.value
 
-    def _alloc(self, p, in_w, in_h, n=None):
+    def _alloc(self, p, in_w, in_h, n=None, dtype=None):
         ow, oh = self.out_dims(p, in_w, in_h)
         shape = output_shape(p, ow, oh)
-        dtype = torch.float32 if (p.normalization or p.fourcc == FourCC.HSV.value) else torch.uint8
+        if dtype is None:  # (else: the element of a tensor entry point)
+            dtype = torch.float32 if (p.normalization or p.fourcc == FourCC.HSV.value) else torch.uint8
         if n is None:
             return torch.empty(shape, dtype=dtype, device=f"cuda:{self.device}")
         # batch: every frame must start 16-byte aligned or its launch group falls back to the element-wise kernel
@@ -164,7 +202,7 @@ class VideoProcessor:
         numel = 1
         for d in shape:
             numel *= d
-        esz = 4 if dtype == torch.float32 else 1
+        esz = torch.empty((), dtype=dtype).element_size()
         stride = (numel * esz + 15) // 16 * 16 // esz
         flat = torch.empty(n * stride, dtype=dtype, device=f"cuda:{self.device}")
         inner = []
@@ -216,22 +254,25 @@ class VideoProcessor:
         N.check(self._lib.tsvpp_convert_batch(self._ctx, n, frames, ctypes.byref(p), outs, stream))
         return out
 
-    def convert_rois(self, ys, uvs, rois, params, out=None, width=None, height=None):
+    def convert_rois(self, ys, uvs, rois, params, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """The cascade behind a detector (tsvpp_convert_rois): every box of `rois` is cut out of its frame, resized to params' width x height,
         colour-converted and stored to its own output, one launch per 64 boxes.  ys / uvs: the NV12 planes of ONE frame (a pair of 2-D uint8
         tensors: rows x pitch) or lists of them -- the frames may differ in size and pitch; rois: (left, top, right, bottom) boxes of frame 0 or
         (frame, left, top, right, bottom); width / height: the frames' picture size (an int for all frames or one per frame; default: the planes'
         own).  Returns (or fills `out`, indexed out[i]) a tensor of shape (n, ...frame shape) with the padded frame stride of convert_batch
-        (every box starts 16-byte aligned), on torch's current stream.  AREA has its own method, convert_rois_area; this one refuses it."""
-        return self._convert_rois(self._lib.tsvpp_convert_rois, ys, uvs, rois, params, out, width, height)
+        (every box starts 16-byte aligned), on torch's current stream.  AREA has its own method, convert_rois_area; this one refuses it.
+        dtype / mean / std (see tensor_spec): with any of them given the boxes come out as what a network takes -- (x / 255 - mean[c]) * (1 / std[c]) in
+        torch.float16 / bfloat16 / float32, planar RGB24 / BGR24 or Y800 with normalization=True -- through tsvpp_convert_rois_tensor, which accepts AREA too."""
+        return self._convert_rois(self._lib.tsvpp_convert_rois, ys, uvs, rois, params, out, width, height, tensor_spec(dtype, mean, std))
 
-    def convert_rois_area(self, ys, uvs, rois, params, out=None, width=None, height=None):
+    def convert_rois_area(self, ys, uvs, rois, params, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """convert_rois for ResizeType.AREA (tsvpp_convert_rois_area), same arguments and result: every box with both ratios above 1 is averaged with the AREA
         down-scale, any other box takes AREA's up-scale rule; the weight rows are generated inside the kernel, so the call allocates and caches nothing however
-        many distinct box sizes it sees.  Any other resize type is refused."""
-        return self._convert_rois(self._lib.tsvpp_convert_rois_area, ys, uvs, rois, params, out, width, height)
+        many distinct box sizes it sees.  Any other resize type is refused.  dtype / mean / std: as convert_rois (the same tensor entry point, which then
+        takes every resize type)."""
+        return self._convert_rois(self._lib.tsvpp_convert_rois_area, ys, uvs, rois, params, out, width, height, tensor_spec(dtype, mean, std))
 
-    def _convert_rois(self, entry, ys, uvs, rois, params, out, width, height):
+    def _convert_rois(self, entry, ys, uvs, rois, params, out, width, height, spec=None):
         p = params.parameters if isinstance(params, FrameParameters) else params
         ys, uvs, boxes = _normalize_rois(ys, uvs, rois)
         widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
@@ -242,20 +283,26 @@ class VideoProcessor:
         if out is None:
             if p.dst_width <= 0 or p.dst_height <= 0 or (p.dst_width | p.dst_height) & 1:
                 raise RuntimeError("-3: convert_rois needs an even, positive output size (width / height of the parameters)")
-            out = self._alloc(p, p.dst_width, p.dst_height, n)  # (a frame of the output size: no stage changes it)
+            out = self._alloc(p, p.dst_width, p.dst_height, n, None if spec is None else _torch_dtype(spec))  # (a frame of the output size: no stage changes it)
         recs = (N.Roi * n)(*[N.Roi(*b) for b in boxes])
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(entry(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), outs, stream))
+        if spec is None:
+            N.check(entry(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), outs, stream))
+        else:
+            N.check(self._lib.tsvpp_convert_rois_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), outs, stream))
         return out
 
-    def convert_letterbox(self, ys, uvs, params, pad=(114, 128, 128), rects=None, out=None, width=None, height=None):
+    def convert_letterbox(self, ys, uvs, params, pad=(114, 128, 128), rects=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """The frame in front of a detector (tsvpp_convert_letterbox): every frame is resized with its aspect kept into an inner rectangle of ONE canvas of params'
         width x height, the rest of the canvas is `pad`, one launch per 32 frames.  ys / uvs: 3-D uint8 tensors (n, rows, pitch) or lists of 2-D tensors -- the
         frames may differ in size and pitch; pad: (Y, U, V), each 0..255 ((114, 128, 128): gray 114, (16, 128, 128): black); rects: one (left, top, width,
         height) per frame, all even and inside the canvas, or None for letterbox_rect's; width / height: the frames' picture size (an int for all frames or one per
         frame; default: the planes' own).  Returns (out, rects): `out` (filled, or allocated with convert_batch's padded frame stride) has shape (n, ...frame shape),
-        on torch's current stream; `rects` is the list of (left, top, width, height) that was used, to map detections back."""
+        on torch's current stream; `rects` is the list of (left, top, width, height) that was used, to map detections back.
+        dtype / mean / std (see tensor_spec): with any of them given the canvases come out as what a network takes (tsvpp_convert_letterbox_tensor), the pad
+        included: it goes through (x / 255 - mean[c]) * (1 / std[c]) like every sample."""
+        spec = tensor_spec(dtype, mean, std)
         p = params.parameters if isinstance(params, FrameParameters) else params
         n = len(ys)
         if n == 0:
@@ -265,11 +312,15 @@ class VideoProcessor:
         if out is None:
             if p.dst_width <= 0 or p.dst_height <= 0 or (p.dst_width | p.dst_height) & 1:
                 raise RuntimeError("-3: convert_letterbox needs an even, positive canvas size (width / height of the parameters)")
-            out = self._alloc(p, p.dst_width, p.dst_height, n)  # (a frame of the canvas size: no stage changes it)
+            out = self._alloc(p, p.dst_width, p.dst_height, n, None if spec is None else _torch_dtype(spec))  # (a frame of the canvas size: no stage changes it)
         recs = None if rects is None else _rects(rects, n)
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(self._lib.tsvpp_convert_letterbox(self._ctx, n, frames, ctypes.byref(p), recs, int(pad[0]), int(pad[1]), int(pad[2]), outs, stream))
+        if spec is None:
+            N.check(self._lib.tsvpp_convert_letterbox(self._ctx, n, frames, ctypes.byref(p), recs, int(pad[0]), int(pad[1]), int(pad[2]), outs, stream))
+        else:
+            N.check(self._lib.tsvpp_convert_letterbox_tensor(self._ctx, n, frames, ctypes.byref(p), ctypes.byref(spec), recs, int(pad[0]), int(pad[1]), int(pad[2]),
+                                                             outs, stream))
         if recs is None:  # (the request was accepted: sizes are positive, the canvas is even)
             used = [letterbox_rect(frames[i].width, frames[i].height, p.dst_width, p.dst_height) for i in range(n)]
         else:
@@ -410,18 +461,19 @@ def _normalize_rois(ys, uvs, rois):
     return ys, uvs, boxes
 
 
-def describe_rois(params, frames, rois, aligned_outputs=True):
+def describe_rois(params, frames, rois, aligned_outputs=True, dtype=None, mean=None, std=None):
     """What a convert_rois of this request would launch, as a dict (tsvpp_describe_rois: mode, out, rois, launches, kernel, grid, lds, staged, ...) -- host logic
-    only, works without a GPU.  frames: (width, height) or (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list; rois as for convert_rois."""
-    return _describe_rois(N.lib().tsvpp_describe_rois, params, frames, rois, aligned_outputs)
+    only, works without a GPU.  frames: (width, height) or (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list; rois as for convert_rois.
+    dtype / mean / std: as convert_rois (tsvpp_describe_rois_tensor: out= names the element, kernel= the tensor instantiation)."""
+    return _describe_rois(N.lib().tsvpp_describe_rois, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
 
 
-def describe_rois_area(params, frames, rois, aligned_outputs=True):
+def describe_rois_area(params, frames, rois, aligned_outputs=True, dtype=None, mean=None, std=None):
     """describe_rois for convert_rois_area (tsvpp_describe_rois_area): the same keys, then down (boxes on the down-scale path) and taps ("<x>x<y>", the largest)."""
-    return _describe_rois(N.lib().tsvpp_describe_rois_area, params, frames, rois, aligned_outputs)
+    return _describe_rois(N.lib().tsvpp_describe_rois_area, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
 
 
-def _describe_rois(entry, params, frames, rois, aligned_outputs):
+def _describe_rois(entry, params, frames, rois, aligned_outputs, spec=None):
     p = params.parameters if isinstance(params, FrameParameters) else params
     if frames and isinstance(frames[0], int):
         frames = [frames]
@@ -436,7 +488,10 @@ def _describe_rois(entry, params, frames, rois, aligned_outputs):
     fr = (N.NV12 * len(recs))(*recs)
     bx = (N.Roi * max(len(boxes), 1))(*[N.Roi(*b) for b in boxes])
     buf = ctypes.create_string_buffer(512)
-    N.check(entry(ctypes.byref(p), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
+    if spec is None:
+        N.check(entry(ctypes.byref(p), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(N.lib().tsvpp_describe_rois_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 
@@ -454,7 +509,7 @@ def letterbox_rect(in_w, in_h, dst_w, dst_h):
     return (r.left, r.top, r.width, r.height)
 
 
-def describe_letterbox(params, frames, rects=None, aligned_outputs=True):
+def describe_letterbox(params, frames, rects=None, aligned_outputs=True, dtype=None, mean=None, std=None):
     """What a convert_letterbox of this request would launch, as a dict (tsvpp_describe_letterbox: describe_rois's keys, then inner = "WxH+left+top" of the first
     frame) -- host logic only, works without a GPU.  frames: (width, height) or (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list."""
     p = params.parameters if isinstance(params, FrameParameters) else params
@@ -468,7 +523,11 @@ def describe_letterbox(params, frames, rects=None, aligned_outputs=True):
     fr = (N.NV12 * max(len(recs), 1))(*recs)
     rc = None if rects is None else _rects(rects, len(recs))
     buf = ctypes.create_string_buffer(512)
-    N.check(N.lib().tsvpp_describe_letterbox(ctypes.byref(p), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
+    spec = tensor_spec(dtype, mean, std)  # (tsvpp_describe_letterbox_tensor: out= names the element, kernel= the tensor instantiation)
+    if spec is None:
+        N.check(N.lib().tsvpp_describe_letterbox(ctypes.byref(p), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(N.lib().tsvpp_describe_letterbox_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

@@ -4,6 +4,7 @@ tsvpp_convert_batch to 640 x 360 into a temporary, a fill of the canvases, a str
 tsvpp_convert_letterbox -- on one stream, timed with HIP events.
 
     python tools/letterbox_ab.py [--out profiles/letterbox_ab.txt] [--repeats 20] [--iters 30] [--ns 1,8,32]
+    python tools/letterbox_ab.py --dtype f16 [--mean a,b,c] [--std a,b,c]     the tensor legs: tsvpp_convert_letterbox_tensor (see tensor_main; appends to profiles/tensor_ab.txt)
 
 Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the MEDIAN
 block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next n frames of a pool of 96 distinct frames (316 MB) and the next
@@ -72,15 +73,116 @@ def expected(y, uv, rect, rt, fcc, planes, norm):
     return out.ravel().view(np.uint8)
 
 
+def tensor_main(a):
+    """The tensor legs at the first configuration of CONFIGS (1080p at pitch 2048 into 640 x 640 BILINEAR BGR24 planar), same protocol (one stream, frames and
+    canvases rotating through more than 256 MiB, median of the blocks with their spread):
+      (a) one tsvpp_convert_letterbox_tensor call with --dtype / --mean / --std: the fused call
+      (b) one tsvpp_convert_letterbox call (fp32) followed by ((x - mean) * scale).to(dtype) in torch on the same stream: what a caller does without (a)
+      (c) the tsvpp_convert_letterbox call of (b) alone: the yardstick
+    Every leg is parity-checked, bit for bit, against tests/tensor_util.py on the last canvas set it wrote.  bytes per frame: the source planes (1920 x 1080 x 1.5)
+    + the canvases a leg writes (+ for (b): the fp32 canvas read back)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tensor_util as T  # the expected bits of the tensor entry points: only these legs need the tests directory
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    base_y = torch.randint(0, 256, (H, PITCH), dtype=torch.uint8, device=dev, generator=gen)
+    base_uv = torch.randint(0, 256, (H // 2, PITCH), dtype=torch.uint8, device=dev, generator=gen)
+    ys = [base_y + (37 * k) % 256 for k in range(a.frames)]
+    uvs = [base_uv + (37 * k) % 256 for k in range(a.frames)]
+    frames = [N.NV12(ys[k].data_ptr(), uvs[k].data_ptr(), PITCH, PITCH, W, H) for k in range(a.frames)]
+    rect = ts.letterbox_rect(W, H, CW, CH)
+    name, rt, fcc, planes, norm = CONFIGS[0]
+    mean, std = [float(v) for v in a.mean.split(",")], [float(v) for v in a.std.split(",")]
+    tdt = T.TORCH[a.dtype]
+    spec = ts.tensor_spec(dtype=tdt, mean=mean, std=std)
+    t_mean = torch.tensor(list(spec.mean), dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+    t_scale = torch.tensor(list(spec.scale), dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+    p = ts.FrameParameters(width=CW, height=CH, resize_type=rt, pixel_format=fcc, planes_pos=planes, normalization=norm).parameters
+    b32, bel, src = 3 * CW * CH * 4, 3 * CW * CH * T.ESIZE[a.dtype], W * H * 3 // 2
+    moved = {"a": src + bel, "b": src + 2 * b32 + bel, "c": src + b32}
+    lines = ["", f"# tools/letterbox_ab.py --dtype {a.dtype} --mean {a.mean} --std {a.std}: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool "
+             f"{a.frames} x 1080p pitch {PITCH} ({a.frames * PITCH * H * 3 // 2 >> 20} MiB), median of {a.repeats} blocks of {a.iters} iterations, one stream",
+             f"# {name.replace('fp32', a.dtype)}: (a) = 1 x tsvpp_convert_letterbox_tensor   (b) = 1 x tsvpp_convert_letterbox (fp32) + ((x - mean) * scale).to({a.dtype}) in torch   "
+             "(c) = the fp32 call of (b) alone", "# us per call, [min .. max of the blocks]; roofline = moved bytes / time / 8 TB/s",
+             f"{'n':>3} | {'(a) us':>8} {'spread':>17} {'roofline':>8} | {'(b) us':>8} {'spread':>17} {'roofline':>8} | {'(c) us':>8} {'spread':>17} {'roofline':>8} | {'a / c':>6} {'b / a':>6}"]
+    for n in [int(v) for v in a.ns.split(",")]:
+        sets, sets_el = max(2, (300 << 20) // (n * b32) + 1), max(2, (300 << 20) // (n * bel) + 1)
+        pool32 = [vpp._alloc(p, CW, CH, n) for _ in range(sets)]
+        pool_el = [vpp._alloc(p, CW, CH, n, tdt) for _ in range(sets_el)]
+        groups = max(1, a.frames // n)
+        frame_arrs = [(N.NV12 * n)(*[frames[(g * n + i) % a.frames] for i in range(n)]) for g in range(groups)]
+        arr32 = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in pool32]
+        arr_el = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in pool_el]
+        ctx, pref, sref, lb, lb_t = vpp._ctx, ctypes.byref(p), ctypes.byref(spec), L.tsvpp_convert_letterbox, L.tsvpp_convert_letterbox_tensor
+        last_b = [None]
+
+        def leg_a(k):
+            if lb_t(ctx, n, frame_arrs[k % groups], pref, sref, None, PAD[0], PAD[1], PAD[2], arr_el[k % sets_el], raw) != 0:
+                raise RuntimeError("tsvpp_convert_letterbox_tensor failed")
+
+        def leg_c(k):
+            if lb(ctx, n, frame_arrs[k % groups], pref, None, PAD[0], PAD[1], PAD[2], arr32[k % sets], raw) != 0:
+                raise RuntimeError("tsvpp_convert_letterbox failed")
+
+        def leg_b(k):
+            leg_c(k)
+            last_b[0] = ((pool32[k % sets] - t_mean) * t_scale).to(tdt)
+
+        res = {}
+        with torch.cuda.stream(stream):
+            for leg, fn in (("a", leg_a), ("b", leg_b), ("c", leg_c)):
+                for t in pool32 + pool_el:
+                    t.zero_()
+                torch.cuda.synchronize()
+                blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(5, a.iters // 2))
+                res[leg] = blocks
+                got = {"a": pool_el[last % sets_el], "b": last_b[0], "c": pool32[last % sets]}[leg]
+                want_spec, want_dt = ((mean, std), a.dtype) if leg != "c" else (T.IDENTITY, T.F32)
+                for i in range(n):
+                    f = ((last % groups) * n + i) % a.frames
+                    q = expected(ys[f].cpu().numpy(), uvs[f].cpu().numpy(), rect, rt, fcc, planes, norm).view(np.float32)
+                    if not np.array_equal(T.bits(got[i]), T.expected(q, 3, want_spec, want_dt)):
+                        raise SystemExit(f"PARITY FAILURE: leg ({leg}) n={n} canvas {i}")
+        m = {k: statistics.median(v) for k, v in res.items()}
+        sp = lambda v: f"{min(v):8.2f}..{max(v):<7.2f}"
+        lines.append(f"{n:>3} | " + " | ".join(f"{m[k]:8.2f} {sp(res[k])} {n * moved[k] / (m[k] * 1e-6) / HBM:8.4f}" for k in "abc") + f" | {m['a'] / m['c']:6.2f} {m['b'] / m['a']:6.2f}")
+        print(lines[-1], flush=True)
+        if n == max(int(v) for v in a.ns.split(",")):
+            ok = m["a"] - m["c"] <= max(res["c"]) - min(res["c"])
+            tail = f"# expectation at n = {n}: (a) not slower than (c) by more than the spread of (c)'s blocks ({max(res['c']) - min(res['c']):.2f} us): (a) - (c) = {m['a'] - m['c']:+.2f} us: {'met' if ok else 'NOT MET'}"
+        del pool32, pool_el
+        torch.cuda.empty_cache()
+    lines += ["# parity: every leg bit-exact against tests/tensor_util.py (the CPU oracle's fp32 canvas, the float32 affine step, round to nearest even) on the last canvas set of every row", tail]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:  # (appends: tools/rois_ab.py --dtype fills the same file)
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "letterbox_ab.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--ns", default="1,8,32")
     ap.add_argument("--frames", type=int, default=96)
+    ap.add_argument("--dtype", choices=("f32", "f16", "bf16"), default=None, help="the tensor legs (tsvpp_convert_letterbox_tensor); default output profiles/tensor_ab.txt, appended to")
+    ap.add_argument("--mean", default="0.485,0.456,0.406", help="per stored channel (with --dtype)")
+    ap.add_argument("--std", default="0.229,0.224,0.225", help="per stored channel (with --dtype); the library is handed float32(1) / float32(std)")
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "tensor_ab.txt" if a.dtype else "letterbox_ab.txt")
+    if a.dtype:
+        return tensor_main(a)
     O.build()
     L = N.lib()
     vpp = ts.VideoProcessor(device=0)

@@ -4,6 +4,7 @@ before tsvpp_convert_rois) against (b) ONE tsvpp_convert_rois -- on one stream, 
 
     python tools/rois_ab.py [--out profiles/rois_ab.txt] [--repeats 20] [--iters 50] [--ns 1,4,16,32,64]
     python tools/rois_ab.py --area [--out profiles/rois_area_ab.txt]      the AREA leg: tsvpp_convert_rois_area (see area_main)
+    python tools/rois_ab.py --dtype f16 [--mean a,b,c] [--std a,b,c]      the tensor legs: tsvpp_convert_rois_tensor (see tensor_main; appends to profiles/tensor_ab.txt)
 
 Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the
 MEDIAN block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next frame of a pool of 96 distinct 1080p frames
@@ -190,6 +191,103 @@ def area_main(a):
     vpp.Close()
 
 
+def tensor_main(a):
+    """The tensor legs at the first configuration of CONFIGS (seeded 64-512 pixel boxes to 224 x 224 BILINEAR BGR24 planar), same protocol (one stream, frames and
+    outputs rotating through more than 256 MiB, median of the blocks with their spread):
+      (a) one tsvpp_convert_rois_tensor call with --dtype / --mean / --std: the fused call
+      (b) one tsvpp_convert_rois call (fp32) followed by ((x - mean) * scale).to(dtype) in torch on the same stream: what a caller does without (a)
+      (c) the tsvpp_convert_rois call of (b) alone: the yardstick
+    Every leg is parity-checked, bit for bit, against tests/tensor_util.py on the last output set it wrote.  bytes: source taps (1.5 per box pixel) + the outputs
+    a leg writes (+ for (b): the fp32 output read back)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tensor_util as T  # the expected bits of the tensor entry points: only these legs need the tests directory
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    base_y = torch.randint(0, 256, (H, W), dtype=torch.uint8, device=dev, generator=gen)
+    base_uv = torch.randint(0, 256, (H // 2, W), dtype=torch.uint8, device=dev, generator=gen)
+    ys = [base_y + (37 * k) % 256 for k in range(a.frames)]
+    uvs = [base_uv + (37 * k) % 256 for k in range(a.frames)]
+    frames = [N.NV12(ys[k].data_ptr(), uvs[k].data_ptr(), W, W, W, H) for k in range(a.frames)]
+    name, dst, rt, fcc, planes, norm = CONFIGS[0]
+    mean, std = [float(v) for v in a.mean.split(",")], [float(v) for v in a.std.split(",")]
+    tdt = T.TORCH[a.dtype]
+    spec = ts.tensor_spec(dtype=tdt, mean=mean, std=std)
+    t_mean = torch.tensor(list(spec.mean), dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+    t_scale = torch.tensor(list(spec.scale), dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+    p = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=rt, pixel_format=fcc, planes_pos=planes, normalization=norm).parameters
+    b32, bel = 3 * dst[0] * dst[1] * 4, 3 * dst[0] * dst[1] * T.ESIZE[a.dtype]
+    lines = ["", f"# tools/rois_ab.py --dtype {a.dtype} --mean {a.mean} --std {a.std}: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool "
+             f"{a.frames} x 1080p ({a.frames * W * H * 3 // 2 >> 20} MiB), median of {a.repeats} blocks of {a.iters} iterations, one stream",
+             f"# {name.replace('fp32', a.dtype)}: (a) = 1 x tsvpp_convert_rois_tensor   (b) = 1 x tsvpp_convert_rois (fp32) + ((x - mean) * scale).to({a.dtype}) in torch   "
+             "(c) = the fp32 call of (b) alone", "# us per call, [min .. max of the blocks]; roofline = moved bytes / time / 8 TB/s",
+             f"{'n':>3} | {'(a) us':>8} {'spread':>15} {'roofline':>8} | {'(b) us':>8} {'spread':>15} {'roofline':>8} | {'(c) us':>8} {'spread':>15} {'roofline':>8} | {'a / c':>6} {'b / a':>6}"]
+    ok = True
+    for n in [int(v) for v in a.ns.split(",")]:
+        boxes = boxes_for(n, seed=100 + n)
+        sets = max(2, min(64, (300 << 20) // (n * b32) + 1))
+        sets_el = max(2, min(64, (300 << 20) // (n * bel) + 1))
+        pool32 = [vpp._alloc(p, dst[0], dst[1], n) for _ in range(sets)]
+        pool_el = [vpp._alloc(p, dst[0], dst[1], n, tdt) for _ in range(sets_el)]
+        src = sum((b[2] - b[0]) * (b[3] - b[1]) * 3 // 2 for b in boxes)
+        moved = {"a": src + n * bel, "b": src + n * (2 * b32 + bel), "c": src + n * b32}
+        recs = (N.Roi * n)(*[N.Roi(0, *b) for b in boxes])
+        arr32 = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in pool32]
+        arr_el = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in pool_el]
+        frame_arrs = [(N.NV12 * 1)(frames[k]) for k in range(a.frames)]
+        ctx, pref, sref, rois, rois_t = vpp._ctx, ctypes.byref(p), ctypes.byref(spec), L.tsvpp_convert_rois, L.tsvpp_convert_rois_tensor
+        last_b = [None]
+
+        def leg_a(k):
+            if rois_t(ctx, 1, frame_arrs[k % a.frames], n, recs, pref, sref, arr_el[k % sets_el], raw) != 0:
+                raise RuntimeError("tsvpp_convert_rois_tensor failed")
+
+        def leg_c(k):
+            if rois(ctx, 1, frame_arrs[k % a.frames], n, recs, pref, arr32[k % sets], raw) != 0:
+                raise RuntimeError("tsvpp_convert_rois failed")
+
+        def leg_b(k):
+            leg_c(k)
+            last_b[0] = ((pool32[k % sets] - t_mean) * t_scale).to(tdt)
+
+        res = {}
+        with torch.cuda.stream(stream):
+            for leg, fn in (("a", leg_a), ("b", leg_b), ("c", leg_c)):
+                for t in pool32 + pool_el:
+                    t.zero_()
+                torch.cuda.synchronize()
+                blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(10, a.iters // 2))
+                res[leg] = blocks
+                y, uv = ys[last % a.frames].cpu().numpy(), uvs[last % a.frames].cpu().numpy()
+                got = {"a": pool_el[last % sets_el], "b": last_b[0], "c": pool32[last % sets]}[leg]
+                want_spec, want_dt = ((mean, std), a.dtype) if leg != "c" else (T.IDENTITY, T.F32)
+                for i, (l, t, r, b) in enumerate(boxes):
+                    q = O.convert(y[t:b, l:r], uv[t // 2:t // 2 + (b - t) // 2, l:r], dst=dst, resize_type=rt, fourcc=fcc, planes=planes, normalization=norm, nthreads=8)[0]
+                    if not np.array_equal(T.bits(got[i]), T.expected(q, 3, want_spec, want_dt)):
+                        raise SystemExit(f"PARITY FAILURE: leg ({leg}) n={n} box {i} {(l, t, r, b)}")
+        m = {k: statistics.median(v) for k, v in res.items()}
+        sp = lambda v: f"{min(v):7.2f}..{max(v):<6.2f}"
+        lines.append(f"{n:>3} | " + " | ".join(f"{m[k]:8.2f} {sp(res[k])} {moved[k] / (m[k] * 1e-6) / HBM:8.4f}" for k in "abc") + f" | {m['a'] / m['c']:6.2f} {m['b'] / m['a']:6.2f}")
+        print(lines[-1], flush=True)
+        if n == max(int(v) for v in a.ns.split(",")):
+            ok = m["a"] - m["c"] <= max(res["c"]) - min(res["c"])
+            tail = f"# expectation at n = {n}: (a) not slower than (c) by more than the spread of (c)'s blocks ({max(res['c']) - min(res['c']):.2f} us): (a) - (c) = {m['a'] - m['c']:+.2f} us: {'met' if ok else 'NOT MET'}"
+        del pool32, pool_el
+        torch.cuda.empty_cache()
+    lines += ["# parity: every leg bit-exact against tests/tensor_util.py (the CPU oracle's fp32 result, the float32 affine step, round to nearest even) on the last output set of every row", tail]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:  # (appends: tools/letterbox_ab.py --dtype fills the same file)
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--area", action="store_true", help="the AREA leg (tsvpp_convert_rois_area); default output profiles/rois_area_ab.txt")
@@ -198,10 +296,15 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--ns", default="1,4,16,32,64")
     ap.add_argument("--frames", type=int, default=96)
+    ap.add_argument("--dtype", choices=("f32", "f16", "bf16"), default=None, help="the tensor legs (tsvpp_convert_rois_tensor); default output profiles/tensor_ab.txt, appended to")
+    ap.add_argument("--mean", default="0.485,0.456,0.406", help="per stored channel (with --dtype)")
+    ap.add_argument("--std", default="0.229,0.224,0.225", help="per stored channel (with --dtype); the library is handed float32(1) / float32(std)")
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "rois_area_ab.txt" if a.area else "rois_ab.txt")
+        a.out = os.path.join(ROOT, "profiles", "tensor_ab.txt" if a.dtype else ("rois_area_ab.txt" if a.area else "rois_ab.txt"))
+    if a.dtype:
+        return tensor_main(a)
     if a.area:
         return area_main(a)
     O.build()

@@ -3,6 +3,7 @@
 //   tsvpp_area.cpp   AREA weight tables, their device cache, the AREA fields of a launch descriptor
 //   tsvpp_api.cpp    contexts, streams, knobs, the conversion itself and its replay cache, tsvpp_describe
 //   tsvpp_table.cpp  persistent frame tables
+//   tsvpp_tiles.h    what the two files below share (templates): the launch fill, the staging budget, the convert and describe skeletons of the tile paths
 //   tsvpp_rois.cpp   regions of interest (both entry points: NEAREST / BILINEAR / BICUBIC and AREA)
 //   tsvpp_letterbox.cpp  aspect-preserving resize into a padded canvas
 // (the tensor entry points -- fp16 / bf16 / fp32 with mean and scale -- live with the path they extend: tsvpp_rois.cpp, tsvpp_letterbox.cpp)

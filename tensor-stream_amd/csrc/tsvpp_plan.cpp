@@ -119,6 +119,43 @@ bool color_flavour(int fourcc, int planes, bool f32, OutKind &out, int &swap_rb)
     }
 }
 
+// ---- what rois_plan and letterbox_plan share (the caller has tested `p` and `frames` for null) ----
+// TSVPP_ERROR class: parameters and frames that describe no request at all
+int tile_request_error(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames) {
+    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the boxes are the crops / the whole frame goes into the rectangle
+    if (p->dst_width <= 0 || p->dst_height <= 0) return TSVPP_ERROR;
+    for (int f = 0; f < n_frames; f++) {
+        const tsvpp_nv12 &fr = frames[f];
+        if (fr.width <= 0 || fr.height <= 0) return TSVPP_ERROR;
+        if (pitch_or_width(fr.pitch_y, fr.width) < fr.width || pitch_or_width(fr.pitch_uv, fr.width) < fr.width) return TSVPP_ERROR;
+    }
+    return TSVPP_OK;
+}
+// TSVPP_UNSUPPORTED class: sizes NV12 has no answer for
+int tile_request_odd(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames) {
+    if ((p->dst_width | p->dst_height) & 1) return TSVPP_UNSUPPORTED;
+    for (int f = 0; f < n_frames; f++)
+        if ((frames[f].width | frames[f].height) & 1) return TSVPP_UNSUPPORTED;
+    return TSVPP_OK;
+}
+// TSVPP_UNSUPPORTED class: the resize type (`area`: the entry point answers AREA and nothing else), the output flavour and size, the grid of launches of up to
+// `max_items` items
+int tile_output_plan(const tsvpp_params *p, bool area, int max_items, RoiPlan &pl) {
+    if (!resize_mode(p->resize_type, pl.mode) || (pl.mode == M_AREA_DOWN) != area) return TSVPP_UNSUPPORTED;
+    if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
+    const bool f32 = p->normalization != 0;
+    if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV: not yet
+    const int channels = p->fourcc == TSVPP_Y800 ? 1 : 3;
+    pl.dst_w = p->dst_width;
+    pl.dst_h = p->dst_height;
+    pl.out_bytes = (size_t)channels * (size_t)pl.dst_w * (size_t)pl.dst_h * (f32 ? sizeof(float) : 1);
+    if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
+    // one workgroup per output tile and item
+    if ((long)((pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * max_items >= (1L << 31)) return TSVPP_UNSUPPORTED;
+    pl.down = pl.taps_x = pl.taps_y = 0;
+    return TSVPP_OK;
+}
+
 } // namespace
 
 namespace tsvpp {
@@ -192,13 +229,7 @@ int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl) {
 int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl, bool area) {
     // TSVPP_ERROR: arguments that describe no request at all
     if (!p || !frames || !rois || n_frames <= 0 || n_rois <= 0) return TSVPP_ERROR;
-    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the boxes are the crops
-    if (p->dst_width <= 0 || p->dst_height <= 0) return TSVPP_ERROR;
-    for (int f = 0; f < n_frames; f++) {
-        const tsvpp_nv12 &fr = frames[f];
-        if (fr.width <= 0 || fr.height <= 0) return TSVPP_ERROR;
-        if (pitch_or_width(fr.pitch_y, fr.width) < fr.width || pitch_or_width(fr.pitch_uv, fr.width) < fr.width) return TSVPP_ERROR;
-    }
+    if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
     for (int i = 0; i < n_rois; i++) {
         const tsvpp_roi &b = rois[i];
         if (b.frame < 0 || b.frame >= n_frames) return TSVPP_ERROR;
@@ -206,23 +237,11 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
         if (b.left < 0 || b.top < 0 || b.right <= b.left || b.bottom <= b.top || b.right > fr.width || b.bottom > fr.height) return TSVPP_ERROR;
     }
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
-    if ((p->dst_width | p->dst_height) & 1) return TSVPP_UNSUPPORTED;
-    for (int f = 0; f < n_frames; f++)
-        if ((frames[f].width | frames[f].height) & 1) return TSVPP_UNSUPPORTED;
+    if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     for (int i = 0; i < n_rois; i++)
         if (((rois[i].right - rois[i].left) | (rois[i].bottom - rois[i].top)) & 1) return TSVPP_UNSUPPORTED;
     // AREA has an entry point of its own (tsvpp_convert_rois_area: its down-scale generates weight rows per tile), which answers nothing else
-    if (!resize_mode(p->resize_type, pl.mode) || (pl.mode == M_AREA_DOWN) != area) return TSVPP_UNSUPPORTED;
-    if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
-    const bool f32 = p->normalization != 0;
-    if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV: not yet
-    const int channels = p->fourcc == TSVPP_Y800 ? 1 : 3;
-    pl.dst_w = p->dst_width;
-    pl.dst_h = p->dst_height;
-    pl.out_bytes = (size_t)channels * (size_t)pl.dst_w * (size_t)pl.dst_h * (f32 ? sizeof(float) : 1);
-    if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
-    if ((long)((pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * TSVPP_MAX_ROIS >= (1L << 31)) return TSVPP_UNSUPPORTED;
-    pl.down = pl.taps_x = pl.taps_y = 0;
+    if (tile_output_plan(p, area, TSVPP_MAX_ROIS, pl) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     if (area) {
         if (pl.dst_w > ROI_AREA_MAX_DST || pl.dst_h > ROI_AREA_MAX_DST) return TSVPP_UNSUPPORTED;
         for (int i = 0; i < n_rois; i++) {
@@ -249,13 +268,7 @@ tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int 
 int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl) {
     // TSVPP_ERROR: arguments that describe no request at all
     if (!p || !in || n <= 0) return TSVPP_ERROR;
-    for (int f = 0; f < n; f++) {
-        const tsvpp_nv12 &fr = in[f];
-        if (fr.width <= 0 || fr.height <= 0) return TSVPP_ERROR;
-        if (pitch_or_width(fr.pitch_y, fr.width) < fr.width || pitch_or_width(fr.pitch_uv, fr.width) < fr.width) return TSVPP_ERROR;
-    }
-    if (p->dst_width <= 0 || p->dst_height <= 0) return TSVPP_ERROR;
-    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the whole frame goes into the rectangle
+    if (tile_request_error(p, n, in) != TSVPP_OK) return TSVPP_ERROR;
     for (int f = 0; rects && f < n; f++) {
         const tsvpp_rect &r = rects[f];
         if (r.width <= 0 || r.height <= 0 || r.left < 0 || r.top < 0) return TSVPP_ERROR;
@@ -263,25 +276,12 @@ int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsv
     }
     if (pad_y < 0 || pad_y > 255 || pad_u < 0 || pad_u > 255 || pad_v < 0 || pad_v > 255) return TSVPP_ERROR;
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
-    if ((p->dst_width | p->dst_height) & 1) return TSVPP_UNSUPPORTED;
-    for (int f = 0; f < n; f++)
-        if ((in[f].width | in[f].height) & 1) return TSVPP_UNSUPPORTED;
+    if (tile_request_odd(p, n, in) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     for (int f = 0; rects && f < n; f++) // (the default rectangle of an even canvas is even)
         if ((rects[f].left | rects[f].top | rects[f].width | rects[f].height) & 1) return TSVPP_UNSUPPORTED;
-    // AREA: its down-scale needs weight rows (vpp_rois_area.hip generates them per tile); not in this kernel yet
-    if (!resize_mode(p->resize_type, pl.mode) || pl.mode == M_AREA_DOWN) return TSVPP_UNSUPPORTED;
-    if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
-    const bool f32 = p->normalization != 0;
-    if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV
-    const int channels = p->fourcc == TSVPP_Y800 ? 1 : 3;
-    pl.dst_w = p->dst_width;
-    pl.dst_h = p->dst_height;
-    pl.out_bytes = (size_t)channels * (size_t)pl.dst_w * (size_t)pl.dst_h * (f32 ? sizeof(float) : 1);
-    if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
-    // (the rectangle travels in 32-bit fields: a canvas side has no limit of its own.  The grid does: one workgroup per canvas tile and frame)
-    if ((long)((pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * TSVPP_MAX_LETTERBOX >= (1L << 31)) return TSVPP_UNSUPPORTED;
-    pl.down = pl.taps_x = pl.taps_y = 0;
-    return TSVPP_OK;
+    // AREA: its down-scale needs weight rows (vpp_rois_area.hip generates them per tile); not in this kernel yet.  The rectangle travels in 32-bit fields: a canvas
+    // side has no limit of its own, the grid has
+    return tile_output_plan(p, false, TSVPP_MAX_LETTERBOX, pl);
 }
 
 // One spec check for both tensor paths.  The caller has the plan's status already (it wins); what is left is about the spec and about what the tensor stores cover.

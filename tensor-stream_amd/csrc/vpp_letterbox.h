@@ -33,30 +33,7 @@ struct LbLaunch {
 };
 static_assert(sizeof(LbLaunch) + 256 <= 4096, "LbLaunch no longer fits the kernarg segment");
 
-// The part of canvas indices [first, last] of one axis that lies inside the rectangle [origin, origin + size), as indices of the rectangle's own grid:
-// [lo, hi], empty (lo > hi) where the tile does not touch the rectangle.  `first`, `origin` and `size` are even and `last` is odd, so lo is even, hi is odd and
-// the chroma pairs of the part are [lo >> 1, hi >> 1].
-__host__ __device__ inline void lb_inner_range(int first, int last, int origin, int size, int &lo, int &hi) {
-    lo = (first > origin ? first : origin) - origin;
-    hi = (last < origin + size - 1 ? last : origin + size - 1) - origin;
-}
-
-// Source footprint of inner columns [a0, a1] / inner rows [b0, b1] in both planes: roi_span_x / roi_span_y (vpp_rois.h) for a run that need not start at a tile's
-// first index nor be a tile long.  Host and device alike: the host sizes the launch's LDS with exactly the numbers the kernel will compute.
-__host__ __device__ inline void lb_span_x(int mode, int a0, int a1, int src_w, float xr, RoiFootprint &f) {
-    roi_axis_span(mode, a0, a1, xr, src_w, f.xlo, f.xhi);
-    roi_clamp(f.xlo, f.xhi, src_w);
-    roi_axis_span(mode, a0 >> 1, a1 >> 1, xr, src_w, f.cxlo, f.cxhi);
-    roi_clamp(f.cxlo, f.cxhi, src_w >> 1);
-}
-__host__ __device__ inline void lb_span_y(int mode, int b0, int b1, int src_h, float yr, RoiFootprint &f) {
-    roi_axis_span(mode, b0, b1, yr, src_h, f.ylo, f.yhi);
-    roi_clamp(f.ylo, f.yhi, src_h);
-    roi_axis_span(mode, b0 >> 1, b1 >> 1, yr, src_h, f.cylo, f.cyhi);
-    roi_clamp(f.cylo, f.cyhi, src_h >> 1);
-}
-// last canvas column / row of the tile that starts at `first`
-__host__ __device__ inline int lb_tile_last(int first, int tile, int dst) { return (first + tile < dst ? first + tile : dst) - 1; }
+// (the part of a tile inside the rectangle and its source footprint: tile_inner_range, tile_span_x / tile_span_y, vpp_rois.h)
 
 // (vpp_letterbox.hip) launches -- or, with `dry_run`, only names -- the kernel of (mode, out, vec, staged); `name` receives the name tsvpp_describe_letterbox reports
 hipError_t launch_letterbox(Mode mode, OutKind out, bool vec, bool staged, const LbLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,

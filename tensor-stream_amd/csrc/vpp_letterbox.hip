@@ -20,6 +20,7 @@
 // shared samplers.  Written for wave64 / CDNA4 only.
 
 #include "vpp_letterbox_core.h"
+#include "vpp_tile_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -27,45 +28,20 @@ namespace tsvpp {
 
 // (the kernel: vpp_letterbox_core.h, shared with vpp_letterbox_tensor.hip)
 
-namespace {
-
-const char *const kModeNames[M_COUNT] = { "M_NONE", "M_NEAREST", "M_BILINEAR", "M_BICUBIC", "M_AREA_DOWN", "M_AREA_UP" };
-const char *const kOutNames[O_COUNT] = { "O_U8_PLANAR", "O_U8_MERGED", "O_F32_PLANAR", "O_F32_MERGED", "O_NV12_U8", "O_NV12_F32", "O_Y800_U8", "O_Y800_F32", "O_HSV_F32" };
-
-template <int MODE, int OUT, bool VEC, bool STAGED>
-hipError_t launch_k(const LbLaunch &L, unsigned grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((vpp_letterbox_kernel<MODE, OUT, VEC, STAGED>), dim3(grid), dim3(ROI_THREADS), lds, stream, L);
-    return hipGetLastError();
-}
-template <int MODE, int OUT>
-hipError_t launch_mo(bool vec, bool staged, const LbLaunch &L, unsigned grid, size_t lds, hipStream_t stream) {
-    if (vec) return staged ? launch_k<MODE, OUT, true, true>(L, grid, lds, stream) : launch_k<MODE, OUT, true, false>(L, grid, 0, stream);
-    return staged ? launch_k<MODE, OUT, false, true>(L, grid, lds, stream) : launch_k<MODE, OUT, false, false>(L, grid, 0, stream);
-}
-// the flavours this kernel is instantiated for: RGB / BGR planar and merged, Y800
-constexpr bool lb_flavour(int out) { return out == O_U8_PLANAR || out == O_U8_MERGED || out == O_F32_PLANAR || out == O_F32_MERGED || out == O_Y800_U8 || out == O_Y800_F32; }
-template <int MODE>
-hipError_t launch_m(OutKind out, bool vec, bool staged, const LbLaunch &L, unsigned grid, size_t lds, hipStream_t stream) {
-    return with_out_kind(out, [&](auto O) {
-        constexpr int OUT = decltype(O)::value;
-        if constexpr (lb_flavour(OUT)) return launch_mo<MODE, OUT>(vec, staged, L, grid, lds, stream);
-        else return hipErrorNotSupported; // a missing kernel is an error, never a fallback
-    });
-}
-
-} // namespace
-
 hipError_t launch_letterbox(Mode mode, OutKind out, bool vec, bool staged, const LbLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
                             size_t name_len, bool dry_run) {
-    const bool known = (mode == M_NEAREST || mode == M_BILINEAR || mode == M_BICUBIC) && lb_flavour(out);
-    if (!known) return hipErrorNotSupported;
-    if (name && name_len) snprintf(name, name_len, "vpp_letterbox<%s,%s,%s,%s>", kModeNames[mode], kOutNames[out], vec ? "vec" : "elem", staged ? "staged" : "gather");
+    if (!tile_mode(mode) || !tile_flavour(out)) return hipErrorNotSupported;
+    if (name && name_len) snprintf(name, name_len, "vpp_letterbox<%s,%s,%s,%s>", kModeNames[mode], kOutNames[out], vec_name(vec), staged_name(staged));
     if (dry_run) return hipSuccess;
-    switch (mode) {
-    case M_NEAREST: return launch_m<M_NEAREST>(out, vec, staged, L, grid, lds_bytes, stream);
-    case M_BILINEAR: return launch_m<M_BILINEAR>(out, vec, staged, L, grid, lds_bytes, stream);
-    default: return launch_m<M_BICUBIC>(out, vec, staged, L, grid, lds_bytes, stream);
-    }
+    return with_tile_mode(mode, [&](auto M) {
+        return with_tile_flavour(out, [&](auto O) {
+            return with_vec_staged(vec, staged, [&](auto V, auto S) {
+                constexpr bool STAGED = decltype(S)::value; // (the gather kernel takes no dynamic LDS)
+                hipLaunchKernelGGL((vpp_letterbox_kernel<decltype(M)::value, decltype(O)::value, decltype(V)::value, STAGED>), dim3(grid), dim3(ROI_THREADS), STAGED ? lds_bytes : 0, stream, L);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 } // namespace tsvpp

@@ -3,9 +3,8 @@
 // (EL_F32 / EL_HALF: tsvpp_convert_letterbox_tensor, vpp_tensor_store.h).  Nothing but the store call differs between them: the pad sample goes through
 // whichever it is, like every other sample.
 #pragma once
-#include "vpp_device.h"
 #include "vpp_letterbox.h"
-#include "vpp_tensor_store.h"
+#include "vpp_tile_core.h"
 
 #pragma clang fp contract(off)
 
@@ -51,8 +50,7 @@ __device__ __forceinline__ void letterbox_thread_tile(const S &s, const LaunchDe
                 Yf[rr][c] = in[c >> 1] ? (float)v : pad_y;
             }
     }
-    if constexpr (EL == EL_LIB) color_store_tile<OUT, VEC>(Yf, Uf, Vf, d, out, i0, j0, ncol);
-    else tensor_store_tile<OUT, EL, VEC>(Yf, Uf, Vf, d, L.spec, (uint8_t *)out, i0, j0, ncol);
+    store_tile<OUT, VEC, EL>(Yf, Uf, Vf, d, L.spec, out, i0, j0, ncol);
 }
 
 template <int MODE, int OUT, bool VEC, bool STAGED, int EL = EL_LIB>
@@ -60,37 +58,18 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_letterbox_kernel(const LbLaun
     using T = typename OutT<OUT>::type;
     typedef __attribute__((address_space(1))) uint8_t *GP; // the records hold GLOBAL addresses (PtrCol, vpp_kernels.h)
     // workgroup -> (frame, canvas tile): all tiles of a canvas are neighbours in the grid
-    const int tiles = L.tiles_x * L.tiles_y;
-    const int frame = (int)blockIdx.x / tiles;
-    const int rem = (int)blockIdx.x - frame * tiles;
-    const int tyi = rem / L.tiles_x, txi = rem - tyi * L.tiles_x;
+    const TileIndex tix = tile_index(L.tiles_x, L.tiles_y);
+    const int frame = tix.item, tyi = tix.tyi, txi = tix.txi;
     if (frame >= L.n_frames) return;
     const LbRec &r = L.r[frame]; // wave-uniform index: scalar loads
 
     // the samplers and the colour back end read their request from a LaunchDesc: this frame's source and ratios, the CANVAS as the output
     LaunchDesc d = {};
-    d.src_w = r.src_w;
-    d.src_h = r.src_h;
-    d.pitch_y = r.pitch_y;
-    d.pitch_uv = r.pitch_uv;
-    d.dst_w = L.dst_w;
-    d.dst_h = L.dst_h;
-    d.xr = r.xr;
-    d.yr = r.yr;
-    d.swap_rb = L.swap_rb;
-    d.color_g = L.color_g;
-    d.k = L.k;
-    d.tx = ROI_TX;
-    d.ty = ROI_TY;
-    d.tx_shift = ROI_TX_SHIFT;
-    d.rpt = 1;
-    d.nt_stores = L.nt_stores;
-    d.last_col0 = VEC ? L.last_col0 : 0;
-    d.u8_xchg = L.u8_xchg;
-    d.luma_only = kLumaOnly<OUT> ? 1 : 0;
+    tile_desc<OUT, VEC>(L, r, d);
 
     const uint8_t *const plane_y = (const uint8_t *)(GP)(uintptr_t)r.y, *const plane_uv = (const uint8_t *)(GP)(uintptr_t)r.uv;
     T *const out = (T *)(GP)(uintptr_t)r.out;
+    // (the coordinates are written out in all three tile kernels: as a helper of vpp_tile_core.h they moved VGPRs in vpp_rois_kernel and vpp_letterbox_kernel)
     const int lx = threadIdx.x & (ROI_TX - 1), ly = threadIdx.x >> ROI_TX_SHIFT;
     const int j_first = roi_tile_col0(txi, L.dst_w, d.last_col0), i_first = tyi * ROI_TILE_H;
     const int j0 = j_first + lx * PXW, i0 = i_first + ly * PXH;
@@ -98,8 +77,8 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_letterbox_kernel(const LbLaun
 
     // the part of the rectangle this tile covers (wave-uniform)
     LbPart t;
-    lb_inner_range(j_first, lb_tile_last(j_first, ROI_TILE_W, L.dst_w), r.left, r.width, t.a0, t.a1);
-    lb_inner_range(i_first, lb_tile_last(i_first, ROI_TILE_H, L.dst_h), r.top, r.height, t.b0, t.b1);
+    tile_inner_range(j_first, tile_last(j_first, ROI_TILE_W, L.dst_w), r.left, r.width, t.a0, t.a1);
+    tile_inner_range(i_first, tile_last(i_first, ROI_TILE_H, L.dst_h), r.top, r.height, t.b0, t.b1);
     if (t.a0 > t.a1 || t.b0 > t.b1) { // none of it: pad, through the colour back end
         if (!active) return;
         const float Uf[2] = { L.pad_u, L.pad_u }, Vf[2] = { L.pad_v, L.pad_v };
@@ -109,16 +88,16 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_letterbox_kernel(const LbLaun
 #pragma unroll
             for (int c = 0; c < PXW; c++) Yf[rr][c] = L.pad_y;
         const int ncol = VEC ? PXW : min(PXW, L.dst_w - j0);
-        if constexpr (EL == EL_LIB) color_store_tile<OUT, VEC>(Yf, Uf, Vf, d, out, i0, j0, ncol);
-        else tensor_store_tile<OUT, EL, VEC>(Yf, Uf, Vf, d, L.spec, (uint8_t *)out, i0, j0, ncol);
+        store_tile<OUT, VEC, EL>(Yf, Uf, Vf, d, L.spec, out, i0, j0, ncol);
         return;
     }
 
     if constexpr (STAGED) {
         RoiFootprint f;
-        lb_span_x(MODE, t.a0, t.a1, r.src_w, r.xr, f);
-        lb_span_y(MODE, t.b0, t.b1, r.src_h, r.yr, f);
+        tile_span_x(MODE, t.a0, t.a1, r.src_w, r.xr, f);
+        tile_span_y(MODE, t.b0, t.b1, r.src_h, r.yr, f);
         if (roi_stageable(f) && roi_lds_need(f, kLumaOnly<OUT>) <= L.lds_bytes) { // (wave-uniform)
+            // (the staging block is written out in all three tile kernels: as a helper it changed their instructions and measured slower, profiles/tile_core_ab.txt)
             const int span_y = f.xhi - f.xlo + 1, span_uv = 2 * (f.cxhi - f.cxlo + 1);
             const int ny = f.yhi - f.ylo + 1, nuv = kLumaOnly<OUT> ? 0 : f.cyhi - f.cylo + 1;
             d.lds_cpr_y = roi_chunks(span_y);
@@ -140,12 +119,7 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_letterbox_kernel(const LbLaun
     }
     if (!active) return;
     GlobalSrc s;
-    s.y = plane_y;
-    s.uv = plane_uv;
-    s.py = r.pitch_y;
-    s.puv = r.pitch_uv;
-    s.w = r.src_w;
-    s.h = r.src_h;
+    tile_global_src(s, r, plane_y, plane_uv);
     letterbox_thread_tile<MODE, OUT, VEC, EL>(s, d, r, t, L, out, i0, j0);
 }
 

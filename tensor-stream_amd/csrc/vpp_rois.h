@@ -139,19 +139,29 @@ __host__ __device__ inline void roi_clamp(int &lo, int &hi, int limit) {
     hi = hi > limit - 1 ? limit - 1 : hi;
     if (lo > hi) lo = hi; // (never for a valid request)
 }
-__host__ __device__ inline void roi_span_x(int mode, int j_first, int dst_w, int src_w, float xr, RoiFootprint &f) {
-    const int j_last = (j_first + ROI_TILE_W < dst_w ? j_first + ROI_TILE_W : dst_w) - 1;
-    roi_axis_span(mode, j_first, j_last, xr, src_w, f.xlo, f.xhi);
+// last output column / row of the tile that starts at `first`
+__host__ __device__ inline int tile_last(int first, int tile, int dst) { return (first + tile < dst ? first + tile : dst) - 1; }
+// Source footprint of output columns [a0, a1] / rows [b0, b1] of an item in both planes.  The ROI kernels hand in their tile (first .. tile_last), the letterbox
+// kernel the part of its tile inside the rectangle (tile_inner_range), in the rectangle's own indices: a run that need not start at a tile's first index nor be a
+// tile long.  Host and device alike: the host sizes the launch's LDS with exactly the numbers the kernel will compute.
+__host__ __device__ inline void tile_span_x(int mode, int a0, int a1, int src_w, float xr, RoiFootprint &f) {
+    roi_axis_span(mode, a0, a1, xr, src_w, f.xlo, f.xhi);
     roi_clamp(f.xlo, f.xhi, src_w);
-    roi_axis_span(mode, j_first >> 1, j_last >> 1, xr, src_w, f.cxlo, f.cxhi);
+    roi_axis_span(mode, a0 >> 1, a1 >> 1, xr, src_w, f.cxlo, f.cxhi);
     roi_clamp(f.cxlo, f.cxhi, src_w >> 1);
 }
-__host__ __device__ inline void roi_span_y(int mode, int i_first, int dst_h, int src_h, float yr, RoiFootprint &f) {
-    const int i_last = (i_first + ROI_TILE_H < dst_h ? i_first + ROI_TILE_H : dst_h) - 1;
-    roi_axis_span(mode, i_first, i_last, yr, src_h, f.ylo, f.yhi);
+__host__ __device__ inline void tile_span_y(int mode, int b0, int b1, int src_h, float yr, RoiFootprint &f) {
+    roi_axis_span(mode, b0, b1, yr, src_h, f.ylo, f.yhi);
     roi_clamp(f.ylo, f.yhi, src_h);
-    roi_axis_span(mode, i_first >> 1, i_last >> 1, yr, src_h, f.cylo, f.cyhi);
+    roi_axis_span(mode, b0 >> 1, b1 >> 1, yr, src_h, f.cylo, f.cyhi);
     roi_clamp(f.cylo, f.cyhi, src_h >> 1);
+}
+// The part of output indices [first, last] of one axis that lies inside the rectangle [origin, origin + size) (vpp_letterbox.h), as indices of the rectangle's
+// own grid: [lo, hi], empty (lo > hi) where the tile does not touch the rectangle.  `first`, `origin` and `size` are even and `last` is odd, so lo is even, hi is
+// odd and the chroma pairs of the part are [lo >> 1, hi >> 1].
+__host__ __device__ inline void tile_inner_range(int first, int last, int origin, int size, int &lo, int &hi) {
+    lo = (first > origin ? first : origin) - origin;
+    hi = (last < origin + size - 1 ? last : origin + size - 1) - origin;
 }
 // 16-byte chunks of one staged row that holds `span` bytes at any misalignment (0..15) of its first byte
 __host__ __device__ inline int roi_chunks(int span) { return ((span + 14) >> 4) + 1; }
@@ -188,8 +198,5 @@ hipError_t launch_rois_tensor(Mode mode, OutKind out, bool vec, bool staged, con
                               size_t name_len, bool dry_run);
 hipError_t launch_rois_area_tensor(OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
                                    size_t name_len, bool dry_run);
-// kernel element (vpp_kernels.h) and its name for a tensor dtype
-inline int tensor_el(int dtype) { return dtype == TSVPP_F32 ? EL_F32 : EL_HALF; }
-inline const char *tensor_el_name(int dtype) { return dtype == TSVPP_F32 ? "EL_F32" : "EL_HALF"; }
 
 } // namespace tsvpp

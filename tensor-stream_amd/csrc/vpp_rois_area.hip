@@ -29,6 +29,7 @@
 // Arithmetic contract as everywhere: single IEEE-754 operations in the reference's order, contraction off.  Written for wave64 / CDNA4 only.
 
 #include "vpp_rois_area_core.h"
+#include "vpp_tile_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -36,30 +37,16 @@ namespace tsvpp {
 
 // (the kernel: vpp_rois_area_core.h, shared with vpp_rois_area_tensor.hip)
 
-namespace {
-
-const char *const kOutNames[O_COUNT] = { "O_U8_PLANAR", "O_U8_MERGED", "O_F32_PLANAR", "O_F32_MERGED", "O_NV12_U8", "O_NV12_F32", "O_Y800_U8", "O_Y800_F32", "O_HSV_F32" };
-
-template <int OUT, bool VEC, bool STAGED> hipError_t launch_k(const RoiLaunch &L, unsigned grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((vpp_rois_area_kernel<OUT, VEC, STAGED>), dim3(grid), dim3(ROI_THREADS), lds, stream, L);
-    return hipGetLastError();
-}
-// the flavours this kernel is instantiated for: RGB / BGR planar and merged, Y800
-constexpr bool roi_flavour(int out) { return out == O_U8_PLANAR || out == O_U8_MERGED || out == O_F32_PLANAR || out == O_F32_MERGED || out == O_Y800_U8 || out == O_Y800_F32; }
-
-} // namespace
-
 hipError_t launch_rois_area(OutKind out, bool vec, bool staged, const RoiLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name, size_t name_len,
                             bool dry_run) {
-    if (!roi_flavour(out)) return hipErrorNotSupported;
-    if (name && name_len) snprintf(name, name_len, "vpp_rois_area<%s,%s,%s>", kOutNames[out], vec ? "vec" : "elem", staged ? "staged" : "gather");
+    if (!tile_flavour(out)) return hipErrorNotSupported;
+    if (name && name_len) snprintf(name, name_len, "vpp_rois_area<%s,%s,%s>", kOutNames[out], vec_name(vec), staged_name(staged));
     if (dry_run) return hipSuccess;
-    return with_out_kind(out, [&](auto O) {
-        constexpr int OUT = decltype(O)::value;
-        if constexpr (roi_flavour(OUT)) {
-            if (vec) return staged ? launch_k<OUT, true, true>(L, grid, lds_bytes, stream) : launch_k<OUT, true, false>(L, grid, lds_bytes, stream);
-            return staged ? launch_k<OUT, false, true>(L, grid, lds_bytes, stream) : launch_k<OUT, false, false>(L, grid, lds_bytes, stream);
-        } else return hipErrorNotSupported; // a missing kernel is an error, never a fallback
+    return with_tile_flavour(out, [&](auto O) {
+        return with_vec_staged(vec, staged, [&](auto V, auto S) { // (lds_bytes either way: the weight rows need LDS in the gather kernel too)
+            hipLaunchKernelGGL((vpp_rois_area_kernel<decltype(O)::value, decltype(V)::value, decltype(S)::value>), dim3(grid), dim3(ROI_THREADS), lds_bytes, stream, L);
+            return hipGetLastError();
+        });
     });
 }
 

@@ -2,9 +2,7 @@
 // units instantiate: vpp_rois_area.hip with the library's colour back end (EL_LIB: every flavour of tsvpp_convert_rois_area) and vpp_rois_area_tensor.hip with the
 // tensor store (EL_F32 / EL_HALF: tsvpp_convert_rois_tensor with TSVPP_AREA, vpp_tensor_store.h).  Nothing but the store call differs between them.
 #pragma once
-#include "vpp_device.h"
-#include "vpp_rois.h"
-#include "vpp_tensor_store.h"
+#include "vpp_tile_core.h"
 
 #pragma clang fp contract(off)
 
@@ -74,14 +72,14 @@ __device__ __forceinline__ void area_thread_tile(const S &s, const LaunchDesc &d
     for (int r = 0; r < PXH; r++)
 #pragma unroll
         for (int c = 0; c < PXW; c++) Yf[r][c] = (float)area_luma(s, d, w, i0 + r, VEC ? j0 + c : min(j0 + c, jmax));
-    if constexpr (EL == EL_LIB) color_store_tile<OUT, VEC>(Yf, Uf, Vf, d, out, i0, j0, ncol);
-    else tensor_store_tile<OUT, EL, VEC>(Yf, Uf, Vf, d, a, (uint8_t *)out, i0, j0, ncol);
+    store_tile<OUT, VEC, EL>(Yf, Uf, Vf, d, a, out, i0, j0, ncol);
 }
 
 template <int OUT, bool VEC, bool STAGED, int EL = EL_LIB>
 __global__ __launch_bounds__(ROI_THREADS) void vpp_rois_area_kernel(const RoiLaunch L) {
     using T = typename OutT<OUT>::type;
     typedef __attribute__((address_space(1))) uint8_t *GP;
+    // (written out: with tile_index of vpp_tile_core.h 16 of the 24 kernels of vpp_rois_area.hip compile to other instructions)
     const int tiles = L.tiles_x * L.tiles_y;
     const int box = (int)blockIdx.x / tiles;
     const int rem = (int)blockIdx.x - box * tiles;
@@ -90,28 +88,11 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_rois_area_kernel(const RoiLau
     const RoiRec &r = L.r[box]; // wave-uniform index: scalar loads
 
     LaunchDesc d = {};
-    d.src_w = r.src_w;
-    d.src_h = r.src_h;
-    d.pitch_y = r.pitch_y;
-    d.pitch_uv = r.pitch_uv;
-    d.dst_w = L.dst_w;
-    d.dst_h = L.dst_h;
-    d.xr = r.xr;
-    d.yr = r.yr;
-    d.swap_rb = L.swap_rb;
-    d.color_g = L.color_g;
-    d.k = L.k;
-    d.tx = ROI_TX;
-    d.ty = ROI_TY;
-    d.tx_shift = ROI_TX_SHIFT;
-    d.rpt = 1;
-    d.nt_stores = L.nt_stores;
-    d.last_col0 = VEC ? L.last_col0 : 0;
-    d.u8_xchg = L.u8_xchg;
-    d.luma_only = kLumaOnly<OUT> ? 1 : 0;
+    tile_desc<OUT, VEC>(L, r, d);
 
     const uint8_t *const plane_y = (const uint8_t *)(GP)(uintptr_t)r.y, *const plane_uv = (const uint8_t *)(GP)(uintptr_t)r.uv;
     T *const out = (T *)(GP)(uintptr_t)r.out;
+    // (the coordinates are written out in all three tile kernels: as a helper of vpp_tile_core.h they moved VGPRs in vpp_rois_kernel and vpp_letterbox_kernel)
     const int lx = threadIdx.x & (ROI_TX - 1), ly = threadIdx.x >> ROI_TX_SHIFT;
     const int j_first = roi_tile_col0(txi, L.dst_w, d.last_col0), i_first = tyi * ROI_TILE_H;
     const int j_last = min(j_first + ROI_TILE_W, L.dst_w) - 1, i_last = min(i_first + ROI_TILE_H, L.dst_h) - 1;
@@ -155,9 +136,10 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_rois_area_kernel(const RoiLau
     if constexpr (STAGED) {
         const int mode = down ? M_AREA_DOWN : M_AREA_UP;
         RoiFootprint f;
-        roi_span_x(mode, j_first, L.dst_w, r.src_w, r.xr, f);
-        roi_span_y(mode, i_first, L.dst_h, r.src_h, r.yr, f);
+        tile_span_x(mode, j_first, j_last, r.src_w, r.xr, f);
+        tile_span_y(mode, i_first, i_last, r.src_h, r.yr, f);
         if (roi_stageable(f) && roi_lds_need(f, kLumaOnly<OUT>) <= L.lds_bytes) { // (wave-uniform)
+            // (the staging block is written out in all three tile kernels: as a helper it changed their instructions and measured slower, profiles/tile_core_ab.txt)
             const int span_y = f.xhi - f.xlo + 1, span_uv = 2 * (f.cxhi - f.cxlo + 1);
             const int ny = f.yhi - f.ylo + 1, nuv = kLumaOnly<OUT> ? 0 : f.cyhi - f.cylo + 1;
             d.lds_cpr_y = roi_chunks(span_y);
@@ -190,12 +172,7 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_rois_area_kernel(const RoiLau
     }
     if (!active) return;
     GlobalSrc gs;
-    gs.y = plane_y;
-    gs.uv = plane_uv;
-    gs.py = r.pitch_y;
-    gs.puv = r.pitch_uv;
-    gs.w = r.src_w;
-    gs.h = r.src_h;
+    tile_global_src(gs, r, plane_y, plane_uv);
     if (down) {
         if (STAGED && staged) area_thread_tile<OUT, VEC, EL>(ls, d, w, L.spec, out, i0, j0);
         else area_thread_tile<OUT, VEC, EL>(gs, d, w, L.spec, out, i0, j0);

@@ -2,9 +2,7 @@
 // with the library's colour back end (EL_LIB: every flavour of tsvpp_convert_rois) and vpp_rois_tensor.hip with the tensor store (EL_F32 / EL_HALF:
 // tsvpp_convert_rois_tensor, vpp_tensor_store.h).  Nothing but the store call differs between them.
 #pragma once
-#include "vpp_device.h"
-#include "vpp_rois.h"
-#include "vpp_tensor_store.h"
+#include "vpp_tile_core.h"
 
 #pragma clang fp contract(off)
 
@@ -15,14 +13,13 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_rois_kernel(const RoiLaunch L
     using T = typename OutT<OUT>::type;
     typedef __attribute__((address_space(1))) uint8_t *GP; // the records hold GLOBAL addresses (PtrCol, vpp_kernels.h)
     // workgroup -> (box, tile): all tiles of a box are neighbours in the grid, so the lines that adjacent tiles share meet in L2
-    const int tiles = L.tiles_x * L.tiles_y;
-    const int box = (int)blockIdx.x / tiles;
-    const int rem = (int)blockIdx.x - box * tiles;
-    const int tyi = rem / L.tiles_x, txi = rem - tyi * L.tiles_x;
+    const TileIndex tix = tile_index(L.tiles_x, L.tiles_y);
+    const int box = tix.item, tyi = tix.tyi, txi = tix.txi;
     if (box >= L.n_rois) return;
     const RoiRec &r = L.r[box]; // wave-uniform index: scalar loads
 
-    // the samplers and the colour back end read their request from a LaunchDesc: this box's
+    // the samplers and the colour back end read their request from a LaunchDesc: this box's (written out, like the GlobalSrc fill below: with tile_desc /
+    // tile_global_src of vpp_tile_core.h the BILINEAR Y800 element-wise gather kernels of this template compile to other instructions)
     LaunchDesc d = {};
     d.src_w = r.src_w;
     d.src_h = r.src_h;
@@ -46,6 +43,7 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_rois_kernel(const RoiLaunch L
 
     const uint8_t *const plane_y = (const uint8_t *)(GP)(uintptr_t)r.y, *const plane_uv = (const uint8_t *)(GP)(uintptr_t)r.uv;
     T *const out = (T *)(GP)(uintptr_t)r.out;
+    // (the coordinates are written out in all three tile kernels: as a helper of vpp_tile_core.h they moved VGPRs in vpp_rois_kernel and vpp_letterbox_kernel)
     const int lx = threadIdx.x & (ROI_TX - 1), ly = threadIdx.x >> ROI_TX_SHIFT;
     const int j_first = roi_tile_col0(txi, L.dst_w, d.last_col0), i_first = tyi * ROI_TILE_H;
     const int j0 = j_first + lx * PXW, i0 = i_first + ly * PXH;
@@ -53,9 +51,10 @@ __global__ __launch_bounds__(ROI_THREADS) void vpp_rois_kernel(const RoiLaunch L
 
     if constexpr (STAGED) {
         RoiFootprint f;
-        roi_span_x(MODE, j_first, L.dst_w, r.src_w, r.xr, f);
-        roi_span_y(MODE, i_first, L.dst_h, r.src_h, r.yr, f);
+        tile_span_x(MODE, j_first, tile_last(j_first, ROI_TILE_W, L.dst_w), r.src_w, r.xr, f);
+        tile_span_y(MODE, i_first, tile_last(i_first, ROI_TILE_H, L.dst_h), r.src_h, r.yr, f);
         if (roi_stageable(f) && roi_lds_need(f, kLumaOnly<OUT>) <= L.lds_bytes) { // (wave-uniform)
+            // (the staging block is written out in all three tile kernels: as a helper it changed their instructions and measured slower, profiles/tile_core_ab.txt)
             const int span_y = f.xhi - f.xlo + 1, span_uv = 2 * (f.cxhi - f.cxlo + 1);
             const int ny = f.yhi - f.ylo + 1, nuv = kLumaOnly<OUT> ? 0 : f.cyhi - f.cylo + 1;
             d.lds_cpr_y = roi_chunks(span_y);

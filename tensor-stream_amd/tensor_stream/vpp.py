@@ -212,6 +212,12 @@ class VideoProcessor:
             acc *= d
         return flat.as_strided((n,) + tuple(shape), (stride,) + tuple(inner))
 
+    def _alloc_items(self, p, n, spec, needs):
+        """The outputs of convert_rois / convert_letterbox: n frames of the parameters' own size (no stage changes it), in the spec's element if there is one."""
+        if p.dst_width <= 0 or p.dst_height <= 0 or (p.dst_width | p.dst_height) & 1:
+            raise RuntimeError(f"-3: {needs} (width / height of the parameters)")
+        return self._alloc(p, p.dst_width, p.dst_height, n, None if spec is None else _torch_dtype(spec))
+
     @staticmethod
     def _frame(y, uv, width, height):
         assert y.is_cuda and uv.is_cuda and y.dtype == torch.uint8 and uv.dtype == torch.uint8
@@ -281,9 +287,7 @@ class VideoProcessor:
         if n == 0:
             raise RuntimeError("-3: convert_rois needs at least one box")
         if out is None:
-            if p.dst_width <= 0 or p.dst_height <= 0 or (p.dst_width | p.dst_height) & 1:
-                raise RuntimeError("-3: convert_rois needs an even, positive output size (width / height of the parameters)")
-            out = self._alloc(p, p.dst_width, p.dst_height, n, None if spec is None else _torch_dtype(spec))  # (a frame of the output size: no stage changes it)
+            out = self._alloc_items(p, n, spec, "convert_rois needs an even, positive output size")
         recs = (N.Roi * n)(*[N.Roi(*b) for b in boxes])
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -310,9 +314,7 @@ class VideoProcessor:
         widths, heights = _per_frame(width, n), _per_frame(height, n)
         frames = (N.NV12 * n)(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(n)])
         if out is None:
-            if p.dst_width <= 0 or p.dst_height <= 0 or (p.dst_width | p.dst_height) & 1:
-                raise RuntimeError("-3: convert_letterbox needs an even, positive canvas size (width / height of the parameters)")
-            out = self._alloc(p, p.dst_width, p.dst_height, n, None if spec is None else _torch_dtype(spec))  # (a frame of the canvas size: no stage changes it)
+            out = self._alloc_items(p, n, spec, "convert_letterbox needs an even, positive canvas size")
         recs = None if rects is None else _rects(rects, n)
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -473,17 +475,22 @@ def describe_rois_area(params, frames, rois, aligned_outputs=True, dtype=None, m
     return _describe_rois(N.lib().tsvpp_describe_rois_area, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
 
 
-def _describe_rois(entry, params, frames, rois, aligned_outputs, spec=None):
-    p = params.parameters if isinstance(params, FrameParameters) else params
+def _geometry_records(frames):
+    """The frames argument of the describe functions -- (width, height), (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list -- as NV12
+    records without planes."""
     if frames and isinstance(frames[0], int):
         frames = [frames]
     recs = []
     for f in frames:
         f = tuple(int(v) for v in f)
-        w, h = f[0], f[1]
         py = f[2] if len(f) > 2 else 0
-        puv = f[3] if len(f) > 3 else py
-        recs.append(N.NV12(None, None, py, puv, w, h))
+        recs.append(N.NV12(None, None, py, f[3] if len(f) > 3 else py, f[0], f[1]))
+    return recs
+
+
+def _describe_rois(entry, params, frames, rois, aligned_outputs, spec=None):
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
     _, _, boxes = _normalize_rois([None] * len(recs), [None] * len(recs), rois)
     fr = (N.NV12 * len(recs))(*recs)
     bx = (N.Roi * max(len(boxes), 1))(*[N.Roi(*b) for b in boxes])
@@ -513,13 +520,7 @@ def describe_letterbox(params, frames, rects=None, aligned_outputs=True, dtype=N
     """What a convert_letterbox of this request would launch, as a dict (tsvpp_describe_letterbox: describe_rois's keys, then inner = "WxH+left+top" of the first
     frame) -- host logic only, works without a GPU.  frames: (width, height) or (width, height, pitch) or (width, height, pitch_y, pitch_uv), one or a list."""
     p = params.parameters if isinstance(params, FrameParameters) else params
-    if frames and isinstance(frames[0], int):
-        frames = [frames]
-    recs = []
-    for f in frames:
-        f = tuple(int(v) for v in f)
-        py = f[2] if len(f) > 2 else 0
-        recs.append(N.NV12(None, None, py, f[3] if len(f) > 3 else py, f[0], f[1]))
+    recs = _geometry_records(frames)
     fr = (N.NV12 * max(len(recs), 1))(*recs)
     rc = None if rects is None else _rects(rects, len(recs))
     buf = ctypes.create_string_buffer(512)

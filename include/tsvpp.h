@@ -173,7 +173,7 @@ int tsvpp_convert_table(tsvpp_ctx *ctx, const tsvpp_table *table, int first, int
  * with xr = (float)width / dst_width, yr = (float)height / dst_height; for a box Convert's crop stage accepts it equals tsvpp_convert(crop = box).  A box of
  * exactly dst_width x dst_height is a plain colour conversion (every interpolation weight is zero).
  * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  TSVPP_UNSUPPORTED here: AREA (it has an entry point
- * of its own, tsvpp_convert_rois_area below), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes, rotated boxes.
+ * of its own, tsvpp_convert_rois_area below), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes; rotated and affine-warped boxes are tsvpp_convert_warp's (below).
  * fp16 / bf16 outputs and a per-channel mean / scale are tsvpp_convert_rois_tensor's (below), not this call's.
  * `frames`, `rois`, `outs` are HOST arrays and may be freed on return: the per-box records (plane origins, pitches, size, ratios, output pointer: 48 bytes)
  * travel BY VALUE in the kernarg segment of their launch -- no staging buffer, no copy, no allocation, no host synchronisation -- which is what bounds a
@@ -326,6 +326,71 @@ int tsvpp_convert_letterbox_tensor(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, 
                                    int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
 int tsvpp_describe_letterbox_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
                                     int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- affine warps (not in the reference) ---------------------------------------------------------------------------------------------------------------------
+ * The second stage behind a detector when an axis-aligned box is not enough: a face aligned to 112 x 112 by a similarity transform, a rotated OCR / aerial box,
+ * an affine crop for a pose head.  `n_warps` outputs, each p->dst_width x p->dst_height, each sampled BILINEAR out of one of `n_frames` NV12 frames through its own
+ * 2 x 3 matrix, colour-converted and stored to its own output, in ceil(n_warps / TSVPP_MAX_WARPS) kernel launches (today: a tsvpp_convert of the whole frame to
+ * fp32 planar, then a grid sampler over it -- a full-frame round trip through memory, and not this library's arithmetic).
+ *   The map      m is the output -> source (inverse) map.  With u = j + 0.5, v = i + 0.5 the centre of output pixel (row i, column j), the source position is
+ *                    X = m[0] u + m[1] v + m[2]        Y = m[3] u + m[4] v + m[5]
+ *                in luma pixels of the WHOLE frame, pixel k covering [k, k + 1).  From OpenCV's index-based inverse matrix [a b c; d e f] (what warpAffine takes
+ *                with WARP_INVERSE_MAP): m = (a, b, c + 0.5 - 0.5 (a + b), d, e, f + 0.5 - 0.5 (d + e)).
+ *   Arithmetic   The host computes once per warp, in fp32 with one rounding each, tx = m[2] - 0.5f, ty = m[5] - 0.5f, ctx = m[2] * 0.5f - 0.5f,
+ *                cty = m[5] * 0.5f - 0.5f (the multiplication by 0.5 is exact).  Luma, output pixel (i, j), contraction off, the fmaf()s explicit:
+ *                    fx = fmaf((float)j + 0.5f, m[0], fmaf((float)i + 0.5f, m[1], tx))        fy = fmaf((float)j + 0.5f, m[3], fmaf((float)i + 0.5f, m[4], ty))
+ *                then per axis the tail of the library's BILINEAR coordinate with limit = the frame's width / height: p = floor(f), w = f - p; p < 0 -> p = 0, w = 0;
+ *                p > limit - 1 -> p = limit - 1, w = 0; the second tap is p + 1 if p + 1 < limit, else p (where w was forced to 0 it is multiplied by zero and need
+ *                not be fetched).  The four taps go through the library's bilinear blend (the fma tree the reference's goldens pin), truncated.  Chroma pair
+ *                (ci, cj): the same with ctx / cty on the pair's own indices, limits width / 2 and height / 2, U and V from byte columns 2 p and 2 p + 1 -- never
+ *                derived from the luma coordinates.  The kernel clamps f into [-1, limit] before converting it to an integer, which changes no result.  The
+ *                virtual NV12 frame of dst_width x dst_height that results goes through the one colour back end: the output is, bit for bit, what tsvpp_convert
+ *                without a resize returns for that virtual frame.  With m = ((float)w / dst_w, 0, 0, 0, (float)h / dst_h, 0) the expressions reduce to the
+ *                BILINEAR coordinate itself: the call equals tsvpp_convert(BILINEAR, dst) of the whole frame bit for bit.
+ *   Border       border_y = border_u = border_v = -1: replicate -- the clamps above are the whole rule.  Otherwise each is 0..255 and a sample whose position lies
+ *                outside the frame takes the border component instead of a blend: luma where fx < -0.5f || fx >= w - 0.5f || fy < -0.5f || fy >= h - 0.5f, chroma
+ *                under the same test on its own fx, fy with w / 2, h / 2 (luma and chroma decide independently).  The border value then goes through the colour
+ *                back end like any sample, as the letterbox pad does.
+ * `frames`, `outs`, `p`, the output layout and size (tsvpp_out_bytes(p, dst_width, dst_height)) are tsvpp_convert_rois's, and so are: host arrays that may be freed on
+ * return; the per-warp records (72 bytes) by value in the kernarg segment, which bounds a launch to TSVPP_MAX_WARPS; no allocation, no copy, no host
+ * synchronisation; legal while `stream` is being captured; always an ordinary in-order launch; TSVPP_OPT_COLOR_G_TERM and the coefficient block honoured.
+ * Supported: p->resize_type == TSVPP_BILINEAR; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.
+ * Status, decided before any device is touched (tsvpp_describe_warp returns the same one):
+ *   TSVPP_ERROR        null arguments, n_frames <= 0, n_warps <= 0, a frame without size or with a pitch below its width, `frame` out of range, dst_* <= 0, non-zero
+ *                      crop_*, a border component outside -1..255 or a mix of -1 and non-negative components, a matrix entry that is not finite; when converting:
+ *                      a null plane or output.
+ *   TSVPP_UNSUPPORTED  odd dst_*, an odd frame size, a resize type other than BILINEAR, an output format outside the list, |m[k]| > 2^24 (with that bound every
+ *                      coordinate is finite), an output of 4 GiB or more.
+ * Out of scope, follow-ups: NEAREST / BICUBIC / AREA warps, perspective (3 x 3) maps, a device-resident matrix list, per-warp output sizes, merged half-precision
+ * tensors. */
+#define TSVPP_MAX_WARPS 32 /* outputs per launch; more are split */
+typedef struct tsvpp_warp {
+    int32_t frame; /* index into `frames` */
+    float m[6];    /* output -> source, see above */
+} tsvpp_warp;      /* 28 bytes */
+int tsvpp_convert_warp(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, const tsvpp_params *p, int border_y, int border_u,
+                       int border_v, void *const *outs, void *stream);
+/* What tsvpp_convert_warp WOULD launch, as one line of key=value text with tsvpp_describe_rois's keys: "mode=warp_bilinear out=f32_planar dst=112x112 warps=33 frames=1
+ * launches=2 kernel=vpp_warp<...> shape=8x16 lds=.. grid=.. tiles=4x4 staged=.. tail=.. nt=.. limit=32 border=replicate" (or border=Y,U,V).  staged = the warps whose
+ * every tile stages its source bounding box in LDS; a launch may mix staged and gathering tiles.  Host only: needs no context and no GPU. */
+int tsvpp_describe_warp(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v,
+                        int aligned_outputs, char *buf, size_t buf_len);
+/* The tensor forms: outputs, `spec` and the status rules are tsvpp_convert_rois_tensor's, word for word (rule 1 is tsvpp_convert_warp's status; rules 2 and 3 come
+ * after it); the border sample goes through the spec like every sample.  Kernel names vpp_warp_tensor<...>. */
+int tsvpp_convert_warp_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, const tsvpp_params *p,
+                              const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+int tsvpp_describe_warp_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps,
+                               int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* The matrix that maps the whole dst_w x dst_h output onto the box of size box_w x box_h centred at (cx, cy) (luma pixels) and rotated by angle_rad (from the x
+ * axis towards the y axis, i.e. clockwise on screen).  With c = cos(angle_rad), s = sin(angle_rad), evaluated in double and each entry rounded once to float:
+ *     m = (box_w c / dst_w, -box_h s / dst_h, cx - 0.5 box_w c + 0.5 box_h s,        box_w s / dst_w, box_h c / dst_h, cy - 0.5 box_w s - 0.5 box_h c)
+ * Angle 0 with the box equal to the frame gives ((float)w / dst_w, 0, 0, 0, (float)h / dst_h, 0).  out->frame is left as it is.  TSVPP_ERROR for a null `out`, an
+ * argument that is not finite, box_w / box_h / dst_w / dst_h <= 0. */
+int tsvpp_warp_rotated_box(double cx, double cy, double box_w, double box_h, double angle_rad, int dst_w, int dst_h, tsvpp_warp *out);
+/* DEBUG ONLY (tests), host only: the source bounding box the kernel and the host compute for output columns [j_first, j_last] / rows [i_first, i_last] (a tile:
+ * even first, odd last) of `warp` on a frame of frame_w x frame_h: out8 = { xlo, xhi, ylo, yhi } in luma pixels, then { cxlo, cxhi, cylo, cyhi } in chroma pairs.
+ * TSVPP_ERROR for null arguments, a frame size <= 0, an empty or negative range. */
+int tsvpp_warp_footprint(const tsvpp_warp *warp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
 
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them

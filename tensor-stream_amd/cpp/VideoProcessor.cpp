@@ -238,6 +238,34 @@ static int convertLetterbox(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ct
     return VREADER_OK;
 }
 
+// ConvertWarp and its tensor overload differ in the entry point of the C ABI they end in (`tensor`: tsvpp_convert_warp_tensor with `spec`)
+static int convertWarp(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps,
+                       int borderY, int borderU, int borderV, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName) {
+    if (isClosed || !inputs || nInputs <= 0 || !warps || nWarps <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
+    void *stream = nullptr;
+    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    std::vector<tsvpp_nv12> frames((size_t)nInputs);
+    for (int f = 0; f < nInputs; f++) {
+        const AVFrame *in = inputs[f];
+        if (!in) CHECK_STATUS(VREADER_ERROR);
+        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
+    }
+    const tsvpp_params p = flatten(options); // options.crop must be empty: the matrices address the whole frame
+    if (tensor) CHECK_STATUS(tsvpp_convert_warp_tensor(ctx, nInputs, frames.data(), nWarps, warps, &p, spec, borderY, borderU, borderV, deviceOuts, stream));
+    else CHECK_STATUS(tsvpp_convert_warp(ctx, nInputs, frames.data(), nWarps, warps, &p, borderY, borderU, borderV, deviceOuts, stream));
+    return VREADER_OK;
+}
+
+int VideoProcessor::ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                                FrameParameters &options, std::string consumerName) {
+    return convertWarp(false, nullptr, ctx, isClosed, inputs, nInputs, warps, nWarps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+}
+
+int VideoProcessor::ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                                FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertWarp(true, spec, ctx, isClosed, inputs, nInputs, warps, nWarps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+}
+
 int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &options, std::string consumerName) {
     if (isClosed || !input || !output) CHECK_STATUS(VREADER_ERROR);
     const tsvpp_params p = flatten(options);

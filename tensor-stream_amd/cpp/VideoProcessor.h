@@ -136,6 +136,14 @@ public:
                     const tsvpp_tensor_spec *spec, std::string consumerName);
     int ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                          const tsvpp_tensor_spec *spec, std::string consumerName);
+    // Rotated and affine-warped boxes (tsvpp_convert_warp, include/tsvpp.h; not in the reference): warps[i] samples inputs[warps[i].frame] BILINEAR through its
+    // output -> source matrix into options.resize.width x height, colour-converted and written to deviceOuts[i], one kernel launch per TSVPP_MAX_WARPS outputs on the
+    // consumer's stream.  borderY = borderU = borderV = -1 replicates the frame's edge; else each is 0..255, the sample outside the frame.  options.resize.type must
+    // be BILINEAR, options.crop empty; the inputs are NOT consumed.  Same status convention as ConvertInto.  With a tensor spec: tsvpp_convert_warp_tensor.
+    int ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                    FrameParameters &options, std::string consumerName);
+    int ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                    FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

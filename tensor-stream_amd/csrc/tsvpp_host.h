@@ -242,6 +242,8 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
 // (tsvpp_convert_letterbox / tsvpp_describe_letterbox; RoiPlan: the canvas is its dst_w x dst_h).  letterbox_rect_of: frame k's rectangle, the caller's or the default
 int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);
 tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int k, int dst_w, int dst_h);
+// (tsvpp_convert_warp / tsvpp_describe_warp; RoiPlan: mode is M_BILINEAR).  The border is (-1, -1, -1), replicate, or three components 0..255
+int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl);
 // (the tensor entry points of both paths) the status of a (params, spec) pair whose plan was accepted: rules 2 and 3 of include/tsvpp.h, in that order
 int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec);
 inline size_t tensor_elem_bytes(int dtype) { return dtype == TSVPP_F32 ? 4 : 2; }

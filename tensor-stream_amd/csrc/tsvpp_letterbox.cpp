@@ -12,6 +12,7 @@ namespace {
 struct LbPath {
     using Launch = LbLaunch;
     static constexpr bool kInnerRect = true; // a frame fills its inner rectangle: tiles that miss it stage nothing
+    static constexpr bool kOwnBudget = false;
     bool tensor;
     const tsvpp_params *p;
     const tsvpp_tensor_spec *spec;
@@ -60,6 +61,7 @@ struct LbPath {
         std::snprintf(buf, len, "tsvpp_convert_letterbox%s n=%d ->%dx%d mode=%d fourcc=%d stream=%p", tensor ? "_tensor" : "", n_frames, pl.dst_w, pl.dst_h, (int)pl.mode, p->fourcc, stream);
     }
     void counts(char *buf, size_t len) const { std::snprintf(buf, len, "frames=%d", n_frames); }
+    const char *mode_name(const RoiPlan &pl) const { return mode_names[pl.mode]; }
     void suffix(char *buf, size_t len, const RoiPlan &pl) const {
         const tsvpp_rect r0 = letterbox_rect_of(frames, rects, 0, pl.dst_w, pl.dst_h);
         std::snprintf(buf, len, " inner=%dx%d+%d+%d", r0.width, r0.height, r0.left, r0.top);

@@ -284,6 +284,28 @@ int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsv
     return tile_output_plan(p, false, TSVPP_MAX_LETTERBOX, pl);
 }
 
+int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl) {
+    // TSVPP_ERROR: arguments that describe no request at all
+    if (!p || !frames || !warps || n_frames <= 0 || n_warps <= 0) return TSVPP_ERROR;
+    if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
+    for (int i = 0; i < n_warps; i++)
+        if (warps[i].frame < 0 || warps[i].frame >= n_frames) return TSVPP_ERROR;
+    const bool replicate = border_y == -1 && border_u == -1 && border_v == -1;
+    if (!replicate && (border_y < 0 || border_y > 255 || border_u < 0 || border_u > 255 || border_v < 0 || border_v > 255)) return TSVPP_ERROR;
+    for (int i = 0; i < n_warps; i++)
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(warps[i].m[k])) return TSVPP_ERROR;
+    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
+    if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    // NEAREST, BICUBIC and AREA warps: follow-ups
+    if (tile_output_plan(p, false, TSVPP_MAX_WARPS, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
+    // with every entry inside 2^24 and indices below 2^31 no coordinate overflows: every f is finite
+    for (int i = 0; i < n_warps; i++)
+        for (int k = 0; k < 6; k++)
+            if (std::fabs(warps[i].m[k]) > 16777216.0f) return TSVPP_UNSUPPORTED;
+    return TSVPP_OK;
+}
+
 // One spec check for both tensor paths.  The caller has the plan's status already (it wins); what is left is about the spec and about what the tensor stores cover.
 int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec) {
     if (!p || !spec) return TSVPP_ERROR;

@@ -13,6 +13,7 @@ namespace {
 struct RoiPath {
     using Launch = RoiLaunch;
     static constexpr bool kInnerRect = false; // a box fills the whole output
+    static constexpr bool kOwnBudget = false;
     bool area, tensor;
     const tsvpp_params *p;
     const tsvpp_tensor_spec *spec;
@@ -64,6 +65,7 @@ struct RoiPath {
                       pl.dst_h, (int)pl.mode, p->fourcc, stream);
     }
     void counts(char *buf, size_t len) const { std::snprintf(buf, len, "rois=%d frames=%d", n_rois, n_frames); }
+    const char *mode_name(const RoiPlan &pl) const { return pl.mode == M_AREA_DOWN ? "area" : mode_names[pl.mode]; }
     void suffix(char *buf, size_t len, const RoiPlan &pl) const {
         if (area) std::snprintf(buf, len, " down=%d taps=%dx%d", pl.down, pl.taps_x, pl.taps_y);
     }

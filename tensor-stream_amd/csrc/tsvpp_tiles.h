@@ -2,14 +2,17 @@
 // canvas; both with their tensor forms).  All of them launch one 32 x 32 output tile per workgroup (vpp_tile_core.h) for up to a fixed number of items -- boxes,
 // frames -- per launch.  Here: the launch fields they share, the staging budget, and the skeletons of the convert and the describe call.  A path is a small struct
 // that holds its request and answers what differs:
-//     using Launch, kInnerRect              RoiLaunch / LbLaunch; whether an item fills a rectangle of the output only (TileItem)
+//     using Launch                          RoiLaunch / LbLaunch / WarpLaunch
+//     kOwnBudget                            false: a tile's footprint is a column span times a row span (item(), below); true: the path sizes the staged
+//                                           footprints itself -- stage_budget(pl, L, budget, luma_only) sets L.lds_bytes and returns the items that stage every tile
 //     p, spec, tensor, n_frames, frames     the request (spec: null unless the tensor entry point was called -- where it may be null too: its TSVPP_ERROR)
 //     plan(pl), items(), limit(pl)          the request's status and RoiPlan; how many items it has; how many go into one launch
 //     fill_items(pl, outs, base, cnt, L)    the count, the records and the path's own fields of one launch group (outs: null in a dry run)
-//     item(pl, L, i)                        record i as a TileItem
+//     item(pl, L, i)                        record i as a TileItem (paths without kOwnBudget)
 //     front_lds(L)                          dynamic LDS in front of the staged footprint (the AREA kernel's weight rows)
 //     launch(pl, vec, staged, L, ...)       the launcher
 //     label(...), counts(...), suffix(...)  the marker label; "rois=8 frames=1" and what follows the common keys in the describe line (with its blank)
+//     mode_name(pl)                         the describe line's mode=
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -30,6 +33,8 @@ struct TileItem {
     float xr, yr;
     int left, top, width, height;
 };
+
+template <class PATH> int tile_separable_budget(const PATH &path, const RoiPlan &pl, typename PATH::Launch &L, int cnt, int budget, bool luma_only);
 
 // One launch group: items [base, base + cnt) as a launch block.  Returns how many of the group's items stage EVERY tile in LDS; L.lds_bytes = the dynamic LDS
 // the launch needs for them (0: the gather kernel).
@@ -53,6 +58,12 @@ template <class PATH> int tile_fill(const PATH &path, const Knobs &kn, const Roi
     // the staging budget: an item stages if the largest footprint among its tiles fits what the workgroup's LDS budget leaves
     const bool luma_only = out_luma_only(pl.out);
     const int budget = kn.force_gather ? 0 : kn.lds_budget_kb * 1024 - roi_static_lds(pl.out, vec) - path.front_lds(L);
+    if constexpr (PATH::kOwnBudget) return path.stage_budget(pl, L, budget, luma_only);
+    else return tile_separable_budget(path, pl, L, cnt, budget, luma_only);
+}
+
+// ... of a path whose tiles tap a column span times a row span of the source: an item stages if the largest footprint among its tiles fits the budget
+template <class PATH> int tile_separable_budget(const PATH &path, const RoiPlan &pl, typename PATH::Launch &L, int cnt, int budget, bool luma_only) {
     int staged = 0, lds = 0;
     for (int i = 0; i < cnt; i++) {
         const TileItem it = path.item(pl, L, i);
@@ -160,7 +171,7 @@ template <class PATH> int tile_describe(PATH path, int aligned_outputs, char *bu
     path.counts(counts, sizeof(counts));
     path.suffix(suffix, sizeof(suffix), pl);
     std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d %s launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d staged=%d tail=%d nt=%d limit=%d%s",
-                  pl.mode == M_AREA_DOWN ? "area" : mode_names[pl.mode], path.tensor ? tensor_out_name(path.spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w,
+                  path.mode_name(pl), path.tensor ? tensor_out_name(path.spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w,
                   pl.dst_h, counts, launches, kname, ROI_TX, ROI_TY, lds0 + roi_static_lds(pl.out, vec), grid0, L.tiles_x, L.tiles_y, staged, L.last_col0 > 0 ? 2 : 0, L.nt_stores,
                   limit, suffix);
     return TSVPP_OK;

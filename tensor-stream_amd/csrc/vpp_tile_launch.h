@@ -13,6 +13,7 @@ inline constexpr const char *kModeNames[M_COUNT] = { "M_NONE", "M_NEAREST", "M_B
 inline constexpr const char *kOutNames[O_COUNT] = { "O_U8_PLANAR", "O_U8_MERGED", "O_F32_PLANAR", "O_F32_MERGED", "O_NV12_U8", "O_NV12_F32", "O_Y800_U8", "O_Y800_F32", "O_HSV_F32" };
 inline const char *vec_name(bool vec) { return vec ? "vec" : "elem"; }
 inline const char *staged_name(bool staged) { return staged ? "staged" : "gather"; }
+inline const char *border_name(bool border) { return border ? "border" : "replicate"; } // (vpp_warp.hip: a constant outside the frame, or the edge pixel)
 
 // the modes the ROI and letterbox kernels are instantiated for (the AREA kernel has no mode argument: it chooses per box)
 constexpr bool tile_mode(int mode) { return mode == M_NEAREST || mode == M_BILINEAR || mode == M_BICUBIC; }
@@ -51,5 +52,7 @@ template <class F> inline hipError_t with_vec_staged(bool vec, bool staged, F &&
     if (vec) return staged ? f(std::true_type(), std::true_type()) : f(std::true_type(), std::false_type());
     return staged ? f(std::false_type(), std::true_type()) : f(std::false_type(), std::false_type());
 }
+// f(BORDER) of the warp units
+template <class F> inline hipError_t with_border(bool border, F &&f) { return border ? f(std::true_type()) : f(std::false_type()); }
 
 } // namespace tsvpp

@@ -12,6 +12,7 @@ TSVPP_MAX_BATCH = 128
 TSVPP_MAX_ROIS = 64  # boxes per launch of tsvpp_convert_rois (their records travel in the kernarg segment)
 TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
 TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
+TSVPP_MAX_WARPS = 32  # outputs per launch of tsvpp_convert_warp
 TSVPP_F32, TSVPP_F16, TSVPP_BF16 = 0, 1, 2  # enum tsvpp_dtype: the element of the tensor entry points
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
@@ -45,6 +46,11 @@ class Rect(ctypes.Structure):
     _fields_ = [("left", ctypes.c_int32), ("top", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
 
 
+class Warp(ctypes.Structure):
+    """struct tsvpp_warp: the output -> source matrix of one output of tsvpp_convert_warp, and the frame it samples."""
+    _fields_ = [("frame", ctypes.c_int32), ("m", ctypes.c_float * 6)]
+
+
 class TensorSpec(ctypes.Structure):
     """struct tsvpp_tensor_spec: element type, per-channel mean and scale (= 1 / std) of the tensor entry points."""
     _fields_ = [("dtype", ctypes.c_int32), ("mean", ctypes.c_float * 3), ("scale", ctypes.c_float * 3)]
@@ -62,7 +68,8 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_table_create", "tsvpp_table_destroy", "tsvpp_table_set", "tsvpp_convert_table", "tsvpp_trim", "tsvpp_set_option", "tsvpp_get_option", "tsvpp_consumer_next_stream", "tsvpp_consumer_synchronize",
            "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables",
            "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox",
-           "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor"]
+           "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor",
+           "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint"]
 
 _lib = None
 
@@ -142,6 +149,19 @@ def lib():
     L.tsvpp_convert_letterbox_tensor.restype = i32
     L.tsvpp_describe_letterbox_tensor.argtypes = [pp, ps, i32, pn, pc, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_describe_letterbox_tensor.restype = i32
+    pw = ctypes.POINTER(Warp)
+    L.tsvpp_convert_warp.argtypes = [vp, i32, pn, i32, pw, pp, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_warp.restype = i32
+    L.tsvpp_describe_warp.argtypes = [pp, i32, pn, i32, pw, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_warp.restype = i32
+    L.tsvpp_convert_warp_tensor.argtypes = [vp, i32, pn, i32, pw, pp, ps, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_warp_tensor.restype = i32
+    L.tsvpp_describe_warp_tensor.argtypes = [pp, ps, i32, pn, i32, pw, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_warp_tensor.restype = i32
+    L.tsvpp_warp_rotated_box.argtypes = [ctypes.c_double] * 5 + [i32, i32, pw]
+    L.tsvpp_warp_rotated_box.restype = i32
+    L.tsvpp_warp_footprint.argtypes = [pw, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
+    L.tsvpp_warp_footprint.restype = i32
     L.tsvpp_debug_area_tables.argtypes = [vp]
     L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

@@ -329,6 +329,34 @@ class VideoProcessor:
             used = [(r.left, r.top, r.width, r.height) for r in recs]
         return out, used
 
+    def convert_warp(self, ys, uvs, warps, params, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """Rotated and affine-warped boxes behind a detector (tsvpp_convert_warp): every entry of `warps` samples its frame BILINEAR through its own 2 x 3
+        output -> source matrix into params' width x height, colour-converted and stored to its own output, one launch per 32 outputs.  ys / uvs: as
+        convert_rois (one frame as a pair of planes, or lists; the frames may differ in size and pitch); warps: (m0, m1, m2, m3, m4, m5) of frame 0 or
+        (frame, m0, ..., m5) -- X = m0 u + m1 v + m2, Y = m3 u + m4 v + m5 with (u, v) = (column + 0.5, row + 0.5) the output pixel's centre, in luma pixels of
+        the whole frame (warp_rotated_box, warp_from_opencv make them); border: None replicates the frame's edge, (Y, U, V), each 0..255, is the sample
+        outside the frame.  params' resize_type must be BILINEAR.  Returns (or fills `out`, indexed out[i]) a tensor of shape (n, ...frame shape) with
+        convert_batch's padded frame stride, on torch's current stream.  dtype / mean / std: as convert_rois (tsvpp_convert_warp_tensor); the border sample goes
+        through them like every sample."""
+        spec = tensor_spec(dtype, mean, std)
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        ys, uvs, recs = _normalize_warps(ys, uvs, warps)
+        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
+        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
+        n = len(recs)
+        if n == 0:
+            raise RuntimeError("-3: convert_warp needs at least one matrix")
+        if out is None:
+            out = self._alloc_items(p, n, spec, "convert_warp needs an even, positive output size")
+        by, bu, bv = _border(border)
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if spec is None:
+            N.check(self._lib.tsvpp_convert_warp(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
+        else:
+            N.check(self._lib.tsvpp_convert_warp_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv, outs, stream))
+        return out
+
     def make_batch(self, ys, uvs, params, out=None, width=None, height=None):
         """Pre-builds the descriptor arrays of a batch (the per-frame structs are built once, not per
         call): returns a handle for run_batch().  Keeps the tensors alive."""
@@ -530,6 +558,62 @@ def describe_letterbox(params, frames, rects=None, aligned_outputs=True, dtype=N
     else:
         N.check(N.lib().tsvpp_describe_letterbox_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
+
+
+def _border(border):
+    """border=None: replicate (-1, -1, -1); else (Y, U, V)"""
+    if border is None:
+        return -1, -1, -1
+    y, u, v = (int(c) for c in border)
+    return y, u, v
+
+
+def _normalize_warps(ys, uvs, warps):
+    """The argument forms of convert_warp / describe_warp as (list of luma planes, list of chroma planes, array of tsvpp_warp): one frame may be given as a bare
+    pair of planes, a matrix of frame 0 as six numbers.  Pure Python: touches no device."""
+    ys, uvs, _ = _normalize_rois(ys, uvs, [])
+    recs = []
+    for w in warps:
+        w = tuple(w)
+        if len(w) == 6:
+            w = (0,) + w
+        if len(w) != 7:
+            raise ValueError(f"a warp is (m0, ..., m5) or (frame, m0, ..., m5), not {w}")
+        recs.append(N.Warp(int(w[0]), (ctypes.c_float * 6)(*[float(v) for v in w[1:]])))
+    return ys, uvs, (N.Warp * max(len(recs), 1))(*recs) if recs else []
+
+
+def describe_warp(params, frames, warps, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_warp of this request would launch, as a dict (tsvpp_describe_warp: describe_rois's keys with warps= for rois=, then border = "replicate" or
+    "Y,U,V") -- host logic only, works without a GPU.  frames: as describe_rois; warps and border as for convert_warp."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
+    _, _, ws = _normalize_warps([None] * len(recs), [None] * len(recs), warps)
+    fr = (N.NV12 * len(recs))(*recs)
+    by, bu, bv = _border(border)
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    n = len(ws)
+    if spec is None:
+        N.check(N.lib().tsvpp_describe_warp(ctypes.byref(p), len(recs), fr, n, ws or None, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(N.lib().tsvpp_describe_warp_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, n, ws or None, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def warp_rotated_box(cx, cy, box_w, box_h, angle_rad, dst_w, dst_h):
+    """The matrix (m0, ..., m5), as float32 values, that maps a dst_w x dst_h output onto the box of box_w x box_h luma pixels centred at (cx, cy) and rotated
+    by angle_rad, clockwise on screen (tsvpp_warp_rotated_box: evaluated in double, each entry rounded once)."""
+    w = N.Warp()
+    N.check(N.lib().tsvpp_warp_rotated_box(float(cx), float(cy), float(box_w), float(box_h), float(angle_rad), int(dst_w), int(dst_h), ctypes.byref(w)))
+    return tuple(w.m)
+
+
+def warp_from_opencv(M):
+    """OpenCV's index-based inverse matrix [[a, b, c], [d, e, f]] (output index -> source index: what cv2.warpAffine takes with WARP_INVERSE_MAP, or
+    cv2.invertAffineTransform of the forward one) as this library's centre-based (m0, ..., m5): m2 = c + 0.5 - 0.5 (a + b), m5 = f + 0.5 - 0.5 (d + e)."""
+    (a, b, c), (d, e, f) = [[float(v) for v in row] for row in M]
+    return (a, b, c + 0.5 - 0.5 * (a + b), d, e, f + 0.5 - 0.5 * (d + e))
 
 
 def debug_last_launch():

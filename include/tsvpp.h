@@ -361,8 +361,8 @@ int tsvpp_describe_letterbox_tensor(const tsvpp_params *p, const tsvpp_tensor_sp
  *                      a null plane or output.
  *   TSVPP_UNSUPPORTED  odd dst_*, an odd frame size, a resize type other than BILINEAR, an output format outside the list, |m[k]| > 2^24 (with that bound every
  *                      coordinate is finite), an output of 4 GiB or more.
- * Out of scope, follow-ups: NEAREST / BICUBIC / AREA warps, perspective (3 x 3) maps, a device-resident matrix list, per-warp output sizes, merged half-precision
- * tensors. */
+ * Out of scope, follow-ups: NEAREST / BICUBIC / AREA warps, a device-resident matrix list, per-warp output sizes, merged half-precision tensors.  Perspective
+ * (3 x 3) maps are tsvpp_convert_perspective's (below). */
 #define TSVPP_MAX_WARPS 32 /* outputs per launch; more are split */
 typedef struct tsvpp_warp {
     int32_t frame; /* index into `frames` */
@@ -391,6 +391,71 @@ int tsvpp_warp_rotated_box(double cx, double cy, double box_w, double box_h, dou
  * even first, odd last) of `warp` on a frame of frame_w x frame_h: out8 = { xlo, xhi, ylo, yhi } in luma pixels, then { cxlo, cxhi, cylo, cyhi } in chroma pairs.
  * TSVPP_ERROR for null arguments, a frame size <= 0, an empty or negative range. */
 int tsvpp_warp_footprint(const tsvpp_warp *warp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
+
+/* ---- perspective warps (not in the reference) ---------------------------------------------------------------------------------------------------------------
+ * What no 2 x 3 matrix rectifies: a licence plate, a document page, a shelf label, a court seen from a broadcast camera, a road surface for a bird's-eye view --
+ * quadrilaterals that are no parallelograms.  `n` outputs, each p->dst_width x p->dst_height, each sampled BILINEAR out of one of `n_frames` NV12 frames through
+ * its own 3 x 3 homography, colour-converted and stored to its own output, in ceil(n / TSVPP_MAX_PERSP) kernel launches.
+ *   The map      h is the output -> source homography, row-major.  With u = j + 0.5, v = i + 0.5 the centre of output pixel (row i, column j), the source position,
+ *                in luma pixels of the WHOLE frame with pixel k covering [k, k + 1), is
+ *                    X = (h[0] u + h[1] v + h[2]) / (h[6] u + h[7] v + h[8])        Y = (h[3] u + h[4] v + h[5]) / (h[6] u + h[7] v + h[8])
+ *   Arithmetic   The half-pixel shift is folded into the numerators.  The host computes once per output, in fp32 with one rounding each (the products by 0.5 and
+ *                by 2 are exact):
+ *                    luma    ax = h0 - 0.5f h6    bx = h1 - 0.5f h7    cx = h2 - 0.5f h8        ay = h3 - 0.5f h6    by = h4 - 0.5f h7    cy = h5 - 0.5f h8
+ *                            g  = h6              hh = h7              k  = h8
+ *                    chroma  ax' = h0 - h6        bx' = h1 - h7        cx' = h2 0.5f - h8 0.5f  ay' = h3 - h6        by' = h4 - h7        cy' = h5 0.5f - h8 0.5f
+ *                            g' = 2 h6            hh' = 2 h7           k'  = h8
+ *                Per sample, contraction off, the fmaf()s explicit, u = (float)j + 0.5f, v = (float)i + 0.5f:
+ *                    nx = fmaf(u, ax, fmaf(v, bx, cx))        ny = fmaf(u, ay, fmaf(v, by, cy))        nw = fmaf(u, g, fmaf(v, hh, k))
+ *                    rw = 1.0f / nw   (IEEE, correctly rounded)        fx = nx * rw        fy = ny * rw
+ *                One reciprocal and two products, not two divisions.  Chroma pair (ci, cj): the same expressions with the primed terms on the pair's own indices
+ *                -- never derived from the luma coordinates.  From fx, fy on everything is tsvpp_convert_warp's, word for word: the axis tail with limit = the
+ *                frame's width / height (chroma: half of each), the four taps through the library's bilinear blend, U and V from byte columns 2 p and 2 p + 1,
+ *                the border rule, and the virtual NV12 frame through the one colour back end.  Hence: with h = (m0, m1, m2, m3, m4, m5, 0, 0, 1) the output is
+ *                bit for bit tsvpp_convert_warp's with m (cx = m2 - 0.5f is tx, cx' = m2 0.5f - 0.5f is ctx, nw = rw = 1 and nx * 1 is exact), so the scale-only
+ *                homography equals tsvpp_convert(BILINEAR, dst) of the whole frame; and h and 4 h give the same bits (every operation scales exactly).
+ *   Domain       nw is monotone in u and in v separately (every operation is monotone, rounding is monotone), so its extremes over the output are those of the
+ *                four corner pixels.  The request is TSVPP_UNSUPPORTED unless nw >= 2^-64, evaluated by the expression above, at the four corner pixels of the
+ *                luma grid and at the four corner pairs of the chroma grid.  Then every rw is finite and positive (<= 2^64), every coordinate is finite and no
+ *                NaN can arise.  A map whose vanishing line (the horizon) crosses the output has no answer here.
+ *   Border       as tsvpp_convert_warp: -1, -1, -1 replicates; else a sample whose position lies outside the frame takes the border component.
+ * `frames`, `outs`, `p`, the output layout and everything about the call are tsvpp_convert_warp's: host arrays that may be freed on return; the per-output records
+ * (112 bytes) by value in the kernarg segment, which bounds a launch to TSVPP_MAX_PERSP; no allocation, no copy, no host synchronisation; legal while `stream` is
+ * being captured; TSVPP_OPT_COLOR_G_TERM and the coefficient block honoured.  Supported: TSVPP_BILINEAR; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.
+ * Status, decided before any device is touched (tsvpp_describe_perspective returns the same one), in tsvpp_convert_warp's order:
+ *   TSVPP_ERROR        everything tsvpp_convert_warp answers with it, an entry of h that is not finite among them; when converting: a null plane or output.
+ *   TSVPP_UNSUPPORTED  everything tsvpp_convert_warp answers with it (|h[k]| > 2^24 for its matrix bound), then the horizon rule above.
+ * Out of scope, TSVPP_UNSUPPORTED or follow-ups: NEAREST / BICUBIC / AREA sampling, a device-resident matrix list, per-output sizes, merged half-precision
+ * tensors, maps whose horizon crosses the output. */
+#define TSVPP_MAX_PERSP 32 /* outputs per launch; more are split */
+typedef struct tsvpp_persp {
+    int32_t frame; /* index into `frames` */
+    float h[9];    /* output -> source, row-major, see above */
+} tsvpp_persp;     /* 40 bytes */
+int tsvpp_convert_perspective(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, const tsvpp_params *p, int border_y,
+                              int border_u, int border_v, void *const *outs, void *stream);
+/* What tsvpp_convert_perspective WOULD launch: tsvpp_describe_warp's line and keys (warps= counts the outputs) with mode=persp_bilinear, kernel=vpp_persp<...> (tensor form:
+ * vpp_persp_tensor<...>) and limit=32.  staged = the outputs whose every tile stages its interval box in LDS.  Host only: needs no context and no GPU. */
+int tsvpp_describe_perspective(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, int border_y, int border_u,
+                               int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* The tensor forms: outputs, `spec` and the status rules are tsvpp_convert_warp_tensor's (rule 1 is tsvpp_convert_perspective's status; rules 2 and 3 come after
+ * it); the border sample goes through the spec like every sample. */
+int tsvpp_convert_perspective_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, const tsvpp_params *p,
+                                     const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+int tsvpp_describe_perspective_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps,
+                                      int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* The homography that maps the corners of the dst_w x dst_h output onto the source points quad = (x0, y0, x1, y1, x2, y2, x3, y3) (luma pixels), in the order
+ * top-left, top-right, bottom-right, bottom-left: Heckbert's closed form, evaluated in double, each entry rounded once to float.
+ *     sx = x0 - x1 + x2 - x3        sy = y0 - y1 + y2 - y3        dx1 = x1 - x2   dx2 = x3 - x2   dy1 = y1 - y2   dy2 = y3 - y2
+ *     sx == 0 and sy == 0 (a parallelogram): g = h = 0 exactly;  otherwise den = dx1 dy2 - dx2 dy1, g = (sx dy2 - dx2 sy) / den, h = (dx1 sy - sx dy1) / den
+ *     h0 = (x1 - x0 + g x1) / dst_w   h1 = (x3 - x0 + h x3) / dst_h   h2 = x0        h3 = (y1 - y0 + g y1) / dst_w   h4 = (y3 - y0 + h y3) / dst_h   h5 = y0
+ *     h6 = g / dst_w                  h7 = h / dst_h                  h8 = 1
+ * out->frame is left as it is.  TSVPP_ERROR for null arguments, an input that is not finite, dst_w / dst_h <= 0, den == 0.  Whether the result is usable (a convex
+ * quad, the horizon off the output) is the request rules' decision, not this helper's. */
+int tsvpp_persp_from_quad(const double quad[8], int dst_w, int dst_h, tsvpp_persp *out);
+/* DEBUG ONLY (tests), host only: tsvpp_warp_footprint for `persp` -- the interval box the kernel and the host compute for a tile.  TSVPP_ERROR as there;
+ * TSVPP_UNSUPPORTED where the denominator falls below 2^-64 on either grid of the range (the request rules refuse such an output). */
+int tsvpp_persp_footprint(const tsvpp_persp *persp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
 
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them

@@ -144,6 +144,13 @@ public:
                     FrameParameters &options, std::string consumerName);
     int ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
                     FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
+    // Homography-warped outputs (tsvpp_convert_perspective, include/tsvpp.h; not in the reference): ConvertWarp with a 3 x 3 output -> source homography per
+    // output (tsvpp_persp_from_quad makes one from a quadrilateral).  A homography whose horizon crosses the output is refused.  With a tensor spec:
+    // tsvpp_convert_perspective_tensor.
+    int ConvertPerspective(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                           FrameParameters &options, std::string consumerName);
+    int ConvertPerspective(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                           FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "tsvpp_host.h"
+#include "vpp_persp.h"
 #include "vpp_rois.h"
 
 using namespace tsvpp;
@@ -284,25 +285,46 @@ int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsv
     return tile_output_plan(p, false, TSVPP_MAX_LETTERBOX, pl);
 }
 
-int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl) {
+// The request rules of the matrix paths, once: REC is tsvpp_warp (K = 6 entries) or tsvpp_persp (K = 9); `limit` = outputs per launch
+template <class REC, int K>
+int matrix_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const REC *recs, float (REC::*entries)[K], int border_y, int border_u,
+                int border_v, int limit, RoiPlan &pl) {
     // TSVPP_ERROR: arguments that describe no request at all
-    if (!p || !frames || !warps || n_frames <= 0 || n_warps <= 0) return TSVPP_ERROR;
+    if (!p || !frames || !recs || n_frames <= 0 || n <= 0) return TSVPP_ERROR;
     if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
-    for (int i = 0; i < n_warps; i++)
-        if (warps[i].frame < 0 || warps[i].frame >= n_frames) return TSVPP_ERROR;
+    for (int i = 0; i < n; i++)
+        if (recs[i].frame < 0 || recs[i].frame >= n_frames) return TSVPP_ERROR;
     const bool replicate = border_y == -1 && border_u == -1 && border_v == -1;
     if (!replicate && (border_y < 0 || border_y > 255 || border_u < 0 || border_u > 255 || border_v < 0 || border_v > 255)) return TSVPP_ERROR;
-    for (int i = 0; i < n_warps; i++)
-        for (int k = 0; k < 6; k++)
-            if (!std::isfinite(warps[i].m[k])) return TSVPP_ERROR;
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < K; k++)
+            if (!std::isfinite((recs[i].*entries)[k])) return TSVPP_ERROR;
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     // NEAREST, BICUBIC and AREA warps: follow-ups
-    if (tile_output_plan(p, false, TSVPP_MAX_WARPS, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
-    // with every entry inside 2^24 and indices below 2^31 no coordinate overflows: every f is finite
-    for (int i = 0; i < n_warps; i++)
-        for (int k = 0; k < 6; k++)
-            if (std::fabs(warps[i].m[k]) > 16777216.0f) return TSVPP_UNSUPPORTED;
+    if (tile_output_plan(p, false, limit, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
+    // with every entry inside 2^24 and indices below 2^31 no numerator or denominator overflows: every one is finite
+    for (int i = 0; i < n; i++)
+        for (int k = 0; k < K; k++)
+            if (std::fabs((recs[i].*entries)[k]) > 16777216.0f) return TSVPP_UNSUPPORTED;
+    return TSVPP_OK;
+}
+
+int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl) {
+    return matrix_plan(p, n_frames, frames, n_warps, warps, &tsvpp_warp::m, border_y, border_u, border_v, TSVPP_MAX_WARPS, pl);
+}
+
+int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, int border_y, int border_u, int border_v, RoiPlan &pl) {
+    const int sts = matrix_plan(p, n_frames, frames, n, persps, &tsvpp_persp::h, border_y, border_u, border_v, TSVPP_MAX_PERSP, pl);
+    if (sts != TSVPP_OK) return sts;
+    // the horizon: the denominator, as the kernel evaluates it, is monotone in each index, so its least value over the output is that of a corner pixel (luma
+    // grid) or corner pair (chroma grid).  Below 2^-64 a reciprocal could overflow or change sign: no answer
+    for (int i = 0; i < n; i++) {
+        PerspGrid luma, chroma;
+        persp_terms(persps[i].h, luma, chroma);
+        if (!(persp_min_denominator(luma, 0, pl.dst_w - 1, 0, pl.dst_h - 1) >= PERSP_MIN_DENOMINATOR)) return TSVPP_UNSUPPORTED;
+        if (!(persp_min_denominator(chroma, 0, (pl.dst_w >> 1) - 1, 0, (pl.dst_h >> 1) - 1) >= PERSP_MIN_DENOMINATOR)) return TSVPP_UNSUPPORTED;
+    }
     return TSVPP_OK;
 }
 

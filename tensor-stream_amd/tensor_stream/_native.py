@@ -13,6 +13,7 @@ TSVPP_MAX_ROIS = 64  # boxes per launch of tsvpp_convert_rois (their records tra
 TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
 TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
 TSVPP_MAX_WARPS = 32  # outputs per launch of tsvpp_convert_warp
+TSVPP_MAX_PERSP = 32  # outputs per launch of tsvpp_convert_perspective
 TSVPP_F32, TSVPP_F16, TSVPP_BF16 = 0, 1, 2  # enum tsvpp_dtype: the element of the tensor entry points
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
@@ -51,6 +52,11 @@ class Warp(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_int32), ("m", ctypes.c_float * 6)]
 
 
+class Persp(ctypes.Structure):
+    """struct tsvpp_persp: the output -> source homography (row-major) of one output of tsvpp_convert_perspective, and the frame it samples."""
+    _fields_ = [("frame", ctypes.c_int32), ("h", ctypes.c_float * 9)]
+
+
 class TensorSpec(ctypes.Structure):
     """struct tsvpp_tensor_spec: element type, per-channel mean and scale (= 1 / std) of the tensor entry points."""
     _fields_ = [("dtype", ctypes.c_int32), ("mean", ctypes.c_float * 3), ("scale", ctypes.c_float * 3)]
@@ -69,7 +75,9 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables",
            "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox",
            "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor",
-           "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint"]
+           "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
+           "tsvpp_convert_perspective", "tsvpp_describe_perspective", "tsvpp_convert_perspective_tensor", "tsvpp_describe_perspective_tensor", "tsvpp_persp_from_quad",
+           "tsvpp_persp_footprint"]
 
 _lib = None
 
@@ -162,6 +170,19 @@ def lib():
     L.tsvpp_warp_rotated_box.restype = i32
     L.tsvpp_warp_footprint.argtypes = [pw, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
     L.tsvpp_warp_footprint.restype = i32
+    pq = ctypes.POINTER(Persp)
+    L.tsvpp_convert_perspective.argtypes = [vp, i32, pn, i32, pq, pp, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_perspective.restype = i32
+    L.tsvpp_describe_perspective.argtypes = [pp, i32, pn, i32, pq, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_perspective.restype = i32
+    L.tsvpp_convert_perspective_tensor.argtypes = [vp, i32, pn, i32, pq, pp, ps, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_perspective_tensor.restype = i32
+    L.tsvpp_describe_perspective_tensor.argtypes = [pp, ps, i32, pn, i32, pq, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_perspective_tensor.restype = i32
+    L.tsvpp_persp_from_quad.argtypes = [ctypes.POINTER(ctypes.c_double), i32, i32, pq]
+    L.tsvpp_persp_from_quad.restype = i32
+    L.tsvpp_persp_footprint.argtypes = [pq, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
+    L.tsvpp_persp_footprint.restype = i32
     L.tsvpp_debug_area_tables.argtypes = [vp]
     L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

@@ -357,6 +357,31 @@ class VideoProcessor:
             N.check(self._lib.tsvpp_convert_warp_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv, outs, stream))
         return out
 
+    def convert_perspective(self, ys, uvs, persps, params, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """Homography-warped outputs (tsvpp_convert_perspective): every entry of `persps` samples its frame BILINEAR through its own 3 x 3 output -> source
+        homography into params' width x height, colour-converted and stored to its own output, one launch per 32 outputs.  ys / uvs, border, out, width, height,
+        dtype / mean / std: as convert_warp.  persps: (h0, ..., h8) of frame 0 or (frame, h0, ..., h8), row-major -- X = (h0 u + h1 v + h2) / (h6 u + h7 v + h8),
+        Y = (h3 u + h4 v + h5) / (h6 u + h7 v + h8) with (u, v) = (column + 0.5, row + 0.5) the output pixel's centre, in luma pixels of the whole frame
+        (perspective_from_quad, perspective_from_opencv make them).  A homography whose horizon crosses the output is refused (-2)."""
+        spec = tensor_spec(dtype, mean, std)
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        ys, uvs, recs = _normalize_persps(ys, uvs, persps)
+        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
+        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
+        n = len(recs)
+        if n == 0:
+            raise RuntimeError("-3: convert_perspective needs at least one homography")
+        if out is None:
+            out = self._alloc_items(p, n, spec, "convert_perspective needs an even, positive output size")
+        by, bu, bv = _border(border)
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if spec is None:
+            N.check(self._lib.tsvpp_convert_perspective(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
+        else:
+            N.check(self._lib.tsvpp_convert_perspective_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv, outs, stream))
+        return out
+
     def make_batch(self, ys, uvs, params, out=None, width=None, height=None):
         """Pre-builds the descriptor arrays of a batch (the per-frame structs are built once, not per
         call): returns a handle for run_batch().  Keeps the tensors alive."""
@@ -614,6 +639,60 @@ def warp_from_opencv(M):
     cv2.invertAffineTransform of the forward one) as this library's centre-based (m0, ..., m5): m2 = c + 0.5 - 0.5 (a + b), m5 = f + 0.5 - 0.5 (d + e)."""
     (a, b, c), (d, e, f) = [[float(v) for v in row] for row in M]
     return (a, b, c + 0.5 - 0.5 * (a + b), d, e, f + 0.5 - 0.5 * (d + e))
+
+
+def _normalize_persps(ys, uvs, persps):
+    """_normalize_warps for convert_perspective / describe_perspective: a homography of frame 0 is nine numbers"""
+    ys, uvs, _ = _normalize_rois(ys, uvs, [])
+    recs = []
+    for q in persps:
+        q = tuple(q)
+        if len(q) == 9:
+            q = (0,) + q
+        if len(q) != 10:
+            raise ValueError(f"a homography is (h0, ..., h8) or (frame, h0, ..., h8), not {q}")
+        recs.append(N.Persp(int(q[0]), (ctypes.c_float * 9)(*[float(v) for v in q[1:]])))
+    return ys, uvs, (N.Persp * max(len(recs), 1))(*recs) if recs else []
+
+
+def describe_perspective(params, frames, persps, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_perspective of this request would launch, as a dict (tsvpp_describe_perspective: describe_warp's keys, mode persp_bilinear) -- host logic
+    only, works without a GPU.  frames: as describe_rois; persps and border as for convert_perspective."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
+    _, _, qs = _normalize_persps([None] * len(recs), [None] * len(recs), persps)
+    fr = (N.NV12 * len(recs))(*recs)
+    by, bu, bv = _border(border)
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    n = len(qs)
+    if spec is None:
+        N.check(N.lib().tsvpp_describe_perspective(ctypes.byref(p), len(recs), fr, n, qs or None, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(N.lib().tsvpp_describe_perspective_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, n, qs or None, by, bu, bv, 1 if aligned_outputs else 0, buf,
+                                                          len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def perspective_from_quad(quad, dst_w, dst_h):
+    """The homography (h0, ..., h8), as float32 values, that maps the corners of a dst_w x dst_h output onto the source points quad = [(x0, y0), (x1, y1), (x2, y2),
+    (x3, y3)] (or eight numbers), top-left, top-right, bottom-right, bottom-left, in luma pixels (tsvpp_persp_from_quad: Heckbert's closed form in double, each
+    entry rounded once).  Whether it is usable -- a convex quad, the horizon off the output -- is convert_perspective's decision."""
+    flat = [float(v) for pt in quad for v in (pt if hasattr(pt, "__len__") else (pt,))]
+    if len(flat) != 8:
+        raise ValueError(f"a quad is four points, not {quad}")
+    q = N.Persp()
+    N.check(N.lib().tsvpp_persp_from_quad((ctypes.c_double * 8)(*flat), int(dst_w), int(dst_h), ctypes.byref(q)))
+    return tuple(q.h)
+
+
+def perspective_from_opencv(M):
+    """OpenCV's index-based inverse matrix [[a, b, c], [d, e, f], [g, h, k]] (output index -> source index: what cv2.warpPerspective takes with WARP_INVERSE_MAP)
+    as this library's centre-based (h0, ..., h8): with k' = k - 0.5 (g + h), rows (a + 0.5 g, b + 0.5 h, c - 0.5 (a + b) + 0.5 k'),
+    (d + 0.5 g, e + 0.5 h, f - 0.5 (d + e) + 0.5 k'), (g, h, k').  With last row (0, 0, 1) this is warp_from_opencv."""
+    (a, b, c), (d, e, f), (g, h, k) = [[float(v) for v in row] for row in M]
+    k2 = k - 0.5 * (g + h)
+    return (a + 0.5 * g, b + 0.5 * h, c - 0.5 * (a + b) + 0.5 * k2, d + 0.5 * g, e + 0.5 * h, f - 0.5 * (d + e) + 0.5 * k2, g, h, k2)
 
 
 def debug_last_launch():

@@ -457,6 +457,80 @@ int tsvpp_persp_from_quad(const double quad[8], int dst_w, int dst_h, tsvpp_pers
  * TSVPP_UNSUPPORTED where the denominator falls below 2^-64 on either grid of the range (the request rules refuse such an output). */
 int tsvpp_persp_footprint(const tsvpp_persp *persp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
 
+/* ---- per-pixel coordinate maps (not in the reference) ----------------------------------------------------------------------------------------------------------
+ * What no matrix describes: the lens.  Undistortion of wide-angle, fisheye and action cameras, stereo rectification, undistort and resize in one pass, cylindrical
+ * and polar unwraps, a stabiliser's mesh warp -- OpenCV's remap.  `n` outputs, each p->dst_width x p->dst_height, each sampled BILINEAR out of one of `n_frames`
+ * NV12 frames through one of `n_maps` coordinate maps in DEVICE memory, colour-converted and stored to its own output, in ceil(n / TSVPP_MAX_REMAPS) kernel
+ * launches (today: a tsvpp_convert of the whole frame to fp32 planar, then a grid sampler over it).
+ *   The map      dst_height rows of dst_width (x, y) pairs, interleaved fp32 (OpenCV's CV_32FC2, a torch tensor (H, W, 2)), rows `pitch` bytes apart.  It is
+ *                OpenCV's: index-based, pixel k centred at k.  Output pixel (row i, column j) samples at fx = map[i][j].x, fy = map[i][j].y with no arithmetic at
+ *                all -- the index space of tsvpp_convert_warp's fx / fy after its - 0.5f.
+ *   Chroma       never derived from the luma taps.  Pair (ci, cj) takes the four luma entries of its 2 x 2 block, x00 x01 / x10 x11 (rows 2 ci, 2 ci + 1, columns
+ *                2 cj, 2 cj + 1), and computes in fp32, contraction off, s = (x00 + x01) + (x10 + x11) -- three additions in that order, each rounded -- then
+ *                cfx = fmaf(s, 0.125f, -0.25f): the block's mean position moved to the pair grid.  cfy likewise from the y entries.
+ *   Any bits     Every bit pattern is a legal coordinate.  Each coordinate is clamped first, c = fminf(fmaxf(f, -1.0f), (float)limit), limit = the frame's width or
+ *                height (chroma: half of it).  fmaxf comes first, so a NaN counts as -1 -- the NaN that +inf + -inf makes in s included.  Everything after the
+ *                clamp works on c.  (For tsvpp_convert_warp this clamp changes no result.)
+ *   Sampling     From c on everything is tsvpp_convert_warp's, word for word: the axis tail, the four taps through the library's bilinear blend, U and V from byte
+ *                columns 2 p and 2 p + 1, the border rule evaluated on c (luma and chroma decide independently; -1, -1, -1 replicates), and the virtual NV12 frame
+ *                of dst_width x dst_height through the one colour back end.
+ *   Identities   The identity map x = j, y = i with dst equal to the frame size is tsvpp_convert without a resize.  A map that holds the BILINEAR coordinates of an
+ *                exact power-of-two ratio (x = 2 j + 0.5, y = 2 i + 0.5 on a frame twice the output) is tsvpp_convert(BILINEAR) at that ratio.  A translation by
+ *                even integers inside the frame is the plain colour conversion of that crop.  A general affine map is NOT bit-identical to tsvpp_convert_warp of
+ *                the same matrix: the chroma coordinate here is the rounded mean of four rounded luma coordinates, there an expression of its own (at
+ *                w / dst = 322 / 70 the two differ by up to 1.5e-5).
+ *   Map memory   is read when the kernel runs -- at launch or at graph replay: the records hold the pointer, not the data, so a captured graph sees map updates.
+ *                The kernel reads no byte outside dst_height rows x 8 * dst_width bytes of each map: pitch padding is never touched.
+ *   LDS hint     A tile stages the bounding box of its taps in LDS, and the kernel finds that box itself (a min / max reduction over the workgroup): the host never
+ *                sees the map and plans nothing per tile.  So it cannot size the launch's LDS either.  Without a hint a launch asks for the context's budget
+ *                (TSVPP_LDS_KB, default 40 KiB, less the kernel's static LDS).  With lds_bytes > 0 on the maps a launch uses it asks for the largest hint among
+ *                them, capped by the budget; a map without a hint counts as the budget.  A tile whose box needs more than the launch has gathers its taps from
+ *                global memory: a wrong hint is never wrong, only slower.  A smooth undistortion map needs 2 - 4 KiB per tile, and the hint restores the
+ *                occupancy a 40 KiB request costs.  tsvpp_remap_lds_need computes it from a host copy of the map.
+ * `frames`, `outs`, `p`, the output layout and everything about the call are tsvpp_convert_warp's: host arrays (maps and remaps too) that may be freed on return;
+ * the per-output records (56 bytes) by value in the kernarg segment, which bounds a launch to TSVPP_MAX_REMAPS; no allocation, no copy, no host synchronisation;
+ * legal while `stream` is being captured; TSVPP_OPT_COLOR_G_TERM and the coefficient block honoured.  Supported: TSVPP_BILINEAR; RGB24 / BGR24 planar and merged,
+ * Y800; uint8 and fp32.
+ * Status, decided before any device is touched (tsvpp_describe_remap returns the same one), in tsvpp_convert_warp's order:
+ *   TSVPP_ERROR        everything tsvpp_convert_warp answers with it except its matrix rule; null `maps` or `remaps`, n_maps <= 0; `map` out of range; a pitch that
+ *                      is non-zero and below 8 * dst_width or no multiple of 8; a negative lds_bytes; when converting: a null plane or output, an `xy` that is
+ *                      null or not 8-byte aligned.
+ *   TSVPP_UNSUPPORTED  odd dst_*, an odd frame size, a resize type other than BILINEAR, an output format outside the list, an output of 4 GiB or more.
+ * Out of scope, follow-ups: NEAREST / BICUBIC sampling, fixed-point (CV_16SC2) and split x / y maps, per-output sizes, merged half-precision tensors. */
+#define TSVPP_MAX_REMAPS 32 /* outputs per launch; more are split */
+typedef struct tsvpp_map {
+    const float *xy;   /* DEVICE memory: dst_height rows of dst_width (x, y) pairs, interleaved fp32; 8-byte aligned */
+    int32_t pitch;     /* bytes per row; 0 = tight (8 * dst_width) */
+    int32_t lds_bytes; /* hint, 0 = none: see "LDS hint" */
+} tsvpp_map;           /* 16 bytes */
+typedef struct tsvpp_remap {
+    int32_t frame; /* index into `frames` */
+    int32_t map;   /* index into `maps` */
+} tsvpp_remap;     /* 8 bytes */
+int tsvpp_convert_remap(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
+                        const tsvpp_params *p, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+/* What tsvpp_convert_remap WOULD launch: tsvpp_describe_warp's line with mode=remap_bilinear, remaps=<n> maps=<n_maps> for warps=, kernel=vpp_remap<OUT,vec|elem,
+ * staged|gather,replicate|border> (tensor form: vpp_remap_tensor<...>) and limit=32.  There is no staged= count: the host cannot know it.  lds= is the first
+ * launch's dynamic LDS, and the kernel is the staged one iff that is non-zero.  `xy` is not read and may be null.  Host only: needs no context and no GPU. */
+int tsvpp_describe_remap(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
+                         int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* The tensor forms: outputs, `spec` and the status rules are tsvpp_convert_rois_tensor's (rule 1 is tsvpp_convert_remap's status; rules 2 and 3 come after it);
+ * the border sample goes through the spec like every sample. */
+int tsvpp_convert_remap_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
+                               const tsvpp_params *p, const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+int tsvpp_describe_remap_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps,
+                                int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* DEBUG ONLY (tests), host only: the source bounding box the kernel computes for output columns [j_first, j_last] / rows [i_first, i_last] (a tile: even first,
+ * odd last) of a map of dst_w x dst_h entries on a frame of frame_w x frame_h, from `host_xy`, a HOST copy of the map (`pitch` bytes per row, 0 = tight):
+ * out8 = { xlo, xhi, ylo, yhi } in luma pixels, then { cxlo, cxhi, cylo, cyhi } in chroma pairs -- floor of the least clamped coordinate .. floor of the largest
+ * + 1, clamped into the frame.  TSVPP_ERROR for null arguments, a size <= 0, an odd size, a bad pitch, a range that is empty or leaves the map. */
+int tsvpp_remap_footprint(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last,
+                          int32_t *out8);
+/* Host only: the largest LDS need (bytes) over all 32 x 32 tiles of a map on a frame_w x frame_h frame, from a HOST copy -- what a caller puts into
+ * tsvpp_map::lds_bytes.  Both tilings count: the plain one and, for 4 k + 2 >= 32 columns, the last tile column shifted to the right edge.  `luma_only`: for Y800
+ * outputs, which stage no chroma.  A negative status for the arguments tsvpp_remap_footprint refuses. */
+int tsvpp_remap_lds_need(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int luma_only);
+
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them
  * per frame, src/Resize.cu:389-406,436-452) and, for UYVY / YUV444 behind a resize, the resized-NV12 scratch of

@@ -294,6 +294,35 @@ int VideoProcessor::ConvertPerspective(AVFrame *const *inputs, int nInputs, cons
     return convertPerspective(true, spec, ctx, isClosed, inputs, nInputs, persps, nPersps, borderY, borderU, borderV, deviceOuts, options, consumerName);
 }
 
+// ConvertRemap and its tensor overload, as convertWarp (`tensor`: tsvpp_convert_remap_tensor with `spec`)
+static int convertRemap(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps,
+                        const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV, void *const *deviceOuts, FrameParameters &options,
+                        const std::string &consumerName) {
+    if (isClosed || !inputs || nInputs <= 0 || !maps || nMaps <= 0 || !remaps || nRemaps <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
+    void *stream = nullptr;
+    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    std::vector<tsvpp_nv12> frames((size_t)nInputs);
+    for (int f = 0; f < nInputs; f++) {
+        const AVFrame *in = inputs[f];
+        if (!in) CHECK_STATUS(VREADER_ERROR);
+        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
+    }
+    const tsvpp_params p = flatten(options); // options.crop must be empty: the maps address the whole frame
+    if (tensor) CHECK_STATUS(tsvpp_convert_remap_tensor(ctx, nInputs, frames.data(), nMaps, maps, nRemaps, remaps, &p, spec, borderY, borderU, borderV, deviceOuts, stream));
+    else CHECK_STATUS(tsvpp_convert_remap(ctx, nInputs, frames.data(), nMaps, maps, nRemaps, remaps, &p, borderY, borderU, borderV, deviceOuts, stream));
+    return VREADER_OK;
+}
+
+int VideoProcessor::ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                                 int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
+    return convertRemap(false, nullptr, ctx, isClosed, inputs, nInputs, maps, nMaps, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+}
+
+int VideoProcessor::ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                                 int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertRemap(true, spec, ctx, isClosed, inputs, nInputs, maps, nMaps, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+}
+
 int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &options, std::string consumerName) {
     if (isClosed || !input || !output) CHECK_STATUS(VREADER_ERROR);
     const tsvpp_params p = flatten(options);

@@ -151,6 +151,13 @@ public:
                            FrameParameters &options, std::string consumerName);
     int ConvertPerspective(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV, void *const *deviceOuts,
                            FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
+    // Per-pixel coordinate maps -- lens undistortion, rectification, unwraps (tsvpp_convert_remap, include/tsvpp.h; not in the reference): output k samples frame
+    // remaps[k].frame BILINEAR where the device-resident map remaps[k].map says, into options' width x height, colour-converted and stored to deviceOuts[k];
+    // on the consumer's stream, status convention as ConvertWarp.  options.crop must be empty.  With a tensor spec: tsvpp_convert_remap_tensor.
+    int ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV,
+                     void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    int ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV,
+                     void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

@@ -246,6 +246,9 @@ tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int 
 int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl);
 // (tsvpp_convert_perspective / tsvpp_describe_perspective) warp_plan's rules in warp_plan's order, then the horizon rule (include/tsvpp.h)
 int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, int border_y, int border_u, int border_v, RoiPlan &pl);
+// (tsvpp_convert_remap / tsvpp_describe_remap) warp_plan's rules in warp_plan's order without the matrix rules, with the maps' (include/tsvpp.h); `xy` is not read
+int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y,
+               int border_u, int border_v, RoiPlan &pl);
 // (the tensor entry points of both paths) the status of a (params, spec) pair whose plan was accepted: rules 2 and 3 of include/tsvpp.h, in that order
 int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec);
 inline size_t tensor_elem_bytes(int dtype) { return dtype == TSVPP_F32 ? 4 : 2; }

@@ -328,6 +328,26 @@ int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, in
     return TSVPP_OK;
 }
 
+int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y,
+               int border_u, int border_v, RoiPlan &pl) {
+    // TSVPP_ERROR: arguments that describe no request at all
+    if (!p || !frames || !maps || !remaps || n_frames <= 0 || n_maps <= 0 || n <= 0) return TSVPP_ERROR;
+    if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
+    for (int i = 0; i < n; i++)
+        if (remaps[i].frame < 0 || remaps[i].frame >= n_frames || remaps[i].map < 0 || remaps[i].map >= n_maps) return TSVPP_ERROR;
+    const bool replicate = border_y == -1 && border_u == -1 && border_v == -1;
+    if (!replicate && (border_y < 0 || border_y > 255 || border_u < 0 || border_u > 255 || border_v < 0 || border_v > 255)) return TSVPP_ERROR;
+    for (int m = 0; m < n_maps; m++) {
+        if (maps[m].pitch != 0 && ((long)maps[m].pitch < 8L * p->dst_width || (maps[m].pitch & 7))) return TSVPP_ERROR;
+        if (maps[m].pitch == 0 && 8L * p->dst_width > 0x7fffffffL) return TSVPP_ERROR; // (the tight pitch travels in 32 bits)
+        if (maps[m].lds_bytes < 0) return TSVPP_ERROR;
+    }
+    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
+    if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    if (tile_output_plan(p, false, TSVPP_MAX_REMAPS, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
+    return TSVPP_OK;
+}
+
 // One spec check for both tensor paths.  The caller has the plan's status already (it wins); what is left is about the spec and about what the tensor stores cover.
 int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec) {
     if (!p || !spec) return TSVPP_ERROR;

@@ -1,0 +1,220 @@
+// tsvpp_remap.cpp -- per-pixel coordinate maps (include/tsvpp.h): tsvpp_convert_remap / tsvpp_describe_remap, their tensor forms (`spec`, null for the first pair;
+// kernel vpp_remap_tensor.hip) and the two host-only functions on a HOST copy of a map, tsvpp_remap_footprint and tsvpp_remap_lds_need; TSVPP_MAX_REMAPS outputs
+// per launch, kernel vpp_remap.hip.  The launch fields and the convert skeleton are tsvpp_tiles.h's; RemapPath below says what differs: the request rules
+// (remap_plan, tsvpp_plan.cpp), the record, and the LDS of a launch -- the maps live in device memory, so there is NO per-tile loop on the convert path: the launch
+// asks for the budget or for the caller's hint, and every workgroup finds its own footprint.
+#include <climits>
+#include <cmath>
+
+#include "tsvpp_tiles.h"
+#include "vpp_remap.h"
+
+using namespace tsvpp;
+
+namespace {
+
+// The request of one call, as tsvpp_tiles.h asks for it
+struct RemapPath {
+    using Launch = RemapLaunch;
+    static constexpr bool kOwnBudget = true;
+    bool tensor;
+    const tsvpp_params *p;
+    const tsvpp_tensor_spec *spec;
+    int n_frames;
+    const tsvpp_nv12 *frames; // (may carry null planes: the describe calls)
+    int n_maps;
+    const tsvpp_map *maps;    // (may carry null xy: the describe calls)
+    int n;
+    const tsvpp_remap *remaps;
+    int border_y, border_u, border_v;
+
+    bool border() const { return border_y >= 0; }
+    int plan(RoiPlan &pl) const { return remap_plan(p, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v, pl); }
+    int items() const { return n; }
+    int limit(const RoiPlan &) const { return (int)TSVPP_MAX_REMAPS; }
+    // (leaves the launch's hint in L.lds_bytes -- the largest over the maps it uses, INT_MAX for a map without one -- for stage_budget, which tile_fill calls next)
+    void fill_items(const RoiPlan &pl, void *const *outs, int base, int cnt, RemapLaunch &L) const {
+        L.n_remaps = cnt;
+        L.border_y = (float)border_y;
+        L.border_u = (float)border_u;
+        L.border_v = (float)border_v;
+        int hint = 0;
+        for (int i = 0; i < cnt; i++) {
+            const tsvpp_remap &q = remaps[base + i];
+            const tsvpp_nv12 &fr = frames[q.frame];
+            const tsvpp_map &m = maps[q.map];
+            RemapRec &r = L.r[i];
+            r.y = (uint64_t)(uintptr_t)fr.y;
+            r.uv = (uint64_t)(uintptr_t)fr.uv;
+            r.out = outs ? (uint64_t)(uintptr_t)outs[base + i] : 0;
+            r.xy = (uint64_t)(uintptr_t)m.xy;
+            r.pitch_y = pitch_or_width(fr.pitch_y, fr.width);
+            r.pitch_uv = pitch_or_width(fr.pitch_uv, fr.width);
+            r.src_w = fr.width;
+            r.src_h = fr.height;
+            r.map_pitch = m.pitch ? m.pitch : 8 * pl.dst_w;
+            r.pad_ = 0;
+            hint = std::max(hint, m.lds_bytes > 0 ? m.lds_bytes : INT_MAX);
+        }
+        L.lds_bytes = hint;
+    }
+    // The launch's dynamic LDS: the hint, capped by what the workgroup's budget leaves behind the reduction's words.  The kernel decides per tile
+    // (need <= L.lds_bytes).  Returns the outputs that MAY stage: all of the launch or none
+    int stage_budget(const RoiPlan &, RemapLaunch &L, int budget, bool) const {
+        budget -= REMAP_REDUCE_LDS;
+        L.lds_bytes = budget > 0 ? std::min(L.lds_bytes, budget) : 0;
+        return L.lds_bytes > 0 ? L.n_remaps : 0;
+    }
+    int front_lds(const RemapLaunch &) const { return 0; }
+    // (vpp_remap.hip and its tensor twin) one launch group, or only its kernel's name
+    hipError_t launch(const RoiPlan &pl, bool vec, bool, const RemapLaunch &L, hipStream_t stream, char *name, size_t name_len, bool dry_run) const {
+        const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n_remaps);
+        return (tensor ? launch_remap_tensor : launch_remap)(pl.out, vec, L.lds_bytes > 0, border(), L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
+    }
+    void label(char *buf, size_t len, const RoiPlan &pl, void *stream) const {
+        std::snprintf(buf, len, "tsvpp_convert_remap%s n=%d maps=%d frames=%d ->%dx%d fourcc=%d stream=%p", tensor ? "_tensor" : "", n, n_maps, n_frames, pl.dst_w, pl.dst_h, p->fourcc, stream);
+    }
+};
+
+// tile_convert behind the one rule it does not know: a map the kernel can address
+int remap_convert(const RemapPath &path, tsvpp_ctx *ctx, void *const *outs, void *stream) {
+    RoiPlan pl;
+    const int sts = tile_request(path, pl);
+    if (sts == TSVPP_OK) {
+        for (int m = 0; m < path.n_maps; m++)
+            if (!path.maps[m].xy || ((uintptr_t)path.maps[m].xy & 7)) {
+                clear_last_launch();
+                return TSVPP_ERROR;
+            }
+    }
+    return tile_convert(path, ctx, outs, stream);
+}
+
+// tile_describe's line without staged= (the host cannot count what it cannot see) and with lds= the dynamic LDS alone: non-zero iff the kernel is the staged one
+int remap_describe(RemapPath path, int aligned_outputs, char *buf, size_t buf_len) {
+    if (!buf || buf_len == 0) return TSVPP_ERROR;
+    buf[0] = 0;
+    RoiPlan pl;
+    const int sts = tile_request(path, pl);
+    if (sts != TSVPP_OK) return sts;
+    Knobs kn; // no context: no device, no streams
+    read_env_knobs(kn);
+    const bool vec = aligned_outputs != 0 && !narrow_tail(pl);
+    int lds0 = 0, grid0 = 0, launches = 0;
+    char kname[128] = "(none)", border[40] = "replicate";
+    RemapLaunch L;
+    const int limit = path.limit(pl);
+    for (int base = 0; base < path.n; base += limit, launches++) {
+        const int cnt = std::min(path.n - base, limit);
+        (void)tile_fill(path, kn, pl, nullptr, base, cnt, vec, L);
+        if (base == 0) {
+            lds0 = L.lds_bytes;
+            grid0 = L.tiles_x * L.tiles_y * cnt;
+            const hipError_t e = path.launch(pl, vec, lds0 > 0, L, nullptr, kname, sizeof(kname), true);
+            if (e != hipSuccess) return (int)e;
+        }
+    }
+    if (path.border()) std::snprintf(border, sizeof(border), "%d,%d,%d", path.border_y, path.border_u, path.border_v);
+    std::snprintf(buf, buf_len, "mode=remap_bilinear out=%s dst=%dx%d remaps=%d maps=%d frames=%d launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d tail=%d nt=%d limit=%d border=%s",
+                  path.tensor ? tensor_out_name(path.spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w, pl.dst_h, path.n, path.n_maps, path.n_frames, launches,
+                  kname, ROI_TX, ROI_TY, lds0, grid0, L.tiles_x, L.tiles_y, L.last_col0 > 0 ? 2 : 0, L.nt_stores, limit, border);
+    return TSVPP_OK;
+}
+
+// ---- a HOST copy of a map ----
+struct HostMap {
+    const uint8_t *xy;
+    long pitch;
+    int dst_w, dst_h, frame_w, frame_h;
+    float x(int i, int j) const { return ((const float *)(xy + i * pitch))[2 * j]; }
+    float y(int i, int j) const { return ((const float *)(xy + i * pitch))[2 * j + 1]; }
+};
+int host_map(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, HostMap &m) {
+    if (!host_xy || dst_w <= 0 || dst_h <= 0 || frame_w <= 0 || frame_h <= 0 || ((dst_w | dst_h | frame_w | frame_h) & 1)) return TSVPP_ERROR;
+    if (pitch != 0 && ((long)pitch < 8L * dst_w || (pitch & 7))) return TSVPP_ERROR;
+    m = HostMap{ (const uint8_t *)host_xy, pitch ? (long)pitch : 8L * dst_w, dst_w, dst_h, frame_w, frame_h };
+    return TSVPP_OK;
+}
+// The footprint of output columns [j0, j1] / rows [i0, i1] (even first, odd last): the extremes the workgroup reduces, accumulated in a loop, through THE
+// footprint function
+void host_footprint(const HostMap &m, int j0, int j1, int i0, int i1, RoiFootprint &f) {
+    const float inf = INFINITY;
+    RemapExtremes e = { inf, -inf, inf, -inf, inf, -inf, inf, -inf };
+    for (int i = i0; i <= i1; i++)
+        for (int j = j0; j <= j1; j++) {
+            const float cx = remap_clamp(m.x(i, j), m.frame_w), cy = remap_clamp(m.y(i, j), m.frame_h);
+            e.x_lo = fminf(e.x_lo, cx);
+            e.x_hi = fmaxf(e.x_hi, cx);
+            e.y_lo = fminf(e.y_lo, cy);
+            e.y_hi = fmaxf(e.y_hi, cy);
+        }
+    for (int ci = i0 >> 1; ci <= i1 >> 1; ci++)
+        for (int cj = j0 >> 1; cj <= j1 >> 1; cj++) {
+            const int i = 2 * ci, j = 2 * cj;
+            const float cx = remap_clamp(remap_chroma(m.x(i, j), m.x(i, j + 1), m.x(i + 1, j), m.x(i + 1, j + 1)), m.frame_w >> 1);
+            const float cy = remap_clamp(remap_chroma(m.y(i, j), m.y(i, j + 1), m.y(i + 1, j), m.y(i + 1, j + 1)), m.frame_h >> 1);
+            e.cx_lo = fminf(e.cx_lo, cx);
+            e.cx_hi = fmaxf(e.cx_hi, cx);
+            e.cy_lo = fminf(e.cy_lo, cy);
+            e.cy_hi = fmaxf(e.cy_hi, cy);
+        }
+    remap_footprint(e, m.frame_w, m.frame_h, f);
+}
+
+} // namespace
+
+extern "C" {
+
+int tsvpp_convert_remap(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
+                        const tsvpp_params *p, int border_y, int border_u, int border_v, void *const *outs, void *stream) {
+    return remap_convert(RemapPath{ false, p, nullptr, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, ctx, outs, stream);
+}
+
+int tsvpp_describe_remap(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
+                         int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
+    return remap_describe(RemapPath{ false, p, nullptr, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+}
+
+int tsvpp_convert_remap_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
+                               const tsvpp_params *p, const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream) {
+    return remap_convert(RemapPath{ true, p, spec, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, ctx, outs, stream);
+}
+
+int tsvpp_describe_remap_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps,
+                                int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
+    return remap_describe(RemapPath{ true, p, spec, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+}
+
+int tsvpp_remap_footprint(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last,
+                          int32_t *out8) {
+    HostMap m;
+    if (!out8 || host_map(host_xy, pitch, dst_w, dst_h, frame_w, frame_h, m) != TSVPP_OK) return TSVPP_ERROR;
+    if (j_first < 0 || i_first < 0 || j_last < j_first || i_last < i_first || j_last >= dst_w || i_last >= dst_h) return TSVPP_ERROR;
+    if ((j_first & 1) || (i_first & 1) || !(j_last & 1) || !(i_last & 1)) return TSVPP_ERROR; // whole pairs: even first, odd last
+    RoiFootprint f;
+    host_footprint(m, j_first, j_last, i_first, i_last, f);
+    const int32_t v[8] = { f.xlo, f.xhi, f.ylo, f.yhi, f.cxlo, f.cxhi, f.cylo, f.cyhi };
+    for (int k = 0; k < 8; k++) out8[k] = v[k];
+    return TSVPP_OK;
+}
+
+int tsvpp_remap_lds_need(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int luma_only) {
+    HostMap m;
+    if (host_map(host_xy, pitch, dst_w, dst_h, frame_w, frame_h, m) != TSVPP_OK) return TSVPP_ERROR;
+    const int tiles_x = (dst_w + ROI_TILE_W - 1) / ROI_TILE_W, tiles_y = (dst_h + ROI_TILE_H - 1) / ROI_TILE_H;
+    const int shifted = ((dst_w & 3) != 0 && dst_w >= ROI_TILE_W) ? dst_w - ROI_TILE_W : 0; // the vector flavour's last tile column (tile_fill, tsvpp_tiles.h)
+    int need = 0;
+    for (int ty = 0; ty < tiles_y; ty++)
+        for (int tx = 0; tx < tiles_x + (shifted ? 1 : 0); tx++) {
+            const int j0 = tx < tiles_x ? tx * ROI_TILE_W : shifted, i0 = ty * ROI_TILE_H;
+            RoiFootprint f;
+            host_footprint(m, j0, tile_last(j0, ROI_TILE_W, dst_w), i0, tile_last(i0, ROI_TILE_H, dst_h), f);
+            // (in 64 bits: a tile that folds a huge frame into itself)
+            const long ny = f.yhi - f.ylo + 1, nuv = luma_only ? 0 : f.cyhi - f.cylo + 1;
+            const long bytes = 16L * (ny * roi_chunks(f.xhi - f.xlo + 1) + nuv * roi_chunks(2 * (f.cxhi - f.cxlo + 1)));
+            need = (int)std::max((long)need, std::min(bytes, (long)INT_MAX));
+        }
+    return need;
+}
+
+} // extern "C"

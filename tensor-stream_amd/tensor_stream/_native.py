@@ -14,6 +14,7 @@ TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
 TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
 TSVPP_MAX_WARPS = 32  # outputs per launch of tsvpp_convert_warp
 TSVPP_MAX_PERSP = 32  # outputs per launch of tsvpp_convert_perspective
+TSVPP_MAX_REMAPS = 32  # outputs per launch of tsvpp_convert_remap
 TSVPP_F32, TSVPP_F16, TSVPP_BF16 = 0, 1, 2  # enum tsvpp_dtype: the element of the tensor entry points
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
@@ -57,6 +58,16 @@ class Persp(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_int32), ("h", ctypes.c_float * 9)]
 
 
+class Map(ctypes.Structure):
+    """struct tsvpp_map: one coordinate map of tsvpp_convert_remap in DEVICE memory -- (x, y) fp32 pairs, row pitch in bytes (0: tight), LDS hint (0: none)."""
+    _fields_ = [("xy", ctypes.c_void_p), ("pitch", ctypes.c_int32), ("lds_bytes", ctypes.c_int32)]
+
+
+class Remap(ctypes.Structure):
+    """struct tsvpp_remap: one output of tsvpp_convert_remap -- the frame it samples and the map it samples it through."""
+    _fields_ = [("frame", ctypes.c_int32), ("map", ctypes.c_int32)]
+
+
 class TensorSpec(ctypes.Structure):
     """struct tsvpp_tensor_spec: element type, per-channel mean and scale (= 1 / std) of the tensor entry points."""
     _fields_ = [("dtype", ctypes.c_int32), ("mean", ctypes.c_float * 3), ("scale", ctypes.c_float * 3)]
@@ -77,7 +88,8 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor",
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
            "tsvpp_convert_perspective", "tsvpp_describe_perspective", "tsvpp_convert_perspective_tensor", "tsvpp_describe_perspective_tensor", "tsvpp_persp_from_quad",
-           "tsvpp_persp_footprint"]
+           "tsvpp_persp_footprint",
+           "tsvpp_convert_remap", "tsvpp_describe_remap", "tsvpp_convert_remap_tensor", "tsvpp_describe_remap_tensor", "tsvpp_remap_footprint", "tsvpp_remap_lds_need"]
 
 _lib = None
 
@@ -183,6 +195,19 @@ def lib():
     L.tsvpp_persp_from_quad.restype = i32
     L.tsvpp_persp_footprint.argtypes = [pq, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
     L.tsvpp_persp_footprint.restype = i32
+    pm, pr, pf = ctypes.POINTER(Map), ctypes.POINTER(Remap), ctypes.POINTER(ctypes.c_float)
+    L.tsvpp_convert_remap.argtypes = [vp, i32, pn, i32, pm, i32, pr, pp, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_remap.restype = i32
+    L.tsvpp_describe_remap.argtypes = [pp, i32, pn, i32, pm, i32, pr, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_remap.restype = i32
+    L.tsvpp_convert_remap_tensor.argtypes = [vp, i32, pn, i32, pm, i32, pr, pp, ps, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_remap_tensor.restype = i32
+    L.tsvpp_describe_remap_tensor.argtypes = [pp, ps, i32, pn, i32, pm, i32, pr, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_remap_tensor.restype = i32
+    L.tsvpp_remap_footprint.argtypes = [pf, i32, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
+    L.tsvpp_remap_footprint.restype = i32
+    L.tsvpp_remap_lds_need.argtypes = [pf, i32, i32, i32, i32, i32, i32]
+    L.tsvpp_remap_lds_need.restype = i32
     L.tsvpp_debug_area_tables.argtypes = [vp]
     L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

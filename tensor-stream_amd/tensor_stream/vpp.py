@@ -357,6 +357,34 @@ class VideoProcessor:
             N.check(self._lib.tsvpp_convert_warp_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv, outs, stream))
         return out
 
+    def convert_remap(self, ys, uvs, maps, params, remaps=None, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """Per-pixel coordinate maps -- lens undistortion, rectification, unwraps, mesh warps (tsvpp_convert_remap): every output samples one frame BILINEAR where
+        one map says, into params' width x height, colour-converted and stored to its own output, one launch per 32 outputs.  ys / uvs: as convert_rois (one frame
+        as a pair of planes, or lists; the frames may differ in size and pitch).  maps: one CUDA float32 tensor (height, width, 2) of (x, y) source positions --
+        OpenCV's remap convention, pixel k centred at k (remap_from_opencv, remap_from_grid make them) -- or a list of them; the last dimension is contiguous, a
+        row stride of >= 2 * width elements becomes the pitch; each may be paired as (tensor, lds_bytes) with the hint of remap_lds_hint.  The tensors are read
+        when the kernel runs: keep them alive, and a captured graph sees their updates.  remaps: a list of (frame, map); None with one map sends every frame
+        through it in order, None with as many maps as frames pairs them up.  border, out, width, height, dtype / mean / std and the result: as convert_warp."""
+        spec = tensor_spec(dtype, mean, std)
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        ys, uvs, _ = _normalize_rois(ys, uvs, [])
+        recs_m = _normalize_maps(maps, p.dst_width, p.dst_height, self.device)
+        recs = _normalize_remaps(remaps, len(ys), len(recs_m))
+        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
+        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
+        n = len(recs)
+        if out is None:
+            out = self._alloc_items(p, n, spec, "convert_remap needs an even, positive output size")
+        by, bu, bv = _border(border)
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if spec is None:
+            N.check(self._lib.tsvpp_convert_remap(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
+        else:
+            N.check(self._lib.tsvpp_convert_remap_tensor(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv,
+                                                         outs, stream))
+        return out
+
     def convert_perspective(self, ys, uvs, persps, params, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """Homography-warped outputs (tsvpp_convert_perspective): every entry of `persps` samples its frame BILINEAR through its own 3 x 3 output -> source
         homography into params' width x height, colour-converted and stored to its own output, one launch per 32 outputs.  ys / uvs, border, out, width, height,
@@ -693,6 +721,121 @@ def perspective_from_opencv(M):
     (a, b, c), (d, e, f), (g, h, k) = [[float(v) for v in row] for row in M]
     k2 = k - 0.5 * (g + h)
     return (a + 0.5 * g, b + 0.5 * h, c - 0.5 * (a + b) + 0.5 * k2, d + 0.5 * g, e + 0.5 * h, f - 0.5 * (d + e) + 0.5 * k2, g, h, k2)
+
+
+def _normalize_maps(maps, dst_w, dst_h, device=None):
+    """The maps argument of convert_remap / describe_remap as an array of tsvpp_map.  A map is a CUDA float32 tensor (dst_h, dst_w, 2) whose last dimension is
+    contiguous (device given: convert_remap), optionally paired as (tensor, lds_bytes); without a device (describe_remap) it may also be (pitch, lds_bytes)
+    integers.  Anything else raises ValueError: nothing reaches the C call."""
+    if isinstance(maps, torch.Tensor) or (isinstance(maps, tuple) and len(maps) == 2 and not isinstance(maps[1], (torch.Tensor, tuple, list))):
+        maps = [maps]
+    recs = []
+    for m in maps:
+        hint = 0
+        if isinstance(m, (tuple, list)):
+            if len(m) != 2:
+                raise ValueError(f"a map is a tensor, (tensor, lds_bytes) or (pitch, lds_bytes), not {m}")
+            m, hint = m[0], int(m[1])
+        if not isinstance(m, torch.Tensor):
+            if device is not None:
+                raise ValueError(f"convert_remap needs its maps as tensors, not {type(m).__name__}")
+            recs.append(N.Map(None, int(m), hint))
+            continue
+        if m.dtype != torch.float32:
+            raise ValueError(f"a map is a float32 tensor, not {m.dtype}")
+        if m.dim() != 3 or tuple(m.shape) != (dst_h, dst_w, 2):
+            raise ValueError(f"a map for a {dst_w} x {dst_h} output has shape ({dst_h}, {dst_w}, 2), not {tuple(m.shape)}")
+        if m.stride(2) != 1 or m.stride(1) != 2 or m.stride(0) < 2 * dst_w:
+            raise ValueError(f"a map's last two dimensions are contiguous and its row stride is at least {2 * dst_w} elements: strides {tuple(m.stride())}")
+        if device is not None and (not m.is_cuda or m.device.index != device):
+            raise ValueError(f"a map lives on cuda:{device}, not on {m.device}")
+        recs.append(N.Map(m.data_ptr() if m.is_cuda else None, 4 * m.stride(0), hint))
+    if not recs:
+        raise ValueError("at least one map is needed")
+    return (N.Map * len(recs))(*recs)
+
+
+def _normalize_remaps(remaps, n_frames, n_maps):
+    """The remaps argument of convert_remap / describe_remap as an array of tsvpp_remap: (frame, map) pairs; None with one map sends every frame through it in
+    order, None with as many maps as frames pairs them up."""
+    if remaps is None:
+        if n_maps == 1:
+            remaps = [(f, 0) for f in range(n_frames)]
+        elif n_maps == n_frames:
+            remaps = [(f, f) for f in range(n_frames)]
+        else:
+            raise ValueError(f"{n_frames} frames and {n_maps} maps do not pair up: say which with remaps=[(frame, map), ...]")
+    pairs = []
+    for r in remaps:
+        r = tuple(int(v) for v in r)
+        if len(r) != 2:
+            raise ValueError(f"a remap is (frame, map), not {r}")
+        pairs.append(r)
+    if not pairs:
+        raise ValueError("at least one (frame, map) is needed")
+    return (N.Remap * len(pairs))(*[N.Remap(*r) for r in pairs])
+
+
+def describe_remap(params, frames, maps, remaps=None, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_remap of this request would launch, as a dict (tsvpp_describe_remap: describe_warp's keys with remaps= and maps= for warps= and without
+    staged=, which the host cannot know; lds is the launch's dynamic LDS) -- host logic only, works without a GPU.  frames: as describe_rois; maps: as for
+    convert_remap (tensors on any device: only strides and hints are read) or (pitch, lds_bytes) integers; remaps and border as for convert_remap."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
+    ms = _normalize_maps(maps, p.dst_width, p.dst_height)
+    rs = _normalize_remaps(remaps, len(recs), len(ms))
+    fr = (N.NV12 * len(recs))(*recs)
+    by, bu, bv = _border(border)
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    if spec is None:
+        N.check(N.lib().tsvpp_describe_remap(ctypes.byref(p), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(N.lib().tsvpp_describe_remap_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv,
+                                                    1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def remap_from_opencv(map_x, map_y):
+    """OpenCV's pair of (H, W) maps (what cv2.initUndistortRectifyMap returns as CV_32FC1, what cv2.remap takes) as one (H, W, 2) float32 map of convert_remap:
+    [..., 0] = x, [..., 1] = y.  OpenCV's convention is the contract's -- no arithmetic.  numpy arrays give a numpy array, tensors a tensor on their device."""
+    if isinstance(map_x, torch.Tensor) or isinstance(map_y, torch.Tensor):
+        map_x, map_y = torch.as_tensor(map_x), torch.as_tensor(map_y)
+        if map_x.dim() != 2 or map_x.shape != map_y.shape:
+            raise ValueError(f"map_x and map_y are (H, W) and alike, not {tuple(map_x.shape)} and {tuple(map_y.shape)}")
+        return torch.stack((map_x.to(torch.float32), map_y.to(device=map_x.device, dtype=torch.float32)), dim=-1).contiguous()
+    map_x, map_y = np.asarray(map_x, dtype=np.float32), np.asarray(map_y, dtype=np.float32)
+    if map_x.ndim != 2 or map_x.shape != map_y.shape:
+        raise ValueError(f"map_x and map_y are (H, W) and alike, not {map_x.shape} and {map_y.shape}")
+    return np.ascontiguousarray(np.stack((map_x, map_y), axis=-1))
+
+
+def remap_from_grid(grid, w, h):
+    """A torch.nn.functional.grid_sample grid (H, W, 2) with align_corners=False, for a source of w x h pixels, as a map of convert_remap, in fp32 and in this
+    operation order: x = ((gx + 1) * w - 1) * 0.5, y = ((gy + 1) * h - 1) * 0.5.  numpy arrays give a numpy array, tensors a tensor on their device."""
+    if isinstance(grid, torch.Tensor):
+        g = grid.to(torch.float32)
+        if g.dim() != 3 or g.shape[2] != 2:
+            raise ValueError(f"a grid is (H, W, 2), not {tuple(g.shape)}")
+        return torch.stack((((g[..., 0] + 1.0) * float(w) - 1.0) * 0.5, ((g[..., 1] + 1.0) * float(h) - 1.0) * 0.5), dim=-1).contiguous()
+    g = np.asarray(grid, dtype=np.float32)
+    if g.ndim != 3 or g.shape[2] != 2:
+        raise ValueError(f"a grid is (H, W, 2), not {g.shape}")
+    one, half = np.float32(1.0), np.float32(0.5)
+    return np.ascontiguousarray(np.stack((((g[..., 0] + one) * np.float32(w) - one) * half, ((g[..., 1] + one) * np.float32(h) - one) * half), axis=-1))
+
+
+def remap_lds_hint(map, frame_w, frame_h, luma_only=False):
+    """The LDS hint of a map on a frame_w x frame_h frame (tsvpp_remap_lds_need): the largest staging need, in bytes, over all of its 32 x 32 tiles -- what
+    convert_remap takes as (tensor, lds_bytes).  Copies the map to the host once; luma_only: for Y800 outputs.  map: a tensor or array (H, W, 2) float32."""
+    host = map.detach().cpu().numpy() if isinstance(map, torch.Tensor) else np.asarray(map)
+    if host.dtype != np.float32 or host.ndim != 3 or host.shape[2] != 2:
+        raise ValueError(f"a map is float32 (H, W, 2), not {host.dtype} {host.shape}")
+    host = np.ascontiguousarray(host)
+    need = N.lib().tsvpp_remap_lds_need(host.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), 0, host.shape[1], host.shape[0], int(frame_w), int(frame_h), 1 if luma_only else 0)
+    if need < 0:
+        N.check(need)
+    return need
 
 
 def debug_last_launch():

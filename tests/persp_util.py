@@ -1,6 +1,7 @@
 """Shared by the perspective tests (tsvpp_convert_perspective): a numpy restatement of the contract of include/tsvpp.h on top of tests/warp_util.py -- the host
 terms, the coordinate with its one reciprocal, the VIRTUAL NV12 frame of dst_w x dst_h and the taps of every sample.  All arithmetic is np.float32, one rounding
-per operation (numpy's float32 division and product are IEEE, correctly rounded); the fused multiply-adds are warp_util.fma32.  Contains no product code."""
+per operation (numpy's float32 division and product are IEEE, correctly rounded); the fused multiply-adds are warp_util.fma32.  Contains no product code.
+Its judge is tests/sampler64.py: an independent float64 evaluation of the header's prose, whose bracket this model must stay inside (tests/test_sampler64_cpu.py)."""
 import numpy as np
 
 import warp_util as W

@@ -1,7 +1,8 @@
 """Shared by the remap tests (tsvpp_convert_remap): a numpy restatement of the contract of include/tsvpp.h that makes the VIRTUAL NV12 frame of dst_w x dst_h -- the
 samples before the colour back end -- and the expected output, which is the existing oracle's conversion without a resize of that virtual frame; and generators
 for the map set the tests use.  From the clamped coordinate on everything is tests/warp_util.py's (axis, bilerp, outside); the chroma coordinate's fused
-multiply-add is its fma32.  All arithmetic is np.float32, one rounding per operation.  Contains no product code."""
+multiply-add is its fma32.  All arithmetic is np.float32, one rounding per operation.  Contains no product code.
+Its judge is tests/sampler64.py: an independent float64 evaluation of the header's prose, whose bracket this model must stay inside (tests/test_sampler64_cpu.py)."""
 import numpy as np
 
 from warp_util import F32, axis, bilerp, fma32, outside

@@ -1,6 +1,7 @@
 """Shared by the warp tests (tsvpp_convert_warp): a numpy restatement of the contract of include/tsvpp.h that makes the VIRTUAL NV12 frame of dst_w x dst_h -- the
 samples before the colour back end -- and the expected output, which is the existing oracle's conversion without a resize of that virtual frame.  All arithmetic
-is np.float32, one rounding per operation; the contract's fused multiply-adds are fma32 below.  Contains no product code."""
+is np.float32, one rounding per operation; the contract's fused multiply-adds are fma32 below.  Contains no product code.
+Its judge is tests/sampler64.py: an independent float64 evaluation of the header's prose, whose bracket this model must stay inside (tests/test_sampler64_cpu.py)."""
 from fractions import Fraction
 
 import numpy as np

@@ -531,6 +531,67 @@ int tsvpp_remap_footprint(const float *host_xy, int pitch, int dst_w, int dst_h,
  * outputs, which stage no chroma.  A negative status for the arguments tsvpp_remap_footprint refuses. */
 int tsvpp_remap_lds_need(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int luma_only);
 
+/* ---- sparse control-grid warps: the warp mesh (not in the reference) ---------------------------------------------------------------------------------------------
+ * The maps people use are smooth: undistortion, rectification, cylindrical unwraps, a stabiliser's per-frame mesh, rolling-shutter correction are described to a
+ * few hundredths of a pixel by one control point per 16 x 16 or 32 x 32 output pixels -- the form every vendor dewarper takes.  A dense map is the largest thing
+ * tsvpp_convert_remap reads (16.6 MB at 1080p, to produce and upload per frame for a stabiliser); the same warp as a 16 x 16 mesh is 67 KB.  tsvpp_convert_mesh is
+ * tsvpp_convert_remap with the coordinate COMPUTED from four control points instead of read, and that computation is a contract:
+ *   Control grid cols = ((dst_width - 1) >> log2_cw) + 2 points per row, rows = ((dst_height - 1) >> log2_ch) + 2 rows (tsvpp_mesh_dims), (x, y) interleaved fp32,
+ *                rows `pitch` bytes apart, in DEVICE memory.  Control point (r, c) is the source position -- index-based, as a dense map's entry -- of output
+ *                pixel (row r << log2_ch, column c << log2_cw).  The last row and column may lie beyond the output.
+ *   Coordinate   of output pixel (row i, column j), per component, in fp32 with contraction off: c = j >> log2_cw, tx = (float)(j & (cw - 1)) * (1.0f / cw) with
+ *                cw = 1 << log2_cw (exact); r and ty likewise from i.  With A = P[r][c], B = P[r][c + 1], C = P[r + 1][c], D = P[r + 1][c + 1]:
+ *                    top = fmaf(tx, B - A, A)      bot = fmaf(tx, D - C, C)      f = fmaf(ty, bot - top, top)
+ *                three subtractions and three fused multiply-adds, each rounded once.  At a control point f is the control value itself.
+ *   From f on    the dense call, word for word: E(mesh), the dst_height x dst_width map of these f, is a tsvpp_map, and the result is, bit for bit,
+ *                tsvpp_convert_remap of E(mesh).  The chroma coordinate of a pair comes from the four UNCLAMPED f of its 2 x 2 block; the clamp ("any bits": a NaN,
+ *                the one inf - inf makes here included, counts as -1), the sampler, the border rule, the colour back end, the staging decision per tile (the
+ *                footprint is reduced from the tile's own clamped coordinates: tsvpp_remap_footprint of E(mesh) describes it) and the LDS hint are that call's.
+ *   Identities   hold because the interpolation of such control points is exact: the identity mesh x = j, y = i with dst equal to the frame is tsvpp_convert
+ *                without a resize; the mesh of x = 2 j + 0.5, y = 2 i + 0.5 is tsvpp_convert(BILINEAR) at 2 : 1; a translation by even integers is the crop.
+ *   Mesh memory  is read when the kernel runs (a captured graph sees mesh updates); no byte outside rows x 8 * cols bytes of a mesh is read: pitch padding is
+ *                never touched.
+ * Everything about the call is tsvpp_convert_remap's: `remaps` pairs a frame with a mesh (`map` indexes `meshes`); host arrays that may be freed on return; the
+ * per-output records (64 bytes, a record type of this call's own) by value in the kernarg segment, ceil(n / TSVPP_MAX_MESHES) launches; no allocation, no copy,
+ * no host synchronisation; legal under stream capture; the same formats, border, TSVPP_OPT_COLOR_G_TERM and coefficient block.
+ * Status, in tsvpp_convert_remap's order with the mesh rules where its map rules are:
+ *   TSVPP_ERROR        what tsvpp_convert_remap answers with it for frames, remaps, sizes and border; null `meshes`, n_meshes <= 0; `map` out of range; a pitch that
+ *                      is no multiple of 8 or -- for a cell size inside 2..8 -- non-zero and below 8 * cols; a negative lds_bytes; when converting: a null
+ *                      plane or output, an `xy` that is null or not 8-byte aligned.
+ *   TSVPP_UNSUPPORTED  what tsvpp_convert_remap answers with it; a log2_cw or log2_ch outside 2..8.
+ * Out of scope: cell sizes that are no power of two, bicubic or spline interpolation of the control points, NEAREST / BICUBIC sampling, per-output sizes. */
+#define TSVPP_MAX_MESHES 32 /* outputs per launch; more are split */
+typedef struct tsvpp_mesh {
+    const float *xy;          /* DEVICE memory: rows x cols control points, (x, y) interleaved fp32, 8-byte aligned */
+    int32_t pitch;            /* bytes per control row; 0 = tight (8 * cols) */
+    int32_t log2_cw, log2_ch; /* cell size in output pixels: 2..8 each (4 .. 256 pixels) */
+    int32_t lds_bytes;        /* hint, as tsvpp_map's */
+} tsvpp_mesh;                 /* 24 bytes */
+int tsvpp_convert_mesh(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
+                       const tsvpp_params *p, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+/* What tsvpp_convert_mesh WOULD launch: tsvpp_describe_remap's line with mode=mesh_bilinear, meshes=<n_meshes> cell=<W>x<H> (the first mesh's cell) for maps=,
+ * kernel=vpp_mesh<OUT,vec|elem,staged|gather,replicate|border> (tensor form: vpp_mesh_tensor<...>) and limit=32.  `xy` is not read.  Host only. */
+int tsvpp_describe_mesh(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
+                        int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* The tensor forms, under the rules of tsvpp_convert_remap_tensor. */
+int tsvpp_convert_mesh_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
+                              const tsvpp_params *p, const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+int tsvpp_describe_mesh_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes,
+                               int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* Host only, all of the following: no context, no GPU; meshes and maps are HOST copies, pitches in bytes with 0 = tight.  Each returns TSVPP_ERROR for a null
+ * argument, a size <= 0 or odd, or a bad pitch, and TSVPP_UNSUPPORTED for a cell size outside 2..8.
+ * tsvpp_mesh_dims: the control grid of a dst_w x dst_h output, cols and rows as above. */
+int tsvpp_mesh_dims(int dst_w, int dst_h, int log2_cw, int log2_ch, int *cols, int *rows);
+/* E(mesh): the dense map (dst_h rows of dst_w (x, y) pairs) that tsvpp_convert_mesh samples through, computed by the function the kernel calls. */
+int tsvpp_mesh_expand(const float *host_mesh, int pitch, int dst_w, int dst_h, int log2_cw, int log2_ch, float *out_xy, int out_pitch);
+/* A dense map sampled at the control positions.  A position past the last pixel of an axis is linearly extrapolated from that axis's last two entries, in double,
+ * x first and then y; each value is rounded once to float. */
+int tsvpp_mesh_from_map(const float *host_xy, int pitch, int dst_w, int dst_h, int log2_cw, int log2_ch, float *out_mesh, int out_pitch);
+/* The largest |E(mesh) - map| over the entries where both are finite (either component), so that a caller can pick a cell size. */
+int tsvpp_mesh_error(const float *host_xy, int pitch, int dst_w, int dst_h, const float *host_mesh, int mesh_pitch, int log2_cw, int log2_ch, float *max_abs);
+/* tsvpp_remap_lds_need of E(mesh): what a caller puts into tsvpp_mesh::lds_bytes. */
+int tsvpp_mesh_lds_need(const float *host_mesh, int pitch, int dst_w, int dst_h, int log2_cw, int log2_ch, int frame_w, int frame_h, int luma_only);
+
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them
  * per frame, src/Resize.cu:389-406,436-452) and, for UYVY / YUV444 behind a resize, the resized-NV12 scratch of

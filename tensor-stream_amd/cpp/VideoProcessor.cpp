@@ -323,6 +323,35 @@ int VideoProcessor::ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvp
     return convertRemap(true, spec, ctx, isClosed, inputs, nInputs, maps, nMaps, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
 }
 
+// ConvertMesh and its tensor overload, as convertRemap (`tensor`: tsvpp_convert_mesh_tensor with `spec`)
+static int convertMesh(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes,
+                       const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV, void *const *deviceOuts, FrameParameters &options,
+                       const std::string &consumerName) {
+    if (isClosed || !inputs || nInputs <= 0 || !meshes || nMeshes <= 0 || !remaps || nRemaps <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
+    void *stream = nullptr;
+    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    std::vector<tsvpp_nv12> frames((size_t)nInputs);
+    for (int f = 0; f < nInputs; f++) {
+        const AVFrame *in = inputs[f];
+        if (!in) CHECK_STATUS(VREADER_ERROR);
+        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
+    }
+    const tsvpp_params p = flatten(options); // options.crop must be empty: the meshes address the whole frame
+    if (tensor) CHECK_STATUS(tsvpp_convert_mesh_tensor(ctx, nInputs, frames.data(), nMeshes, meshes, nRemaps, remaps, &p, spec, borderY, borderU, borderV, deviceOuts, stream));
+    else CHECK_STATUS(tsvpp_convert_mesh(ctx, nInputs, frames.data(), nMeshes, meshes, nRemaps, remaps, &p, borderY, borderU, borderV, deviceOuts, stream));
+    return VREADER_OK;
+}
+
+int VideoProcessor::ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                                int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
+    return convertMesh(false, nullptr, ctx, isClosed, inputs, nInputs, meshes, nMeshes, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+}
+
+int VideoProcessor::ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                                int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertMesh(true, spec, ctx, isClosed, inputs, nInputs, meshes, nMeshes, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+}
+
 int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &options, std::string consumerName) {
     if (isClosed || !input || !output) CHECK_STATUS(VREADER_ERROR);
     const tsvpp_params p = flatten(options);

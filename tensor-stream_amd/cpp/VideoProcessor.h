@@ -158,6 +158,13 @@ public:
                      void *const *deviceOuts, FrameParameters &options, std::string consumerName);
     int ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV,
                      void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
+    // Sparse control-grid warps -- a warp mesh per lens or per stabilised frame (tsvpp_convert_mesh, include/tsvpp.h; not in the reference): ConvertRemap with the
+    // coordinate interpolated from the device-resident control grid remaps[k].map (an index into `meshes`) instead of read per pixel; bit for bit ConvertRemap of
+    // the expanded mesh (tsvpp_mesh_expand).  Everything else as ConvertRemap.  With a tensor spec: tsvpp_convert_mesh_tensor.
+    int ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV,
+                    void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    int ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV,
+                    void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

@@ -249,6 +249,9 @@ int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, in
 // (tsvpp_convert_remap / tsvpp_describe_remap) warp_plan's rules in warp_plan's order without the matrix rules, with the maps' (include/tsvpp.h); `xy` is not read
 int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y,
                int border_u, int border_v, RoiPlan &pl);
+// (tsvpp_convert_mesh / tsvpp_describe_mesh) remap_plan's rules in remap_plan's order with the meshes' rules where the maps' are (include/tsvpp.h); `xy` is not read
+int mesh_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps, int border_y,
+              int border_u, int border_v, RoiPlan &pl);
 // (the tensor entry points of both paths) the status of a (params, spec) pair whose plan was accepted: rules 2 and 3 of include/tsvpp.h, in that order
 int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec);
 inline size_t tensor_elem_bytes(int dtype) { return dtype == TSVPP_F32 ? 4 : 2; }

@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "tsvpp_host.h"
+#include "vpp_mesh.h"
 #include "vpp_persp.h"
 #include "vpp_rois.h"
 
@@ -348,7 +349,33 @@ int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, in
     return TSVPP_OK;
 }
 
-// One spec check for both tensor paths.  The caller has the plan's status already (it wins); what is left is about the spec and about what the tensor stores cover.
+int mesh_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps, int border_y,
+              int border_u, int border_v, RoiPlan &pl) {
+    // TSVPP_ERROR: arguments that describe no request at all
+    if (!p || !frames || !meshes || !remaps || n_frames <= 0 || n_meshes <= 0 || n <= 0) return TSVPP_ERROR;
+    if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
+    for (int i = 0; i < n; i++)
+        if (remaps[i].frame < 0 || remaps[i].frame >= n_frames || remaps[i].map < 0 || remaps[i].map >= n_meshes) return TSVPP_ERROR;
+    const bool replicate = border_y == -1 && border_u == -1 && border_v == -1;
+    if (!replicate && (border_y < 0 || border_y > 255 || border_u < 0 || border_u > 255 || border_v < 0 || border_v > 255)) return TSVPP_ERROR;
+    for (int m = 0; m < n_meshes; m++) {
+        // (a cell size outside the range has no column count to hold a pitch against: its answer is TSVPP_UNSUPPORTED, below)
+        const bool cell = meshes[m].log2_cw >= MESH_LOG2_MIN && meshes[m].log2_cw <= MESH_LOG2_MAX;
+        if (meshes[m].pitch & 7) return TSVPP_ERROR;
+        if (cell && meshes[m].pitch != 0 && (long)meshes[m].pitch < 8L * mesh_points(p->dst_width, meshes[m].log2_cw)) return TSVPP_ERROR;
+        if (meshes[m].lds_bytes < 0) return TSVPP_ERROR;
+    }
+    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
+    if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    if (tile_output_plan(p, false, TSVPP_MAX_MESHES, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
+    for (int m = 0; m < n_meshes; m++) {
+        if (meshes[m].log2_cw < MESH_LOG2_MIN || meshes[m].log2_cw > MESH_LOG2_MAX) return TSVPP_UNSUPPORTED;
+        if (meshes[m].log2_ch < MESH_LOG2_MIN || meshes[m].log2_ch > MESH_LOG2_MAX) return TSVPP_UNSUPPORTED;
+    }
+    return TSVPP_OK;
+}
+
+// One spec check for both tensor paths. The caller has the plan's status already (it wins); what is left is about the spec and about what the tensor stores cover.
 int tensor_spec_status(const tsvpp_params *p, const tsvpp_tensor_spec *spec) {
     if (!p || !spec) return TSVPP_ERROR;
     const int used = p->fourcc == TSVPP_Y800 ? 1 : 3; // channels the format reads mean / scale of (a fourcc outside the list: all three, then rule 3)

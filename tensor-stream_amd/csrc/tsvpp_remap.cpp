@@ -71,6 +71,8 @@ struct RemapPath {
         const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n_remaps);
         return (tensor ? launch_remap_tensor : launch_remap)(pl.out, vec, L.lds_bytes > 0, border(), L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
     }
+    const char *mode_name() const { return "remap_bilinear"; }
+    void counts(char *buf, size_t len) const { std::snprintf(buf, len, "remaps=%d maps=%d frames=%d", n, n_maps, n_frames); }
     void label(char *buf, size_t len, const RoiPlan &pl, void *stream) const {
         std::snprintf(buf, len, "tsvpp_convert_remap%s n=%d maps=%d frames=%d ->%dx%d fourcc=%d stream=%p", tensor ? "_tensor" : "", n, n_maps, n_frames, pl.dst_w, pl.dst_h, p->fourcc, stream);
     }
@@ -88,37 +90,6 @@ int remap_convert(const RemapPath &path, tsvpp_ctx *ctx, void *const *outs, void
             }
     }
     return tile_convert(path, ctx, outs, stream);
-}
-
-// tile_describe's line without staged= (the host cannot count what it cannot see) and with lds= the dynamic LDS alone: non-zero iff the kernel is the staged one
-int remap_describe(RemapPath path, int aligned_outputs, char *buf, size_t buf_len) {
-    if (!buf || buf_len == 0) return TSVPP_ERROR;
-    buf[0] = 0;
-    RoiPlan pl;
-    const int sts = tile_request(path, pl);
-    if (sts != TSVPP_OK) return sts;
-    Knobs kn; // no context: no device, no streams
-    read_env_knobs(kn);
-    const bool vec = aligned_outputs != 0 && !narrow_tail(pl);
-    int lds0 = 0, grid0 = 0, launches = 0;
-    char kname[128] = "(none)", border[40] = "replicate";
-    RemapLaunch L;
-    const int limit = path.limit(pl);
-    for (int base = 0; base < path.n; base += limit, launches++) {
-        const int cnt = std::min(path.n - base, limit);
-        (void)tile_fill(path, kn, pl, nullptr, base, cnt, vec, L);
-        if (base == 0) {
-            lds0 = L.lds_bytes;
-            grid0 = L.tiles_x * L.tiles_y * cnt;
-            const hipError_t e = path.launch(pl, vec, lds0 > 0, L, nullptr, kname, sizeof(kname), true);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-    if (path.border()) std::snprintf(border, sizeof(border), "%d,%d,%d", path.border_y, path.border_u, path.border_v);
-    std::snprintf(buf, buf_len, "mode=remap_bilinear out=%s dst=%dx%d remaps=%d maps=%d frames=%d launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d tail=%d nt=%d limit=%d border=%s",
-                  path.tensor ? tensor_out_name(path.spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w, pl.dst_h, path.n, path.n_maps, path.n_frames, launches,
-                  kname, ROI_TX, ROI_TY, lds0, grid0, L.tiles_x, L.tiles_y, L.last_col0 > 0 ? 2 : 0, L.nt_stores, limit, border);
-    return TSVPP_OK;
 }
 
 // ---- a HOST copy of a map ----
@@ -172,7 +143,7 @@ int tsvpp_convert_remap(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, 
 
 int tsvpp_describe_remap(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
                          int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
-    return remap_describe(RemapPath{ false, p, nullptr, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+    return tile_describe_unplanned(RemapPath{ false, p, nullptr, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_convert_remap_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
@@ -182,7 +153,7 @@ int tsvpp_convert_remap_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *f
 
 int tsvpp_describe_remap_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps,
                                 int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
-    return remap_describe(RemapPath{ true, p, spec, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+    return tile_describe_unplanned(RemapPath{ true, p, spec, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_remap_footprint(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last,

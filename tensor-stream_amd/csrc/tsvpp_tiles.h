@@ -177,4 +177,37 @@ template <class PATH> int tile_describe(PATH path, int aligned_outputs, char *bu
     return TSVPP_OK;
 }
 
+// tile_describe for the paths whose coordinates live in device memory (tsvpp_remap.cpp, tsvpp_mesh.cpp): the line without staged= (the host cannot count what it
+// cannot see) and with lds= the dynamic LDS alone, non-zero iff the kernel is the staged one.  The path says mode_name() and counts() ("remaps=8 maps=1 frames=8")
+template <class PATH> int tile_describe_unplanned(PATH path, int aligned_outputs, char *buf, size_t buf_len) {
+    if (!buf || buf_len == 0) return TSVPP_ERROR;
+    buf[0] = 0;
+    RoiPlan pl;
+    const int sts = tile_request(path, pl);
+    if (sts != TSVPP_OK) return sts;
+    Knobs kn; // no context: no device, no streams
+    read_env_knobs(kn);
+    const bool vec = aligned_outputs != 0 && !narrow_tail(pl);
+    int lds0 = 0, grid0 = 0, launches = 0;
+    char kname[128] = "(none)", border[40] = "replicate", counts[96] = "";
+    typename PATH::Launch L;
+    const int limit = path.limit(pl);
+    for (int base = 0; base < path.n; base += limit, launches++) {
+        const int cnt = std::min(path.n - base, limit);
+        (void)tile_fill(path, kn, pl, nullptr, base, cnt, vec, L);
+        if (base == 0) {
+            lds0 = L.lds_bytes;
+            grid0 = L.tiles_x * L.tiles_y * cnt;
+            const hipError_t e = path.launch(pl, vec, lds0 > 0, L, nullptr, kname, sizeof(kname), true);
+            if (e != hipSuccess) return (int)e;
+        }
+    }
+    if (path.border()) std::snprintf(border, sizeof(border), "%d,%d,%d", path.border_y, path.border_u, path.border_v);
+    path.counts(counts, sizeof(counts));
+    std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d %s launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d tail=%d nt=%d limit=%d border=%s",
+                  path.mode_name(), path.tensor ? tensor_out_name(path.spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w, pl.dst_h, counts, launches,
+                  kname, ROI_TX, ROI_TY, lds0, grid0, L.tiles_x, L.tiles_y, L.last_col0 > 0 ? 2 : 0, L.nt_stores, limit, border);
+    return TSVPP_OK;
+}
+
 } // namespace tsvpp

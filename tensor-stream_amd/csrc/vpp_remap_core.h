@@ -19,6 +19,28 @@ struct RemapCoords {
     float cx[2], cy[2];
 };
 
+// From the entries of a thread tile to its coordinates: the chroma pairs from the UNCLAMPED luma entries, then THE clamp.  Whoever fills ex / ey -- a map that
+// is read (remap_load), a control grid that is interpolated (mesh_load, vpp_mesh_core.h) -- everything behind the entries is this function.
+template <bool VEC> __device__ __forceinline__ void remap_coords(const float (&ex)[PXH][PXW], const float (&ey)[PXH][PXW], int dst_w, int src_w, int src_h, int j0, RemapCoords &c) {
+    const int cw = src_w >> 1, ch = src_h >> 1;
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+        c.cx[p] = remap_clamp(remap_chroma(ex[0][2 * p], ex[0][2 * p + 1], ex[1][2 * p], ex[1][2 * p + 1]), cw);
+        c.cy[p] = remap_clamp(remap_chroma(ey[0][2 * p], ey[0][2 * p + 1], ey[1][2 * p], ey[1][2 * p + 1]), ch);
+    }
+    if (!VEC && dst_w - j0 < PXW) { // the second pair does not exist: it is sampled where the first one is, and never stored
+        c.cx[1] = c.cx[0];
+        c.cy[1] = c.cy[0];
+    }
+#pragma unroll
+    for (int rr = 0; rr < PXH; rr++)
+#pragma unroll
+        for (int k = 0; k < PXW; k++) {
+            c.x[rr][k] = remap_clamp(ex[rr][k], src_w);
+            c.y[rr][k] = remap_clamp(ey[rr][k], src_h);
+        }
+}
+
 // Map entries of the thread tile at output (i0, j0), clamped.  Row and column indices are clamped into the output, so no load leaves dst_h rows x 8 * dst_w bytes
 // of the map whatever the thread: a lane without pixels reads entries of others (and takes no part in the reduction), a column that does not exist (element-wise
 // flavour, 4 k + 2 columns) repeats the row's last one, as the samplers of the other tile kernels do.
@@ -46,23 +68,7 @@ template <bool VEC> __device__ __forceinline__ void remap_load(const uint8_t *xy
             }
         }
     }
-    const int cw = src_w >> 1, ch = src_h >> 1;
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        c.cx[p] = remap_clamp(remap_chroma(ex[0][2 * p], ex[0][2 * p + 1], ex[1][2 * p], ex[1][2 * p + 1]), cw);
-        c.cy[p] = remap_clamp(remap_chroma(ey[0][2 * p], ey[0][2 * p + 1], ey[1][2 * p], ey[1][2 * p + 1]), ch);
-    }
-    if (!VEC && dst_w - j0 < PXW) { // the second pair does not exist: it is sampled where the first one is, and never stored
-        c.cx[1] = c.cx[0];
-        c.cy[1] = c.cy[0];
-    }
-#pragma unroll
-    for (int rr = 0; rr < PXH; rr++)
-#pragma unroll
-        for (int k = 0; k < PXW; k++) {
-            c.x[rr][k] = remap_clamp(ex[rr][k], src_w);
-            c.y[rr][k] = remap_clamp(ey[rr][k], src_h);
-        }
+    remap_coords<VEC>(ex, ey, dst_w, src_w, src_h, j0, c);
 }
 
 // ---- the footprint reduction: min / max over the workgroup's 128 lanes -------------------------------------------------------------------------------------
@@ -120,8 +126,9 @@ __device__ __forceinline__ RemapExtremes remap_reduce(const RemapCoords &c, bool
 }
 
 // convert_thread_tile (vpp_device.h) with the map's coordinates: 2 x 4 luma samples and 2 chroma pairs of the virtual NV12 frame, then the one colour back end
-template <int OUT, bool VEC, bool BORDER, int EL, class S>
-__device__ __forceinline__ void remap_thread_tile(const S &s, const LaunchDesc &d, const RemapLaunch &L, const RemapCoords &c, typename OutT<OUT>::type *out, int i0, int j0) {
+// (LT: the launch block that carries the border sample and the tensor spec -- RemapLaunch, or MeshLaunch of vpp_mesh.h)
+template <int OUT, bool VEC, bool BORDER, int EL, class S, class LT>
+__device__ __forceinline__ void remap_thread_tile(const S &s, const LaunchDesc &d, const LT &L, const RemapCoords &c, typename OutT<OUT>::type *out, int i0, int j0) {
     const int ncol = VEC ? PXW : min(PXW, d.dst_w - j0);
     float Uf[2] = { 128.0f, 128.0f }, Vf[2] = { 128.0f, 128.0f }, Yf[PXH][PXW];
     if constexpr (!kLumaOnly<OUT>) {

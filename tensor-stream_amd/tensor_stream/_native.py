@@ -15,6 +15,7 @@ TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
 TSVPP_MAX_WARPS = 32  # outputs per launch of tsvpp_convert_warp
 TSVPP_MAX_PERSP = 32  # outputs per launch of tsvpp_convert_perspective
 TSVPP_MAX_REMAPS = 32  # outputs per launch of tsvpp_convert_remap
+TSVPP_MAX_MESHES = 32  # outputs per launch of tsvpp_convert_mesh
 TSVPP_F32, TSVPP_F16, TSVPP_BF16 = 0, 1, 2  # enum tsvpp_dtype: the element of the tensor entry points
 TSVPP_OPT_INPUTS_READY = 1
 TSVPP_OPT_COLOR_G_TERM = 2
@@ -63,6 +64,12 @@ class Map(ctypes.Structure):
     _fields_ = [("xy", ctypes.c_void_p), ("pitch", ctypes.c_int32), ("lds_bytes", ctypes.c_int32)]
 
 
+class Mesh(ctypes.Structure):
+    """struct tsvpp_mesh: one warp mesh of tsvpp_convert_mesh in DEVICE memory -- rows x cols (x, y) fp32 control points, row pitch in bytes (0: tight), the cell
+    size as two logarithms (2..8), LDS hint (0: none)."""
+    _fields_ = [("xy", ctypes.c_void_p), ("pitch", ctypes.c_int32), ("log2_cw", ctypes.c_int32), ("log2_ch", ctypes.c_int32), ("lds_bytes", ctypes.c_int32)]
+
+
 class Remap(ctypes.Structure):
     """struct tsvpp_remap: one output of tsvpp_convert_remap -- the frame it samples and the map it samples it through."""
     _fields_ = [("frame", ctypes.c_int32), ("map", ctypes.c_int32)]
@@ -89,7 +96,9 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
            "tsvpp_convert_perspective", "tsvpp_describe_perspective", "tsvpp_convert_perspective_tensor", "tsvpp_describe_perspective_tensor", "tsvpp_persp_from_quad",
            "tsvpp_persp_footprint",
-           "tsvpp_convert_remap", "tsvpp_describe_remap", "tsvpp_convert_remap_tensor", "tsvpp_describe_remap_tensor", "tsvpp_remap_footprint", "tsvpp_remap_lds_need"]
+           "tsvpp_convert_remap", "tsvpp_describe_remap", "tsvpp_convert_remap_tensor", "tsvpp_describe_remap_tensor", "tsvpp_remap_footprint", "tsvpp_remap_lds_need",
+           "tsvpp_convert_mesh", "tsvpp_describe_mesh", "tsvpp_convert_mesh_tensor", "tsvpp_describe_mesh_tensor", "tsvpp_mesh_dims", "tsvpp_mesh_expand",
+           "tsvpp_mesh_from_map", "tsvpp_mesh_error", "tsvpp_mesh_lds_need"]
 
 _lib = None
 
@@ -208,6 +217,25 @@ def lib():
     L.tsvpp_remap_footprint.restype = i32
     L.tsvpp_remap_lds_need.argtypes = [pf, i32, i32, i32, i32, i32, i32]
     L.tsvpp_remap_lds_need.restype = i32
+    pe, pi = ctypes.POINTER(Mesh), ctypes.POINTER(ctypes.c_int)
+    L.tsvpp_convert_mesh.argtypes = [vp, i32, pn, i32, pe, i32, pr, pp, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_mesh.restype = i32
+    L.tsvpp_describe_mesh.argtypes = [pp, i32, pn, i32, pe, i32, pr, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_mesh.restype = i32
+    L.tsvpp_convert_mesh_tensor.argtypes = [vp, i32, pn, i32, pe, i32, pr, pp, ps, i32, i32, i32, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_mesh_tensor.restype = i32
+    L.tsvpp_describe_mesh_tensor.argtypes = [pp, ps, i32, pn, i32, pe, i32, pr, i32, i32, i32, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_mesh_tensor.restype = i32
+    L.tsvpp_mesh_dims.argtypes = [i32, i32, i32, i32, pi, pi]
+    L.tsvpp_mesh_dims.restype = i32
+    L.tsvpp_mesh_expand.argtypes = [pf, i32, i32, i32, i32, i32, pf, i32]
+    L.tsvpp_mesh_expand.restype = i32
+    L.tsvpp_mesh_from_map.argtypes = [pf, i32, i32, i32, i32, i32, pf, i32]
+    L.tsvpp_mesh_from_map.restype = i32
+    L.tsvpp_mesh_error.argtypes = [pf, i32, i32, i32, pf, i32, i32, i32, pf]
+    L.tsvpp_mesh_error.restype = i32
+    L.tsvpp_mesh_lds_need.argtypes = [pf, i32, i32, i32, i32, i32, i32, i32, i32]
+    L.tsvpp_mesh_lds_need.restype = i32
     L.tsvpp_debug_area_tables.argtypes = [vp]
     L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

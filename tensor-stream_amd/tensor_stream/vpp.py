@@ -385,6 +385,34 @@ class VideoProcessor:
                                                          outs, stream))
         return out
 
+    def convert_mesh(self, ys, uvs, meshes, params, cell=(16, 16), remaps=None, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """Sparse control-grid warps -- a warp mesh per lens, per stabilised frame (tsvpp_convert_mesh): convert_remap with the coordinate interpolated from one
+        control point per cell of cw x ch output pixels instead of read per pixel; bit for bit convert_remap of mesh_expand(mesh).  meshes: one CUDA float32 tensor
+        (rows, cols, 2) of (x, y) source positions, (rows, cols) = mesh_dims(width, height, cell) -- control point (r, c) belongs to output pixel (r * ch, c * cw),
+        index-based as a dense map's entry (mesh_from_map, mesh_undistort make them) -- or a list of them; the last dimension is contiguous, a row stride of
+        >= 2 * cols elements becomes the pitch; each may be paired as (tensor, lds_bytes) with the hint of mesh_lds_hint.  cell: (cw, ch), powers of two 4..256,
+        for all meshes or a list with one per mesh.  The tensors are read when the kernel runs: keep them alive, and a captured graph sees their updates.
+        remaps: a list of (frame, mesh), None as for convert_remap.  Everything else: as convert_remap."""
+        spec = tensor_spec(dtype, mean, std)
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        ys, uvs, _ = _normalize_rois(ys, uvs, [])
+        recs_m = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height, self.device)
+        recs = _normalize_remaps(remaps, len(ys), len(recs_m))
+        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
+        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
+        n = len(recs)
+        if out is None:
+            out = self._alloc_items(p, n, spec, "convert_mesh needs an even, positive output size")
+        by, bu, bv = _border(border)
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if spec is None:
+            N.check(self._lib.tsvpp_convert_mesh(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
+        else:
+            N.check(self._lib.tsvpp_convert_mesh_tensor(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv,
+                                                        outs, stream))
+        return out
+
     def convert_perspective(self, ys, uvs, persps, params, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """Homography-warped outputs (tsvpp_convert_perspective): every entry of `persps` samples its frame BILINEAR through its own 3 x 3 output -> source
         homography into params' width x height, colour-converted and stored to its own output, one launch per 32 outputs.  ys / uvs, border, out, width, height,
@@ -836,6 +864,190 @@ def remap_lds_hint(map, frame_w, frame_h, luma_only=False):
     if need < 0:
         N.check(need)
     return need
+
+
+def _cell_logs(cell):
+    """(cw, ch) in output pixels as (log2_cw, log2_ch): positive powers of two (the range 4..256 is the C call's rule)"""
+    try:
+        cw, ch = (int(v) for v in cell)
+    except (TypeError, ValueError):
+        raise ValueError(f"a cell is (cw, ch), not {cell}") from None
+    for v in (cw, ch):
+        if v <= 0 or v & (v - 1):
+            raise ValueError(f"a cell size is a power of two, not {v}")
+    return cw.bit_length() - 1, ch.bit_length() - 1
+
+
+def mesh_dims(dst_w, dst_h, cell):
+    """(rows, cols) of the control grid of a dst_w x dst_h output at cell = (cw, ch) (tsvpp_mesh_dims): one point beyond the cell of the last pixel on each axis."""
+    lw, lh = _cell_logs(cell)
+    cols, rows = ctypes.c_int(0), ctypes.c_int(0)
+    N.check(N.lib().tsvpp_mesh_dims(int(dst_w), int(dst_h), lw, lh, ctypes.byref(cols), ctypes.byref(rows)))
+    return rows.value, cols.value
+
+
+def _normalize_meshes(meshes, cell, dst_w, dst_h, device=None):
+    """The meshes argument of convert_mesh / describe_mesh as an array of tsvpp_mesh: _normalize_maps for control grids.  cell: (cw, ch) for all meshes, or a list
+    with one (cw, ch) per mesh.  A mesh is a float32 tensor (rows, cols, 2) of mesh_dims' shape whose last dimension is contiguous, optionally paired as
+    (tensor, lds_bytes); without a device (describe_mesh) it may also be (pitch, lds_bytes) integers.  Anything else raises ValueError: nothing reaches the C call."""
+    if isinstance(meshes, torch.Tensor) or (isinstance(meshes, tuple) and len(meshes) == 2 and not isinstance(meshes[1], (torch.Tensor, tuple, list))):
+        meshes = [meshes]
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("at least one mesh is needed")
+    if not isinstance(cell, (tuple, list)):
+        raise ValueError(f"a cell is (cw, ch), not {cell}")
+    cells = list(cell)
+    if cells and not isinstance(cells[0], (tuple, list)):
+        cells = [tuple(cells)] * len(meshes)
+    if len(cells) != len(meshes):
+        raise ValueError(f"{len(meshes)} meshes and {len(cells)} cells: give one (cw, ch) or one per mesh")
+    recs = []
+    for m, cl in zip(meshes, cells):
+        lw, lh = _cell_logs(cl)
+        rows, cols = ((dst_h - 1) >> lh) + 2, ((dst_w - 1) >> lw) + 2
+        hint = 0
+        if isinstance(m, (tuple, list)):
+            if len(m) != 2:
+                raise ValueError(f"a mesh is a tensor, (tensor, lds_bytes) or (pitch, lds_bytes), not {m}")
+            m, hint = m[0], int(m[1])
+        if not isinstance(m, torch.Tensor):
+            if device is not None:
+                raise ValueError(f"convert_mesh needs its meshes as tensors, not {type(m).__name__}")
+            recs.append(N.Mesh(None, int(m), lw, lh, hint))
+            continue
+        if m.dtype != torch.float32:
+            raise ValueError(f"a mesh is a float32 tensor, not {m.dtype}")
+        if m.dim() != 3 or tuple(m.shape) != (rows, cols, 2):
+            raise ValueError(f"a mesh for a {dst_w} x {dst_h} output at cell {tuple(cl)} has shape ({rows}, {cols}, 2), not {tuple(m.shape)}")
+        if m.stride(2) != 1 or m.stride(1) != 2 or m.stride(0) < 2 * cols:
+            raise ValueError(f"a mesh's last two dimensions are contiguous and its row stride is at least {2 * cols} elements: strides {tuple(m.stride())}")
+        if device is not None and (not m.is_cuda or m.device.index != device):
+            raise ValueError(f"a mesh lives on cuda:{device}, not on {m.device}")
+        recs.append(N.Mesh(m.data_ptr() if m.is_cuda else None, 4 * m.stride(0), lw, lh, hint))
+    return (N.Mesh * len(recs))(*recs)
+
+
+def describe_mesh(params, frames, meshes, cell=(16, 16), remaps=None, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_mesh of this request would launch, as a dict (tsvpp_describe_mesh: describe_remap's keys with meshes= and cell= for maps=, mode
+    mesh_bilinear) -- host logic only, works without a GPU.  frames: as describe_rois; meshes: as for convert_mesh (tensors on any device: only strides and hints
+    are read) or (pitch, lds_bytes) integers; cell, remaps and border as for convert_mesh."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
+    ms = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height)
+    rs = _normalize_remaps(remaps, len(recs), len(ms))
+    fr = (N.NV12 * len(recs))(*recs)
+    by, bu, bv = _border(border)
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    if spec is None:
+        N.check(N.lib().tsvpp_describe_mesh(ctypes.byref(p), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(N.lib().tsvpp_describe_mesh_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv,
+                                                   1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def _host_pairs(a, what):
+    """a tensor or array (H, W, 2) float32 as a contiguous numpy array, and whether it came as a tensor"""
+    host = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if host.dtype != np.float32 or host.ndim != 3 or host.shape[2] != 2:
+        raise ValueError(f"a {what} is float32 (H, W, 2), not {host.dtype} {host.shape}")
+    return np.ascontiguousarray(host)
+
+
+def _like(host, src):
+    return torch.from_numpy(host).to(src.device) if isinstance(src, torch.Tensor) else host
+
+
+_PF = ctypes.POINTER(ctypes.c_float)
+
+
+def mesh_from_map(xy, cell):
+    """A dense map (H, W, 2) of convert_remap as the warp mesh (rows, cols, 2) of convert_mesh at cell = (cw, ch) (tsvpp_mesh_from_map): the map sampled at the
+    control positions; a position past the last pixel of an axis is extrapolated linearly from that axis's last two entries, in double, x first and then y.
+    mesh_error says what the mesh loses.  numpy arrays give a numpy array, tensors a tensor on their device."""
+    lw, lh = _cell_logs(cell)
+    host = _host_pairs(xy, "map")
+    h, w = host.shape[:2]
+    rows, cols = mesh_dims(w, h, cell)
+    out = np.empty((rows, cols, 2), np.float32)
+    N.check(N.lib().tsvpp_mesh_from_map(host.ctypes.data_as(_PF), 0, w, h, lw, lh, out.ctypes.data_as(_PF), 0))
+    return _like(out, xy)
+
+
+def mesh_expand(mesh, dst_size, cell):
+    """E(mesh): the dense map (dst_h, dst_w, 2) that convert_mesh samples through, from the function the kernel calls (tsvpp_mesh_expand); convert_remap of it is
+    convert_mesh of the mesh, bit for bit.  dst_size: (dst_w, dst_h).  numpy arrays give a numpy array, tensors a tensor on their device."""
+    lw, lh = _cell_logs(cell)
+    w, h = (int(v) for v in dst_size)
+    host = _host_pairs(mesh, "mesh")
+    if host.shape[:2] != mesh_dims(w, h, cell):
+        raise ValueError(f"a mesh for a {w} x {h} output at cell {tuple(cell)} has shape {mesh_dims(w, h, cell) + (2,)}, not {host.shape}")
+    out = np.empty((h, w, 2), np.float32)
+    N.check(N.lib().tsvpp_mesh_expand(host.ctypes.data_as(_PF), 0, w, h, lw, lh, out.ctypes.data_as(_PF), 0))
+    return _like(out, mesh)
+
+
+def mesh_error(xy, mesh, cell):
+    """The largest |E(mesh) - map| in pixels over the finite entries of a dense map (H, W, 2) and a mesh for it (tsvpp_mesh_error): pick the largest cell whose
+    error the application tolerates."""
+    lw, lh = _cell_logs(cell)
+    host, hm = _host_pairs(xy, "map"), _host_pairs(mesh, "mesh")
+    h, w = host.shape[:2]
+    if hm.shape[:2] != mesh_dims(w, h, cell):
+        raise ValueError(f"a mesh for a {w} x {h} map at cell {tuple(cell)} has shape {mesh_dims(w, h, cell) + (2,)}, not {hm.shape}")
+    worst = ctypes.c_float(0.0)
+    N.check(N.lib().tsvpp_mesh_error(host.ctypes.data_as(_PF), 0, w, h, hm.ctypes.data_as(_PF), 0, lw, lh, ctypes.byref(worst)))
+    return worst.value
+
+
+def mesh_lds_hint(mesh, dst_size, cell, frame_w, frame_h, luma_only=False):
+    """The LDS hint of a mesh for a dst_size = (dst_w, dst_h) output on a frame_w x frame_h frame (tsvpp_mesh_lds_need: remap_lds_hint of mesh_expand(mesh)) --
+    what convert_mesh takes as (tensor, lds_bytes).  Copies the mesh to the host once; luma_only: for Y800 outputs."""
+    lw, lh = _cell_logs(cell)
+    w, h = (int(v) for v in dst_size)
+    hm = _host_pairs(mesh, "mesh")
+    if hm.shape[:2] != mesh_dims(w, h, cell):
+        raise ValueError(f"a mesh for a {w} x {h} output at cell {tuple(cell)} has shape {mesh_dims(w, h, cell) + (2,)}, not {hm.shape}")
+    need = N.lib().tsvpp_mesh_lds_need(hm.ctypes.data_as(_PF), 0, w, h, lw, lh, int(frame_w), int(frame_h), 1 if luma_only else 0)
+    if need < 0:
+        N.check(need)
+    return need
+
+
+def mesh_undistort(K, dist, new_K, dst_size, cell):
+    """The undistortion mesh of a camera, as a numpy array (rows, cols, 2) float32: OpenCV's distortion model evaluated at the control positions in float64 -- the
+    direct forward formula behind cv2.initUndistortRectifyMap (no rectification), no iteration, no dense map.  K, new_K: 3 x 3 camera matrices of the distorted
+    frame and of the output; dist: (k1, k2, p1, p2[, k3[, k4, k5, k6]]); dst_size: (dst_w, dst_h); cell: (cw, ch).  For the output pixel (u, v):
+    x = (u - cx') / fx', y = (v - cy') / fy', r2 = x x + y y, a = k1 r2 + k2 r2^2 + k3 r2^3, b = k4 r2 + k5 r2^2 + k6 r2^3, g = (a - b) / (1 + b) (the radial
+    factor less one), dx = x g + 2 p1 x y + p2 (r2 + 2 x x), dy = y g + p1 (r2 + 2 y y) + 2 p2 x y, and the source position is
+    ((u - cx') (fx / fx') + cx + fx dx, (v - cy') (fy / fy') + cy + fy dy): with no distortion and K = new_K exactly (u, v)."""
+    _cell_logs(cell)
+    K, new_K = np.asarray(K, np.float64), np.asarray(new_K, np.float64)
+    d = [float(v) for v in np.asarray(dist, np.float64).ravel()]
+    if K.shape != (3, 3) or new_K.shape != (3, 3):
+        raise ValueError("K and new_K are 3 x 3 camera matrices")
+    if len(d) not in (4, 5, 8):
+        raise ValueError(f"dist is (k1, k2, p1, p2), with k3, or with k3 .. k6: not {len(d)} numbers")
+    d += [0.0] * (8 - len(d))
+    k1, k2, p1, p2, k3, k4, k5, k6 = d
+    w, h = (int(v) for v in dst_size)
+    rows, cols = mesh_dims(w, h, cell)
+    u = (np.arange(cols, dtype=np.float64) * int(cell[0]))[None, :]
+    v = (np.arange(rows, dtype=np.float64) * int(cell[1]))[:, None]
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    nfx, nfy, ncx, ncy = new_K[0, 0], new_K[1, 1], new_K[0, 2], new_K[1, 2]
+    x, y = (u - ncx) / nfx + 0.0 * v, (v - ncy) / nfy + 0.0 * u
+    r2 = x * x + y * y
+    a = r2 * (k1 + r2 * (k2 + r2 * k3))
+    b = r2 * (k4 + r2 * (k5 + r2 * k6))
+    g = (a - b) / (1.0 + b)
+    dx = x * g + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+    dy = y * g + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+    mx = (u - ncx) * (fx / nfx) + cx + fx * dx
+    my = (v - ncy) * (fy / nfy) + cy + fy * dy
+    return np.ascontiguousarray(np.stack((mx, my), axis=-1).astype(np.float32))
 
 
 def debug_last_launch():

@@ -147,6 +147,9 @@ int tsvpp_convert_batch(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
  *   tsvpp_convert_table   == tsvpp_convert_batch over entries [first, first + n), same results, same status codes.
  *   tsvpp_table_destroy   frees the table (the caller has waited for conversions that use it).  Destroying the CONTEXT first is legal: tsvpp_destroy releases the
  *                         device memory of its live tables, their handles remain valid arguments of tsvpp_table_destroy only.
+ * tsvpp_table_set on a stream that is being captured into a hipGraph is refused: TSVPP_UNSUPPORTED, nothing is enqueued and the table is unchanged (its copies
+ * would become graph nodes that re-read recycled staging memory at every replay).  Set the entries on an ordinary stream before or after the capture; the captured
+ * tsvpp_convert_table reads whatever the table holds at replay time.  (A NULL stream is taken as not capturing.)
  * A table belongs to the context that created it (its device).  tsvpp_table_set calls are serialised against each other; a tsvpp_convert_table that runs
  * concurrently with a tsvpp_table_set of the SAME entries from another thread is the caller's race (as two writers of one AVFrame would be), and a captured
  * hipGraph replays the table as the device holds it at replay time (entries are read by the kernels, not baked into the graph). */
@@ -650,12 +653,19 @@ int tsvpp_enable_markers(tsvpp_ctx *ctx, int on);
  * set -- the library's parity statements are about the reference's literals. */
 #define TSVPP_OPT_UNSAFE_COEFFS 3
 #define TSVPP_HAVE_OPTIONS 1
+/* Threads.  tsvpp_set_option, tsvpp_get_option and tsvpp_enable_markers may be called while other threads convert through the same context: every option is
+ * read and written atomically, and a conversion that runs beside the call uses the old value or the new one, whole -- never a launch remembered from the old
+ * value after the call has returned to a thread that then converts.  What the OPTION promises is still the caller's to keep: a conversion that may see
+ * TSVPP_OPT_INPUTS_READY set must meet its conditions (1) and (2).  tsvpp_set_coeffs is different, see there. */
 int tsvpp_set_option(tsvpp_ctx *ctx, int option, int value);
 int tsvpp_get_option(const tsvpp_ctx *ctx, int option, int *value);
 
 /* Colour constants: read the active block, replace it (e.g. with the block received
  * from rank 0), restore the defaults.  tsvpp_set_coeffs accepts only the default block (bit for bit) unless
- * TSVPP_OPT_UNSAFE_COEFFS is set: TSVPP_UNSUPPORTED otherwise. */
+ * TSVPP_OPT_UNSAFE_COEFFS is set: TSVPP_UNSUPPORTED otherwise.
+ * tsvpp_set_coeffs needs a QUIESCENT context: no conversion, tsvpp_prepare* or tsvpp_get_coeffs of this context may run on another thread
+ * during the call -- the block is eight floats that launches copy as they are, not an atomic value.  Set it once, after tsvpp_create (the multi-GPU broadcast
+ * does), or between two points where the caller has joined its converting threads. */
 int tsvpp_get_coeffs(const tsvpp_ctx *ctx, tsvpp_coeffs *out);
 int tsvpp_set_coeffs(tsvpp_ctx *ctx, const tsvpp_coeffs *in);
 void tsvpp_default_coeffs(tsvpp_coeffs *out);

@@ -387,7 +387,8 @@ int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &op
     }
     {
         std::lock_guard<std::mutex> lk(poolSync);
-        if (handedOut.size() > 65536) handedOut.clear(); // a caller that only ever hipFree()s leaves its entries behind: bounded (Release then answers VREADER_ERROR for the forgotten ones)
+        // never forgotten while the caller may still Release() it (VideoProcessor.h).  A caller that hipFree()s instead leaves its entry behind until the allocator hands
+        // the address out again -- this line then overwrites it -- or until Close(): one entry per distinct address, not per frame.
         handedOut[dst] = bytes;
     }
     output->opaque = dst;

@@ -169,7 +169,10 @@ public:
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in
     // the steady state.  `stream`: the stream on which the caller's LAST use of the buffer was enqueued (nullptr = the legacy default stream); the reuse is ordered
-    // behind an event recorded there, nothing is synchronised.  Buffers still pooled at Close() are freed.  VREADER_ERROR for a pointer Convert did not hand out.
+    // behind an event recorded there, nothing is synchronised.  Buffers still pooled at Close() are freed.  VREADER_ERROR for a pointer Convert did not hand out (or one released twice).
+    // The processor remembers every result it handed out until it is released, its address is handed out again, or Close(): a result is never forgotten while its
+    // caller may still Release() it, however many Converts lie in between.  A caller that hipFree()s its results costs one remembered entry per distinct address.
+    // Convert and Release may be called from several threads on one object (the pool has its own lock); Init and Close may not run beside them.
     int Release(void *opaque, hipStream_t stream = nullptr);
     template <class T> int DumpFrame(T *output, FrameParameters options, std::shared_ptr<FILE> dumpFile);
     void Close();

@@ -15,6 +15,7 @@ using namespace tsvpp;
 
 namespace tsvpp {
 thread_local LaunchRecord *g_launch_rec = nullptr;
+thread_local bool g_build_declined = false;
 
 // The tracer library is looked up at run time -- rocprofv3's SDK flavour first, the legacy roctracer one second.
 Roctx::Roctx() {
@@ -133,7 +134,10 @@ int scratch_grow(tsvpp_ctx *ctx, tsvpp_ctx::ScratchSlot *slot, size_t need) {
     if (slot->bytes >= need) return TSVPP_OK;
     uint8_t *fresh = nullptr;
     hipError_t e = hipMalloc((void **)&fresh, need);
-    if (e != hipSuccess) return (int)e;
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); // reported here: a launcher's `return hipGetLastError()` later on this thread must not find it
+        return (int)e;
+    }
     if (slot->buf) {
         std::lock_guard<std::mutex> lk(ctx->scratch_mu);
         ctx->retired.push_back(slot->buf);
@@ -234,7 +238,7 @@ struct RecordArm { // points launch_fused's launches at `rec` for the lifetime o
 };
 
 int try_replay(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, void *const *outs, void *stream) {
-    const uint64_t epoch = ctx->epoch.load(std::memory_order_relaxed);
+    const uint64_t epoch = ctx->epoch.load(std::memory_order_acquire); // (a plain load on x86)
     const int py = pitch_or_width(in[0].pitch_y, in[0].width), puv = pitch_or_width(in[0].pitch_uv, in[0].width);
     bool classed = false, aligned4 = false, vec = false; // alignment class of THIS call, computed once (every entry of one request has the same crop offsets)
     for (int k = 0; k < kReplayEntries; k++) {
@@ -320,8 +324,11 @@ int tsvpp::convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
     g_last_launch = nullptr; // (tsvpp_debug_last_launch: no stale record survives a conversion that records none)
     if (!ctx || !in || !p || !outs || n < 0) return TSVPP_ERROR;
     if (n == 0) return TSVPP_OK;
+    g_build_declined = false;
+    // The epoch first, every option after it (OptInt, tsvpp_host.h).  tsvpp_set_option stores the value before it moves the epoch, so a launch built from newer
+    // options than `epoch0` stands for is remembered under an epoch that is already past -- never replayed -- and one built from older options cannot be.
+    const uint64_t epoch0 = ctx->epoch.load(std::memory_order_acquire);
     const bool replayable = ctx->knobs.replay && tab.y == nullptr && n <= TSVPP_MAX_BATCH && !ctx->markers;
-    const uint64_t epoch0 = ctx->epoch.load(std::memory_order_relaxed);
     if (replayable) { // the same request as one of this thread's recent ones: its finished launch again, with this call's frame pointers
         const int r = try_replay(ctx, n, in, p, outs, stream);
         if (r != kReplayMiss) return r;
@@ -373,7 +380,8 @@ int tsvpp::convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
     // formats (pass 1 writes the stream's scratch buffer, which the previous call's pass 2 may still be reading)
     // ... and only for launches small enough to gain from starting beside their predecessor: measured on the headline (profiles/r06_curve_values.txt, one consumer on two
     // streams) 1 / 2 / 4 frames per launch 0.367 / 0.573 / 0.661 -> 0.410 / 0.583 / 0.682 of the roofline, but 8 frames (113 MB) 0.719 -> 0.682
-    d.any_order = ((ctx->inputs_ready == 1 || ctx->inputs_ready == 2) && tab.y == nullptr && !rq.two_pass &&
+    const int inputs_ready = ctx->inputs_ready; // read once
+    d.any_order = ((inputs_ready == 1 || inputs_ready == 2) && tab.y == nullptr && !rq.two_pass &&
                    (size_t)n * plan_moved_bytes(pl) <= TSVPP_BARRIER_FREE_MAX_BYTES) ? 1 : 0;
     int max_launch = TSVPP_MAX_BATCH;
     if (from_table) {
@@ -415,7 +423,9 @@ int tsvpp::convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
                 g_last_launch = nullptr; // (an earlier launch group's record does not describe a failed conversion)
                 return (int)e;
             }
-            if (keep && rec.count == 1 && rec.fn) {
+            // (a launch that fell back because a capturing stream kept a table from being built is right for this call and wrong to remember: the next ordinary
+            // call builds the table)
+            if (keep && rec.count == 1 && rec.fn && !g_build_declined) {
                 const LaunchRecord *kept = remember_launch(ctx, epoch0, n, in, p, pitch_y, pitch_uv, aligned4, vec, off.y, off.uv, rec);
                 if (ctx->knobs.debug) g_last_launch = kept;
             } else if (ctx->knobs.debug && rec.count > 0) { // (count == 0: nothing was launched, and rec.d was never written)
@@ -494,6 +504,7 @@ int tsvpp_create(int device, int max_consumers, tsvpp_ctx **out_ctx) {
         hipStream_t s = nullptr;
         e = hipStreamCreate(&s); // blocking stream, as the reference (src/VideoProcessor.cpp:86)
         if (e != hipSuccess) {
+            (void)hipGetLastError();
             for (auto &st : ctx->streams)
                 if (st.second) (void)hipStreamDestroy(st.second);
             geo_cache_destroy(ctx->geo);
@@ -547,7 +558,8 @@ int tsvpp_consumer_next_stream(tsvpp_ctx *ctx, const char *name, size_t launch_b
     std::lock_guard<std::mutex> lk(ctx->stream_mu);
     const int i = consumer_slot(ctx, name);
     if (i < 0) return TSVPP_ERROR; // pool exhausted (reference src/VideoProcessor.cpp:100-103)
-    if (!(ctx->inputs_ready == 1 || ctx->inputs_ready == 3) || launch_bytes > TSVPP_OVERLAP_MAX_BYTES) { // (large launches do not overlap: see the header)
+    const int inputs_ready = ctx->inputs_ready;
+    if (!(inputs_ready == 1 || inputs_ready == 3) || launch_bytes > TSVPP_OVERLAP_MAX_BYTES) { // (large launches do not overlap: see the header)
         *out_stream = (void *)ctx->streams[(size_t)i].second;
         return TSVPP_OK;
     }
@@ -556,7 +568,10 @@ int tsvpp_consumer_next_stream(tsvpp_ctx *ctx, const char *name, size_t launch_b
         if (guard.status != TSVPP_OK) return guard.status;
         hipStream_t s = nullptr;
         const hipError_t e = hipStreamCreate(&s); // blocking, as the pool's first stream
-        if (e != hipSuccess) return (int)e;
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return (int)e;
+        }
         ctx->streams2[(size_t)i] = s;
     }
     const uint8_t t = ctx->turn[(size_t)i];

@@ -136,7 +136,9 @@ void set_area_desc(const Plan &pl, const AreaTable &tx, const AreaTable &ty, con
     }
 }
 
-// A host vector as a fresh device allocation; on failure nothing stays allocated and `dev` is null (the runtime's last error is left to the caller).
+// A host vector as a fresh device allocation; on failure nothing stays allocated, `dev` is null and the runtime's last error is cleared: the failure is this
+// function's result, and a launcher that ends in `return hipGetLastError()` must not find it later -- a first AREA conversion refused inside a capture made the
+// thread's NEXT successful launch report the capture error.
 template <class T> hipError_t upload(const std::vector<T> &v, T *&dev) {
     dev = nullptr;
     hipError_t e = hipMalloc((void **)&dev, v.size() * sizeof(T));
@@ -144,6 +146,7 @@ template <class T> hipError_t upload(const std::vector<T> &v, T *&dev) {
         (void)hipFree(dev);
         dev = nullptr;
     }
+    if (e != hipSuccess) (void)hipGetLastError();
     return e;
 }
 
@@ -203,7 +206,10 @@ int get_area_div(tsvpp_ctx *ctx, float xr, float yr, const AreaTable &tx, const 
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         // (the NULL stream is never queried: asking the legacy stream while another stream captures in global mode invalidates that capture)
         if (stream && hipStreamIsCapturing(stream, &cap) != hipSuccess) (void)hipGetLastError();
-        if (cap != hipStreamCaptureStatusNone) return TSVPP_OK; // no allocation, no synchronous copy during capture
+        if (cap != hipStreamCaptureStatusNone) { // no allocation, no synchronous copy during capture
+            g_build_declined = true;
+            return TSVPP_OK;
+        }
         const int tx4 = 4 * tx.nk, ty4 = 4 * ty.nk;
         std::vector<float> tab((size_t)tx.rows * ty.rows);
         for (int jx = 0; jx < tx.rows; jx++) {

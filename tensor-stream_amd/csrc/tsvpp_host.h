@@ -67,12 +67,27 @@ struct RoiPlan {
     int down = 0, taps_x = 0, taps_y = 0; // AREA: boxes on the down-scale path, their largest tap counts
 };
 
+// An int that tsvpp_set_option / tsvpp_enable_markers may write while conversions on other threads read it (include/tsvpp.h: options may be set beside
+// conversions).  Relaxed atomic accesses -- plain loads and stores on x86: the replay hit pays nothing for them -- and copyable, so that Knobs stays plain data.
+// A writer stores the value FIRST and moves tsvpp_ctx::epoch afterwards; a conversion loads the epoch (acquire) before it reads any option, so a launch is never
+// remembered under an epoch newer than the values it was built from.
+struct OptInt {
+    std::atomic<int> v;
+    OptInt(int x = 0) : v(x) {}
+    OptInt(const OptInt &o) : v(o.load()) {}
+    OptInt &operator=(const OptInt &o) { store(o.load()); return *this; }
+    OptInt &operator=(int x) { store(x); return *this; }
+    operator int() const { return load(); }
+    int load() const { return v.load(std::memory_order_relaxed); }
+    void store(int x) { v.store(x, std::memory_order_relaxed); }
+};
+
 // Everything of a context that the launch descriptor is filled from (fill_desc): the tuning knobs (read_env_knobs) and the two options the API sets that
 // travel in the descriptor.  Plain data: tsvpp_describe makes one of its own, without a context.  A knob that travels in the descriptor has its LaunchDesc
 // member's name; kKnobs (tsvpp_api.cpp) is the one place that says which environment variable sets it and where it goes.
 struct Knobs {
-    tsvpp_coeffs coeffs;                // tsvpp_set_coeffs
-    int color_g = 0;                    // TSVPP_OPT_COLOR_G_TERM
+    tsvpp_coeffs coeffs;                // tsvpp_set_coeffs (a quiescent context only: include/tsvpp.h)
+    OptInt color_g;                     // TSVPP_OPT_COLOR_G_TERM
     int force_gather = 0;               // TSVPP_FORCE_GATHER=1: always use the global-gather kernel (A/B, tests)
     int nt_stores = -1, tile_order = 0, shape_tx = 0, shape_ty = 0; // TSVPP_NT (0 plain, 1 nt, 2 sc1; -1 = per kernel), TSVPP_TILE_ORDER, TSVPP_SHAPE=tx,ty
     int num_cus = 256;                  // compute units of the device (tsvpp_create reads it; 256 without a device)
@@ -135,13 +150,13 @@ struct tsvpp_ctx {
     std::map<void *, std::unique_ptr<ScratchSlot>> scratch;
     std::vector<uint8_t *> retired;
     std::mutex scratch_mu;
-    int markers = 0; // tsvpp_enable_markers: roctx ranges around every conversion (the reference's NVTX ranges)
-    int inputs_ready = 0; // TSVPP_OPT_INPUTS_READY: fused launches do not wait for earlier work on their stream (include/tsvpp.h)
+    tsvpp::OptInt markers; // tsvpp_enable_markers: roctx ranges around every conversion (the reference's NVTX ranges)
+    tsvpp::OptInt inputs_ready; // TSVPP_OPT_INPUTS_READY: fused launches do not wait for earlier work on their stream (include/tsvpp.h)
     // Replay cache (convert_impl): a thread keeps the finished launches of its last requests, keyed by this context's id and epoch.  The epoch moves whenever
     // something a finished launch descriptor depends on changes or may be freed: tsvpp_set_coeffs, tsvpp_set_option, tsvpp_enable_markers, tsvpp_trim.
     uint64_t id = 0;
     std::atomic<uint64_t> epoch{ 1 };
-    int unsafe_coeffs = 0; // TSVPP_OPT_UNSAFE_COEFFS: tsvpp_set_coeffs accepts a block that differs from the defaults
+    tsvpp::OptInt unsafe_coeffs; // TSVPP_OPT_UNSAFE_COEFFS: tsvpp_set_coeffs accepts a block that differs from the defaults
     std::set<struct tsvpp_table *> tables; // live frame tables: released with the context if the caller destroys it first
     std::mutex tables_mu;
 };

@@ -102,11 +102,28 @@ int tsvpp_table_set(tsvpp_table *table, int first, int n, const tsvpp_nv12 *in, 
     if (sts != TSVPP_OK) return sts;
     DeviceGuard guard(table->ctx);
     if (guard.status != TSVPP_OK) return guard.status;
+    // Not on a capturing stream (include/tsvpp.h): the copies would become graph nodes that read a staging slot at every replay, long after later uploads have
+    // rewritten it, and the event behind them a captured event that nobody can wait for -- the slot would stay busy for good.  Refused before a slot is touched.
+    // (the NULL stream is never queried: asking the legacy stream while another stream captures in global mode invalidates that capture)
+    if (stream) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone) return TSVPP_UNSUPPORTED;
+    }
     // this upload's staging slot: wait for the copies that last read it, grow it if needed
     tsvpp_table::Slot &sl = table->slots[table->next_slot];
     if (sl.busy) {
         const hipError_t e = hipEventSynchronize(sl.done);
-        if (e != hipSuccess) return (int)e;
+        if (e != hipSuccess) {
+            // the wait itself was refused: the event is of no use any more.  The slot is reset -- a fresh event on its next use, its buffer kept -- and this call
+            // reports the error; the next upload takes the slot as free instead of failing for as long as the table lives.
+            (void)hipGetLastError();
+            (void)hipEventDestroy(sl.done);
+            sl.done = nullptr;
+            sl.busy = false;
+            table->next_slot = (table->next_slot + 1) % tsvpp_table::kSlots; // (its buffer rests for three uploads: a copy may still be reading it)
+            return (int)e;
+        }
         sl.busy = false;
     }
     if (sl.entries < (size_t)n) {
@@ -121,7 +138,7 @@ int tsvpp_table_set(tsvpp_table *table, int first, int n, const tsvpp_nv12 *in, 
     }
     if (!sl.done) {
         const hipError_t e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-        if (e != hipSuccess) return (int)e;
+        if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; } // (reported here: the thread's next launch must not find it)
     }
     for (int f = 0; f < n; f++) {
         sl.buf[f] = (uint64_t)(uintptr_t)in[f].y;

@@ -530,7 +530,10 @@ const BcEntry *bicubic_cols_tables(const LaunchDesc &d, hipStream_t stream, bool
         if (!may_build) return nullptr;
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         // (the NULL stream is never queried: asking the legacy stream while another stream captures in global mode invalidates that capture)
-        if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return nullptr;
+        if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            g_build_declined = true;
+            return nullptr;
+        }
         if (!geo_cache_make_room(cache)) return nullptr;
         std::vector<uint8_t> buf;
         auto append = [&](const void *p, size_t n) {

@@ -653,7 +653,10 @@ static bool geo_lookup(GeoCache *cache, bool areaup, const LaunchDesc &d, hipStr
         if (!may_build) return false;
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         // (the NULL stream is never queried: asking the legacy stream while another stream captures in global mode invalidates that capture)
-        if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return false;
+        if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            g_build_declined = true;
+            return false;
+        }
         if (!geo_cache_make_room(cache)) return false;
         GeoHost g;
         GeoEntry e;
@@ -670,8 +673,13 @@ static bool geo_lookup(GeoCache *cache, bool areaup, const LaunchDesc &d, hipStr
             memcpy(host.data() + e.off_ty, g.ty.data(), b_ty);
             memcpy(host.data() + e.off_col, g.col.data(), b_col);
             memcpy(host.data() + e.off_row, g.row.data(), b_row);
-            if (hipMalloc((void **)&e.dev, total) != hipSuccess) return false;
+            // (a failure here only costs the tables: the launch goes on with the self-computing kernel, and its `return hipGetLastError()` must not report it)
+            if (hipMalloc((void **)&e.dev, total) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
             if (hipMemcpy(e.dev, host.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipGetLastError();
                 (void)hipFree(e.dev);
                 return false;
             }

@@ -196,6 +196,10 @@ struct LaunchRecord {
     LaunchDesc d;
 };
 extern thread_local LaunchRecord *g_launch_rec;
+// Set by a table cache that DECLINED to build what the launch wanted because its stream is being captured (geo_lookup, bicubic_cols_tables, get_area_div): the
+// launch that follows is the self-computing fallback, right for this call and wrong to remember -- the next ordinary call builds the tables.  A flag of the
+// thread rather than of the record: the AREA divisor table is looked up before a record is armed.  convert_impl clears it per conversion.
+extern thread_local bool g_build_declined;
 inline void record_launch(const void *fn, dim3 grid, dim3 block, size_t lds, const LaunchDesc &d) {
     LaunchRecord *r = g_launch_rec;
     if (!r) return;

@@ -69,6 +69,21 @@ typedef struct tsvpp_nv12 {
     int32_t height;
 } tsvpp_nv12;
 
+/* The source limit.  Inside one plane the kernels address with unsigned 32-bit byte offsets, counted from the address they are handed -- and the kernels
+ * that fetch 16-byte chunks count from the 16-byte boundary at or below it, up to 15 bytes earlier.  The SPAN of a plane, as seen from that address,
+ *     span = (rows - 1) * pitch + row_bytes
+ * must therefore stay below TSVPP_SOURCE_SPAN_LIMIT = 2^32 - 16, for the luma plane (rows, row_bytes = height, width of the region) and for the chroma
+ * plane (height / 2, width) each, with each plane's own pitch.  The region, and the address it is seen from, is
+ *   tsvpp_convert / _batch / _table, tsvpp_describe      the crop box where Convert's crop stage applies (the planes advanced to its origin), else the frame;
+ *   tsvpp_convert_rois / _rois_area / _rois_tensor       each box (the planes advanced to the box's origin): a small box in a huge frame is legal;
+ *   letterbox, warp, perspective, remap, mesh            the whole frame.
+ * A request with a span at or above the limit is TSVPP_UNSUPPORTED, from the describe call and the convert call alike, before anything is launched.  It comes
+ * after the TSVPP_ERROR rules on the request itself (sizes, crop, boxes, pitches), which the describe calls share; the convert calls look at their pointers
+ * only afterwards, so a null plane or output pointer together with an over-limit span answers TSVPP_UNSUPPORTED, not TSVPP_ERROR.  Spans of 2^31 and more are
+ * ordinary requests.  A pitch travels in 32 bits (below 2^31); a coordinate map or control grid is addressed
+ * with 64-bit offsets and has no such limit; an output stays below 2^32 bytes (each call's own rule). */
+#define TSVPP_SOURCE_SPAN_LIMIT 0xFFFFFFF0ull
+
 /* Flat mirror of FrameParameters {ResizeOptions, ColorOptions, CropOptions}
  * (reference include/VideoProcessor.h:39-105).  Zero-initialised == the
  * reference defaults except fourcc/planes (reference: RGB24, MERGED). */

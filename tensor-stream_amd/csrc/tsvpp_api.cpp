@@ -337,7 +337,8 @@ int tsvpp::convert_impl(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp
     int sts = make_plan(p, in[0].width, in[0].height, pl);
     if (sts != TSVPP_OK) return sts;
     const int pitch_y = pitch_or_width(in[0].pitch_y, in[0].width), pitch_uv = pitch_or_width(in[0].pitch_uv, in[0].width);
-    if (pitch_y < in[0].width || pitch_uv < in[0].width) return TSVPP_ERROR;
+    sts = plan_source_status(pl, in[0].width, pitch_y, pitch_uv);
+    if (sts != TSVPP_OK) return sts;
     // dst_w is even; when it is 4 k + 2 launch_fused shifts the launch's last tile column to the frame's right edge (or, where it cannot, the
     // vector-store kernels skip the two-column tail of every row and a tiny element-wise launch converts it); rows then start 8 bytes / 2 bytes
     // off the vector alignment, which global stores tolerate.
@@ -736,7 +737,9 @@ int tsvpp_describe(const tsvpp_params *p, int in_width, int in_height, int pitch
     if (sts != TSVPP_OK) return sts;
     pitch_y = pitch_or_width(pitch_y, in_width);
     pitch_uv = pitch_or_width(pitch_uv, in_width);
-    if (pitch_y < in_width || pitch_uv < in_width || n_frames < 1) return TSVPP_ERROR;
+    if (n_frames < 1) return TSVPP_ERROR;
+    sts = plan_source_status(pl, in_width, pitch_y, pitch_uv);
+    if (sts != TSVPP_OK) return sts;
     Knobs kn; // no context: no device, no streams
     read_env_knobs(kn);
     LaunchDesc d;

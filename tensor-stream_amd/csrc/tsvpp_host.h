@@ -219,6 +219,14 @@ inline CropOff plane_offsets(int left, int top, int pitch_y, int pitch_uv) {
 }
 inline CropOff crop_offsets(const Plan &pl, int pitch_y, int pitch_uv) { return plane_offsets(pl.off_x, pl.off_y, pitch_y, pitch_uv); }
 
+// The source limit (include/tsvpp.h: TSVPP_SOURCE_SPAN_LIMIT): a region of w x h luma pixels as the kernels see it from the plane addresses advanced to its
+// origin -- the crop box, a ROI box, or the whole frame.  (w, h > 0 and even, pitches >= w: the callers have checked.)  The kernels' offsets are unsigned 32-bit
+// products (profiles/addressing_limits.txt), the chunked ones counted from up to 15 bytes below the address.
+inline bool plane_span_ok(int rows, int pitch, int row_bytes) { return (uint64_t)(rows - 1) * (uint64_t)pitch + (uint64_t)row_bytes < TSVPP_SOURCE_SPAN_LIMIT; }
+inline int source_span_status(int w, int h, int pitch_y, int pitch_uv) {
+    return plane_span_ok(h, pitch_y, w) && plane_span_ok(h >> 1, pitch_uv, w) ? TSVPP_OK : TSVPP_UNSUPPORTED;
+}
+
 // LaunchDesc::in_aligned4 for one frame: `y` / `uv` are its crop-adjusted plane addresses (the bare crop offsets where the frame itself is taken as aligned)
 inline bool planes_aligned4(int pitch_y, int pitch_uv, uintptr_t y, uintptr_t uv) { return pitch_y % 4 == 0 && pitch_uv % 4 == 0 && y % 4 == 0 && uv % 4 == 0; }
 
@@ -253,6 +261,9 @@ inline constexpr const char *out_names[O_COUNT_ALL] = { "u8_planar", "u8_merged"
 // ---- functions that cross files ----------------------------------------------------------------------------------------------------------------------
 // tsvpp_plan.cpp
 int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl);
+// (tsvpp_convert* / tsvpp_describe, after make_plan) the rules about the source planes: TSVPP_ERROR for a pitch below the frame's width, TSVPP_UNSUPPORTED for a
+// plane span at or above TSVPP_SOURCE_SPAN_LIMIT as seen from the plan's source origin
+int plan_source_status(const Plan &pl, int in_w, int pitch_y, int pitch_uv);
 int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl, bool area = false);
 // (tsvpp_convert_letterbox / tsvpp_describe_letterbox; RoiPlan: the canvas is its dst_w x dst_h).  letterbox_rect_of: frame k's rectangle, the caller's or the default
 int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);

@@ -140,6 +140,14 @@ int tile_request_odd(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *fram
         if ((frames[f].width | frames[f].height) & 1) return TSVPP_UNSUPPORTED;
     return TSVPP_OK;
 }
+// TSVPP_UNSUPPORTED class: a frame whose plane spans the kernels' 32-bit offsets cannot carry (the calls that sample the whole frame; tile_request_odd has passed)
+int tile_frame_spans(int n_frames, const tsvpp_nv12 *frames) {
+    for (int f = 0; f < n_frames; f++) {
+        const tsvpp_nv12 &fr = frames[f];
+        if (source_span_status(fr.width, fr.height, pitch_or_width(fr.pitch_y, fr.width), pitch_or_width(fr.pitch_uv, fr.width)) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    }
+    return TSVPP_OK;
+}
 // TSVPP_UNSUPPORTED class: the resize type (`area`: the entry point answers AREA and nothing else), the output flavour and size, the grid of launches of up to
 // `max_items` items
 int tile_output_plan(const tsvpp_params *p, bool area, int max_items, RoiPlan &pl) {
@@ -228,6 +236,13 @@ int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl) {
     return TSVPP_OK;
 }
 
+// What Convert's source planes add to make_plan's answer (tsvpp_convert*, tsvpp_describe): pitches of 0 resolved by the caller.  The region the kernels see is the
+// plan's source -- the crop box, the planes advanced to its origin -- or the whole frame.
+int plan_source_status(const Plan &pl, int in_w, int pitch_y, int pitch_uv) {
+    if (pitch_y < in_w || pitch_uv < in_w) return TSVPP_ERROR;
+    return source_span_status(pl.src_w, pl.src_h, pitch_y, pitch_uv);
+}
+
 int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl, bool area) {
     // TSVPP_ERROR: arguments that describe no request at all
     if (!p || !frames || !rois || n_frames <= 0 || n_rois <= 0) return TSVPP_ERROR;
@@ -242,6 +257,12 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     for (int i = 0; i < n_rois; i++)
         if (((rois[i].right - rois[i].left) | (rois[i].bottom - rois[i].top)) & 1) return TSVPP_UNSUPPORTED;
+    for (int i = 0; i < n_rois; i++) { // the source limit, per box: the kernel is handed the planes advanced to the box's origin
+        const tsvpp_nv12 &fr = frames[rois[i].frame];
+        if (source_span_status(rois[i].right - rois[i].left, rois[i].bottom - rois[i].top, pitch_or_width(fr.pitch_y, fr.width),
+                               pitch_or_width(fr.pitch_uv, fr.width)) != TSVPP_OK)
+            return TSVPP_UNSUPPORTED;
+    }
     // AREA has an entry point of its own (tsvpp_convert_rois_area: its down-scale generates weight rows per tile), which answers nothing else
     if (tile_output_plan(p, area, TSVPP_MAX_ROIS, pl) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     if (area) {
@@ -281,6 +302,7 @@ int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsv
     if (tile_request_odd(p, n, in) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     for (int f = 0; rects && f < n; f++) // (the default rectangle of an even canvas is even)
         if ((rects[f].left | rects[f].top | rects[f].width | rects[f].height) & 1) return TSVPP_UNSUPPORTED;
+    if (tile_frame_spans(n, in) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     // AREA: its down-scale needs weight rows (vpp_rois_area.hip generates them per tile); not in this kernel yet.  The rectangle travels in 32-bit fields: a canvas
     // side has no limit of its own, the grid has
     return tile_output_plan(p, false, TSVPP_MAX_LETTERBOX, pl);
@@ -302,6 +324,7 @@ int matrix_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, i
             if (!std::isfinite((recs[i].*entries)[k])) return TSVPP_ERROR;
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     // NEAREST, BICUBIC and AREA warps: follow-ups
     if (tile_output_plan(p, false, limit, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
     // with every entry inside 2^24 and indices below 2^31 no numerator or denominator overflows: every one is finite
@@ -345,6 +368,7 @@ int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, in
     }
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     if (tile_output_plan(p, false, TSVPP_MAX_REMAPS, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
     return TSVPP_OK;
 }
@@ -367,6 +391,7 @@ int mesh_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
     }
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     if (tile_output_plan(p, false, TSVPP_MAX_MESHES, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
     for (int m = 0; m < n_meshes; m++) {
         if (meshes[m].log2_cw < MESH_LOG2_MIN || meshes[m].log2_cw > MESH_LOG2_MAX) return TSVPP_UNSUPPORTED;

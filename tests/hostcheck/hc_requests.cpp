@@ -8,7 +8,8 @@
 //            device while the thread's current device is the first
 //   tile     the describe and the convert call of the ROI / AREA-ROI / letterbox / warp / perspective families (tensor forms included) for the same arguments
 //   remap, mesh   the same with map / mesh buffers behind the stub's "device" pointers, and the host-side helpers on the host copies
-// then the helper entry points on valid inputs and on every refusal the header names, and last a subset of the requests with the n-th allocation failing,
+// then the helper entry points on valid inputs and on every refusal the header names, the source limit (plane spans one byte under TSVPP_SOURCE_SPAN_LIMIT and at
+// it through every describe / convert pair: source_spans), and last a subset of the requests with the n-th allocation failing,
 // n = 1, 2, 3 ... until the call succeeds.
 // Exit status 0 only without a failed assertion, a stub violation, or anything the stub still holds at the end.
 #include <cmath>
@@ -529,6 +530,131 @@ void refusals(const Env &e) {
     HC_CHECK(tsvpp_set_coeffs(e.ctx, &k) == TSVPP_UNSUPPORTED, "a block that differs from the defaults, without TSVPP_OPT_UNSAFE_COEFFS");
 }
 
+// ---- the source limit (include/tsvpp.h: TSVPP_SOURCE_SPAN_LIMIT) -------------------------------------------------------------------------------------------------
+// Every describe / convert pair on frames whose plane spans lie one byte under the limit (accepted, launched) and at it (TSVPP_UNSUPPORTED, nothing launched), luma
+// and chroma separately, and on a small crop / box inside a frame far beyond the limit.  Nothing of these sizes is allocated: the stub records launches, and the
+// library's host arithmetic on the pitches is what the sanitizers see.
+struct SpanGeom { int w, h, py, puv; };
+// an even width and pitches with (rows - 1) * pitch + w == span, for the luma plane (h rows) and the chroma plane (h / 2 rows) each; span 0: an ordinary pitch (wide enough for a frame 128 columns wider)
+SpanGeom span_geom(int h, uint64_t span_y, uint64_t span_uv) {
+    for (int w = 32; w < 8192; w += 2) {
+        if (span_y && (span_y - (uint64_t)w) % (uint64_t)(h - 1)) continue;
+        if (span_uv && (span_uv - (uint64_t)w) % (uint64_t)(h / 2 - 1)) continue;
+        const uint64_t py = span_y ? (span_y - (uint64_t)w) / (uint64_t)(h - 1) : (uint64_t)((w + 128 + 15) & ~15);
+        const uint64_t puv = span_uv ? (span_uv - (uint64_t)w) / (uint64_t)(h / 2 - 1) : (uint64_t)((w + 128 + 15) & ~15);
+        if (py < (1ull << 31) && puv < (1ull << 31)) return SpanGeom{ w, h, (int)py, (int)puv };
+    }
+    std::fprintf(stderr, "hc_requests: no geometry for spans %llu / %llu\n", (unsigned long long)span_y, (unsigned long long)span_uv);
+    std::exit(3);
+}
+
+void expect_span(int ds, int cs, int want, const char *call, const char *what) {
+    HC_CHECK(ds == want && cs == want, "%s, %s: describe answers %d, convert %d, expected %d", call, what, ds, cs, want);
+    if (want == TSVPP_OK) HC_CHECK(hc_stub_launch_count() >= 1, "%s, %s: accepted and nothing launched", call, what);
+    else HC_CHECK(hc_stub_launch_count() == 0, "%s, %s: refused and %zu launches recorded", call, what, hc_stub_launch_count());
+    hc_stub_clear_launches();
+}
+
+// tsvpp_describe / tsvpp_convert / _batch / _table on `fr` with the crop of `p`
+void plain_span_case(const Env &e, const tsvpp_nv12 &fr, const tsvpp_params &p, int want, const char *what) {
+    char desc[512];
+    void *out = e.out;
+    hc_stub_clear_launches();
+    const int ds = tsvpp_describe(&p, fr.width, fr.height, fr.pitch_y, fr.pitch_uv, 1, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert(e.ctx, &fr, &p, e.out, e.stream), want, "tsvpp_convert", what);
+    expect_span(ds, tsvpp_convert_batch(e.ctx, 1, &fr, &p, &out, e.stream), want, "tsvpp_convert_batch", what);
+    tsvpp_table *tab = nullptr;
+    HC_CHECK(tsvpp_table_create(e.ctx, 4, &tab) == TSVPP_OK && tab, "table_create");
+    if (!tab) return;
+    HC_CHECK(tsvpp_table_set(tab, 1, 1, &fr, &out, e.stream) == TSVPP_OK, "table_set: %s", what);
+    hc_stub_clear_launches();
+    expect_span(ds, tsvpp_convert_table(e.ctx, tab, 1, 1, &p, e.stream), want, "tsvpp_convert_table", what);
+    tsvpp_table_destroy(tab);
+}
+
+// the ROI calls on one box of `fr`
+void rois_span_case(const Env &e, const tsvpp_nv12 &fr, const tsvpp_roi &box, int want, const char *what) {
+    char desc[512];
+    void *out = e.out;
+    tsvpp_params p = {};
+    p.dst_width = 64, p.dst_height = 32, p.resize_type = TSVPP_BILINEAR, p.fourcc = TSVPP_RGB24, p.planes = TSVPP_PLANAR, p.normalization = 1;
+    const tsvpp_tensor_spec spec = { TSVPP_F32, { 0.f, 0.f, 0.f }, { 1.f, 1.f, 1.f } };
+    hc_stub_clear_launches();
+    int ds = tsvpp_describe_rois(&p, 1, &fr, 1, &box, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_rois(e.ctx, 1, &fr, 1, &box, &p, &out, e.stream), want, "tsvpp_convert_rois", what);
+    ds = tsvpp_describe_rois_tensor(&p, &spec, 1, &fr, 1, &box, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_rois_tensor(e.ctx, 1, &fr, 1, &box, &p, &spec, &out, e.stream), want, "tsvpp_convert_rois_tensor", what);
+    p.resize_type = TSVPP_AREA;
+    p.dst_width = 16, p.dst_height = 8;
+    ds = tsvpp_describe_rois_area(&p, 1, &fr, 1, &box, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_rois_area(e.ctx, 1, &fr, 1, &box, &p, &out, e.stream), want, "tsvpp_convert_rois_area", what);
+}
+
+// the calls that sample the whole frame: letterbox, warp, perspective, remap, mesh and their tensor forms
+void frame_span_case(const Env &e, const tsvpp_nv12 &fr, int want, const char *what) {
+    char desc[512];
+    void *out = e.out;
+    tsvpp_params p = {};
+    p.dst_width = 64, p.dst_height = 32, p.resize_type = TSVPP_BILINEAR, p.fourcc = TSVPP_RGB24, p.planes = TSVPP_PLANAR, p.normalization = 1;
+    const tsvpp_tensor_spec spec = { TSVPP_F32, { 0.f, 0.f, 0.f }, { 1.f, 1.f, 1.f } };
+    const tsvpp_warp warp = { 0, { (float)fr.width / 64.f, 0.f, 0.f, 0.f, (float)fr.height / 32.f, 0.f } };
+    const tsvpp_persp persp = { 0, { warp.m[0], 0.f, 0.f, 0.f, warp.m[4], 0.f, 0.f, 0.f, 1.f } };
+    const tsvpp_map map = { (const float *)e.out, 0, 0 };   // (never read: the stub executes nothing)
+    const tsvpp_mesh mesh = { (const float *)e.out, 0, 4, 4, 0 };
+    const tsvpp_remap pair = { 0, 0 };
+    hc_stub_clear_launches();
+    int ds = tsvpp_describe_letterbox(&p, 1, &fr, nullptr, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_letterbox(e.ctx, 1, &fr, &p, nullptr, 114, 128, 128, &out, e.stream), want, "tsvpp_convert_letterbox", what);
+    ds = tsvpp_describe_letterbox_tensor(&p, &spec, 1, &fr, nullptr, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_letterbox_tensor(e.ctx, 1, &fr, &p, &spec, nullptr, 114, 128, 128, &out, e.stream), want, "tsvpp_convert_letterbox_tensor", what);
+    ds = tsvpp_describe_warp(&p, 1, &fr, 1, &warp, -1, -1, -1, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_warp(e.ctx, 1, &fr, 1, &warp, &p, -1, -1, -1, &out, e.stream), want, "tsvpp_convert_warp", what);
+    ds = tsvpp_describe_warp_tensor(&p, &spec, 1, &fr, 1, &warp, 16, 128, 128, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_warp_tensor(e.ctx, 1, &fr, 1, &warp, &p, &spec, 16, 128, 128, &out, e.stream), want, "tsvpp_convert_warp_tensor", what);
+    ds = tsvpp_describe_perspective(&p, 1, &fr, 1, &persp, -1, -1, -1, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_perspective(e.ctx, 1, &fr, 1, &persp, &p, -1, -1, -1, &out, e.stream), want, "tsvpp_convert_perspective", what);
+    ds = tsvpp_describe_perspective_tensor(&p, &spec, 1, &fr, 1, &persp, 16, 128, 128, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_perspective_tensor(e.ctx, 1, &fr, 1, &persp, &p, &spec, 16, 128, 128, &out, e.stream), want, "tsvpp_convert_perspective_tensor", what);
+    ds = tsvpp_describe_remap(&p, 1, &fr, 1, &map, 1, &pair, -1, -1, -1, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_remap(e.ctx, 1, &fr, 1, &map, 1, &pair, &p, -1, -1, -1, &out, e.stream), want, "tsvpp_convert_remap", what);
+    ds = tsvpp_describe_remap_tensor(&p, &spec, 1, &fr, 1, &map, 1, &pair, 16, 128, 128, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_remap_tensor(e.ctx, 1, &fr, 1, &map, 1, &pair, &p, &spec, 16, 128, 128, &out, e.stream), want, "tsvpp_convert_remap_tensor", what);
+    ds = tsvpp_describe_mesh(&p, 1, &fr, 1, &mesh, 1, &pair, -1, -1, -1, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_mesh(e.ctx, 1, &fr, 1, &mesh, 1, &pair, &p, -1, -1, -1, &out, e.stream), want, "tsvpp_convert_mesh", what);
+    ds = tsvpp_describe_mesh_tensor(&p, &spec, 1, &fr, 1, &mesh, 1, &pair, 16, 128, 128, 1, desc, sizeof(desc));
+    expect_span(ds, tsvpp_convert_mesh_tensor(e.ctx, 1, &fr, 1, &mesh, 1, &pair, &p, &spec, 16, 128, 128, &out, e.stream), want, "tsvpp_convert_mesh_tensor", what);
+}
+
+void source_spans(const Env &e) {
+    const uint64_t L = TSVPP_SOURCE_SPAN_LIMIT;
+    const struct { uint64_t y, uv; int want; const char *what; } cases[] = {
+        { L - 1, L - 1, TSVPP_OK, "both planes one byte under the limit" },
+        { (1ull << 31) + 1, (1ull << 31) + 1, TSVPP_OK, "both planes just past 2^31" },
+        { L, 0, TSVPP_UNSUPPORTED, "the luma plane at the limit" },
+        { 0, L, TSVPP_UNSUPPORTED, "the chroma plane at the limit" },
+        { L - 1, L, TSVPP_UNSUPPORTED, "luma one byte under, chroma at the limit" },
+        { 1ull << 32, 1ull << 32, TSVPP_UNSUPPORTED, "both planes at 2^32" },
+    };
+    tsvpp_params whole = {};
+    whole.dst_width = 64, whole.dst_height = 32, whole.resize_type = TSVPP_BILINEAR, whole.fourcc = TSVPP_RGB24, whole.planes = TSVPP_PLANAR, whole.normalization = 1;
+    for (const auto &c : cases) {
+        const SpanGeom g = span_geom(16, c.y, c.uv);
+        const tsvpp_nv12 fr = { e.y, e.uv, g.py, g.puv, g.w, g.h };
+        plain_span_case(e, fr, whole, c.want, c.what);
+        frame_span_case(e, fr, c.want, c.what);
+        const tsvpp_roi all = { 0, 0, 0, g.w, g.h };
+        rois_span_case(e, fr, all, c.want, c.what);
+        // the same planes as rows 100 .. 115, columns 64 .. 64 + w of a frame 400 rows high: the crop / box decides, the frame (beyond the limit in every case) does not
+        const tsvpp_nv12 big = { e.y, e.uv, g.py, g.puv, g.w + 128, 400 };
+        tsvpp_params crop = whole;
+        crop.crop_left = 64, crop.crop_top = 100, crop.crop_right = 64 + g.w, crop.crop_bottom = 100 + g.h;
+        plain_span_case(e, big, crop, c.want, c.what);
+        const tsvpp_roi box = { 0, 64, 100, 64 + g.w, 100 + g.h };
+        rois_span_case(e, big, box, c.want, c.what);
+        if (c.want == TSVPP_OK) frame_span_case(e, big, TSVPP_UNSUPPORTED, "a frame beyond the limit whatever the request reads of it");
+    }
+}
+
 // ---- allocation failures: the n-th allocation of a call fails, n = 1, 2, 3 ... until the call succeeds ---------------------------------------------------------
 // Every failing call returns a non-OK status; the context it failed in still converts, and is destroyed.  What must not happen: a leak (the stub's live count and
 // the leak check at exit), a stale runtime error that the next launch reports, a half-built cache entry.
@@ -630,6 +756,7 @@ int main(int argc, char **argv) {
     HC_CHECK(counts[0] > 0 && counts[1] > 0 && counts[2] > 0 && counts[3] > 0, "the request file holds every kind of request");
     helpers();
     refusals(e);
+    source_spans(e);
     allocation_failures(e);
     tsvpp_destroy(e.ctx);
     (void)hipFree(e.y);

@@ -260,3 +260,135 @@ def test_the_baseline_requests_select_the_kernels_the_profiles_name():
     for name, entry in traffic.items():
         if name in want and entry.get("kernel"):
             assert entry["kernel"].split("::")[-1] == want[name], (name, entry["kernel"], entry.get("round"))
+
+
+# ---- the source limit (include/tsvpp.h: TSVPP_SOURCE_SPAN_LIMIT) ------------------------------------------------------------------------------------------------
+# The kernels address a plane with unsigned 32-bit offsets from the address they are handed (profiles/addressing_limits.txt): a plane whose span
+# (rows - 1) * pitch + row_bytes, seen from there, reaches the limit is TSVPP_UNSUPPORTED in every describe call (tests/hostcheck/hc_requests.cpp: the convert
+# calls agree); one byte under it the request is an ordinary one -- it selects what the same request selects at an everyday pitch of the same residue mod 16.
+SPAN_LIMIT = (1 << 32) - 16
+SPAN_H = 16  # rows of the test frames: 15 luma and 7 chroma row steps, so both pitches stay below 2^31
+
+
+def span_geometry(span_y, span_uv, h=SPAN_H):
+    """(w, h, pitch_y, pitch_uv): an even width and pitches with (rows - 1) * pitch + w == span for the luma plane (h rows) and the chroma plane (h / 2 rows)
+    each; a span of None: an everyday pitch, the width + 128 rounded up to 16 (so that a frame 128 columns wider can hold the region)"""
+    for w in range(32, 8192, 2):
+        if (span_y is None or (span_y - w) % (h - 1) == 0) and (span_uv is None or (span_uv - w) % (h // 2 - 1) == 0):
+            py = (w + 128 + 15) // 16 * 16 if span_y is None else (span_y - w) // (h - 1)
+            puv = (w + 128 + 15) // 16 * 16 if span_uv is None else (span_uv - w) // (h // 2 - 1)
+            if py < (1 << 31) and puv < (1 << 31):
+                return w, h, py, puv
+    raise AssertionError((span_y, span_uv, h))
+
+
+def everyday(w, pitch):
+    """the least pitch >= w with pitch's residue mod 16"""
+    return w + (pitch - w) % 16
+
+
+def _fp(dst, rt=B, fourcc=RGB24, planes=0, norm=True, crop=(0, 0, 0, 0)):
+    return ts.FrameParameters(width=dst[0], height=dst[1], crop_coords=crop, resize_type=rt, pixel_format=fourcc, planes_pos=planes, normalization=norm)
+
+
+def _describers():
+    """{name: f(frame=(w, h, pitch_y, pitch_uv)) -> describe's dict}: every describe entry point, the plain one with several kernels behind it; the frame is the
+    region the source limit is about (the whole frame, or the box of the ROI calls)"""
+    def plain(dst_of, **kw):
+        def f(fr):
+            w, h, py, puv = fr
+            return ts.describe(_fp(dst_of(w, h), **kw), w, h, pitch=py, pitch_uv=puv, n_frames=1)
+        return f
+
+    def warp_m(w, h):
+        return (w / 64.0, 0.0, 0.0, 0.0, h / 32.0, 0.0)
+
+    import torch
+    t = dict(dtype=torch.float16)
+    return {
+        "describe:colour-only": plain(lambda w, h: (0, 0), rt=N),
+        "describe:bilinear-up": plain(lambda w, h: (2 * w, 2 * h)),
+        "describe:bilinear-down-u8": plain(lambda w, h: (w // 4 * 2, h // 2), norm=False),
+        "describe:bicubic": plain(lambda w, h: (w // 3 // 2 * 2 + 2, 10), rt=C),
+        "describe:area-down": plain(lambda w, h: (w // 4 * 2, h // 2), rt=A, planes=1),
+        "describe:nearest-y800": plain(lambda w, h: (w // 3 // 2 * 2, 6), rt=N, fourcc=Y800),
+        "describe:uyvy": plain(lambda w, h: (0, 0), rt=N, fourcc=UYVY, norm=False),
+        "describe_rois": lambda fr: ts.describe_rois(_fp((64, 32)), fr, [(0, 0, fr[0], fr[1])]),
+        "describe_rois_area": lambda fr: ts.describe_rois_area(_fp((16, 8), rt=A), fr, [(0, 0, fr[0], fr[1])]),
+        "describe_rois_tensor": lambda fr: ts.describe_rois(_fp((64, 32)), fr, [(0, 0, fr[0], fr[1])], **t),
+        "describe_letterbox": lambda fr: ts.describe_letterbox(_fp((64, 32)), fr),
+        "describe_letterbox_tensor": lambda fr: ts.describe_letterbox(_fp((64, 32)), fr, **t),
+        "describe_warp": lambda fr: ts.describe_warp(_fp((64, 32)), fr, [warp_m(fr[0], fr[1])]),
+        "describe_warp_tensor": lambda fr: ts.describe_warp(_fp((64, 32)), fr, [warp_m(fr[0], fr[1])], border=(16, 128, 128), **t),
+        "describe_perspective": lambda fr: ts.describe_perspective(_fp((64, 32)), fr, [warp_m(fr[0], fr[1]) + (0.0, 0.0, 1.0)]),
+        "describe_perspective_tensor": lambda fr: ts.describe_perspective(_fp((64, 32)), fr, [warp_m(fr[0], fr[1]) + (0.0, 0.0, 1.0)], **t),
+        "describe_remap": lambda fr: ts.describe_remap(_fp((64, 32)), fr, (0, 0)),
+        "describe_remap_tensor": lambda fr: ts.describe_remap(_fp((64, 32)), fr, (0, 0), border=(16, 128, 128), **t),
+        "describe_mesh": lambda fr: ts.describe_mesh(_fp((64, 32)), fr, (0, 0)),
+        "describe_mesh_tensor": lambda fr: ts.describe_mesh(_fp((64, 32)), fr, (0, 0), **t),
+    }
+
+
+def test_the_header_states_the_source_limit():
+    import os
+    import re
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "tsvpp.h")).read()
+    m = re.search(r"^#define TSVPP_SOURCE_SPAN_LIMIT (0x[0-9A-Fa-f]+)ull$", header, re.M)
+    assert m and int(m.group(1), 16) == SPAN_LIMIT, m and m.group(0)
+
+
+@pytest.mark.parametrize("name", sorted(_describers()))
+def test_a_plane_span_one_byte_under_the_limit_is_an_ordinary_request_and_at_the_limit_unsupported(name):
+    f = _describers()[name]
+    for spans in ((SPAN_LIMIT - 1, SPAN_LIMIT - 1), ((1 << 31) + 1, (1 << 31) + 1), (SPAN_LIMIT - 1, None), (None, SPAN_LIMIT - 1)):
+        w, h, py, puv = span_geometry(*spans)
+        assert (spans[0] is None or (h - 1) * py + w == spans[0]) and (spans[1] is None or (h // 2 - 1) * puv + w == spans[1])
+        big, small = f((w, h, py, puv)), f((w, h, everyday(w, py), everyday(w, puv)))
+        assert big == small, f"{name}, spans {spans}: the pitches ({py}, {puv}) select\n  {big}\nthe pitches ({everyday(w, py)}, {everyday(w, puv)})\n  {small}"
+        assert big["kernel"] != "", big
+    for spans in ((SPAN_LIMIT, None), (None, SPAN_LIMIT), (SPAN_LIMIT, SPAN_LIMIT), (SPAN_LIMIT - 1, SPAN_LIMIT), (1 << 32, 1 << 32), ((1 << 32) + 2, None)):
+        w, h, py, puv = span_geometry(*spans)
+        with pytest.raises(RuntimeError, match="-2"):
+            f((w, h, py, puv))
+
+
+def test_the_source_limit_is_on_the_span_the_kernel_sees_a_small_crop_or_box_in_a_huge_frame_stays_legal():
+    """Convert's crop and the ROI boxes advance the plane addresses to their origin (64-bit host arithmetic): rows 100 .. 115, columns 64 .. 64 + w of a frame of
+    400 rows whose own spans are 25 times the limit are the request of the test above; the calls that sample the whole frame refuse that frame."""
+    import torch
+    for spans, ok in (((SPAN_LIMIT - 1, SPAN_LIMIT - 1), True), ((SPAN_LIMIT, None), False), ((None, SPAN_LIMIT), False)):
+        w, h, py, puv = span_geometry(*spans)
+        frame, box = (w + 128, 400, py, puv), (64, 100, 64 + w, 100 + h)
+        calls = {"describe": lambda fr: ts.describe(_fp((64, 32), crop=box), fr[0], fr[1], pitch=fr[2], pitch_uv=fr[3], n_frames=1),
+                 "describe_rois": lambda fr: ts.describe_rois(_fp((64, 32)), fr, [box]),
+                 "describe_rois_area": lambda fr: ts.describe_rois_area(_fp((16, 8), rt=A), fr, [box]),
+                 "describe_rois_tensor": lambda fr: ts.describe_rois(_fp((64, 32)), fr, [box], dtype=torch.bfloat16)}
+        for name, f in calls.items():
+            if ok:
+                big, small = f(frame), f((w + 128, 400, everyday(w + 128, py), everyday(w + 128, puv)))
+                assert big == small, (name, big, small)
+                assert f(frame)["kernel"]
+            else:
+                with pytest.raises(RuntimeError, match="-2"):
+                    f(frame)
+        for name in ("describe_letterbox", "describe_warp", "describe_perspective", "describe_remap", "describe_mesh"):
+            with pytest.raises(RuntimeError, match="-2"):
+                _describers()[name](frame)
+    # a box of a legal frame cannot have a span beyond the frame's; a frame beyond the limit with one legal and one illegal box is refused
+    w, h, py, puv = span_geometry(SPAN_LIMIT - 1, SPAN_LIMIT - 1)
+    frame = (w + 128, 400, py, puv)
+    with pytest.raises(RuntimeError, match="-2"):
+        ts.describe_rois(_fp((64, 32)), frame, [(64, 100, 64 + w, 100 + h), (64, 100, 64 + w, 100 + h + 2)])
+
+
+def test_the_source_limit_comes_after_every_error_rule():
+    """TSVPP_ERROR (-3) wins over the span's TSVPP_UNSUPPORTED (-2): a pitch below the width, a box outside its frame, a border component out of range"""
+    w, h, py, puv = span_geometry(SPAN_LIMIT, SPAN_LIMIT)
+    with pytest.raises(RuntimeError, match="-3"):
+        ts.describe(_fp((64, 32)), w, h, pitch=py, pitch_uv=w - 2, n_frames=1)
+    with pytest.raises(RuntimeError, match="-3"):
+        ts.describe_rois(_fp((64, 32)), (w, h, py, puv), [(0, 0, w + 2, h)])
+    with pytest.raises(RuntimeError, match="-3"):
+        ts.describe_warp(_fp((64, 32)), (w, h, py, puv), [(1.0, 0.0, 0.0, 0.0, 1.0, 0.0)], border=(300, 0, 0))
+    with pytest.raises(RuntimeError, match="-3"):
+        ts.describe_letterbox(_fp((64, 32)), (w, h, py, puv), rects=[(0, 0, 66, 32)])

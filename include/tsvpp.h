@@ -191,7 +191,7 @@ int tsvpp_convert_table(tsvpp_ctx *ctx, const tsvpp_table *table, int first, int
  * with xr = (float)width / dst_width, yr = (float)height / dst_height; for a box Convert's crop stage accepts it equals tsvpp_convert(crop = box).  A box of
  * exactly dst_width x dst_height is a plain colour conversion (every interpolation weight is zero).
  * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  TSVPP_UNSUPPORTED here: AREA (it has an entry point
- * of its own, tsvpp_convert_rois_area below), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table, per-box output sizes; rotated and affine-warped boxes are tsvpp_convert_warp's (below).
+ * of its own, tsvpp_convert_rois_area below), NV12 / UYVY / YUV444 / HSV outputs.  Neither are boxes out of a tsvpp_table; per-box output sizes are tsvpp_convert_rois_sized's (below); rotated and affine-warped boxes are tsvpp_convert_warp's (below).
  * fp16 / bf16 outputs and a per-channel mean / scale are tsvpp_convert_rois_tensor's (below), not this call's.
  * `frames`, `rois`, `outs` are HOST arrays and may be freed on return: the per-box records (plane origins, pitches, size, ratios, output pointer: 48 bytes)
  * travel BY VALUE in the kernarg segment of their launch -- no staging buffer, no copy, no allocation, no host synchronisation -- which is what bounds a
@@ -344,6 +344,61 @@ int tsvpp_convert_letterbox_tensor(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, 
                                    int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
 int tsvpp_describe_letterbox_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
                                     int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- regions of interest, each to its own output size (not in the reference) -----------------------------------------------------------------------------------
+ * tsvpp_convert_rois with the output size taken PER BOX: text lines that go to one height and a width of their own, the levels of a pyramid or preview ladder,
+ * the inputs of several heads (112 x 112, 96 x 32, 128 x 256) behind one detector pass.  With tsvpp_convert_rois that is one call per distinct size.
+ * Contract: output i is, bit for bit and in every flavour, what tsvpp_convert_rois returns for the ONE box rois[i] with p->dst_width = rois[i].dst_width and
+ * p->dst_height = rois[i].dst_height.  Ratios, the crop rule, an odd `left`, a box of exactly its output size and the replicated edges are inherited from there.
+ *   rois[i]     tsvpp_roi's fields under tsvpp_roi's rules, then dst_width / dst_height: THIS box's output size, > 0 and even.
+ *   outs[i]     tsvpp_rois_sized_bytes(p, spec, rois[i].dst_width, rois[i].dst_height) bytes of device memory, tight, laid out as tsvpp_convert_rois's output.
+ *   p           resize_type, fourcc, planes, normalization.  p->dst_width and p->dst_height MUST BE 0 (a caller who sets them believes they apply: TSVPP_ERROR);
+ *               p->crop_* must be zero.
+ * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  The tensor forms take tsvpp_convert_rois_tensor's `spec` under
+ * that block's rules, word for word: planar and Y800 only, fp16 / bf16 / fp32, outputs aligned to their element.  AREA is TSVPP_UNSUPPORTED in all four entry points,
+ * the tensor ones included: its kernel generates the weight rows of a tile behind a serial chain over the output columns in front of it, and wide strips are the
+ * wrong shape for that -- a follow-up.
+ * As in tsvpp_convert_rois: `frames`, `rois`, `outs` are HOST arrays and may be freed on return; the per-box records (tsvpp_convert_rois's 48 bytes + the output
+ * size and the box's place in the grid: 64 bytes) travel BY VALUE in the kernarg segment, which bounds a launch to TSVPP_MAX_ROIS_SIZED boxes; no allocation, no
+ * copy, no host synchronisation; legal while `stream` is being captured; always an ordinary in-order launch; TSVPP_OPT_COLOR_G_TERM and the context's coefficient
+ * block are honoured.
+ * Launch splitting.  Vector stores need a 16-byte aligned output and a box that is not a narrow tail (an output 4 k + 2 columns wide and narrower than 32).  Outputs
+ * of different sizes packed tightly are misaligned all the time, and one such box must not drag the others onto the element-wise kernel: the call splits its boxes
+ * into the vector-eligible ones and the rest, keeps the order inside each class and issues each class in chunks of TSVPP_MAX_ROIS_SIZED, the vector class first:
+ * launches = ceil(n_vec / 48) + ceil(n_el / 48), all on `stream`.  The outputs are independent: the result does not depend on the split.
+ * Status, decided before any device is touched (the describe calls return the same one); every TSVPP_ERROR condition over all boxes comes before any
+ * TSVPP_UNSUPPORTED one:
+ *   TSVPP_ERROR        everything tsvpp_convert_rois calls an error; a box with dst_width or dst_height <= 0; non-zero p->dst_width / p->dst_height (and,
+ *                      converting: a null context, plane or output, a tensor output not aligned to its element)
+ *   TSVPP_UNSUPPORTED  odd box width / height, odd dst_* of a box, odd frame size, AREA or an unknown resize type, an output format outside the list above, a box
+ *                      whose source span reaches TSVPP_SOURCE_SPAN_LIMIT, a box whose output is 4 GiB or more (or has 2^31 / 48 tiles of 32 x 32 or more); then,
+ *                      tensor forms, rules 2 and 3 of the tensor block above.
+ * The describe line, key=value throughout: "mode=bilinear out=u8_merged dst=var rois=12 frames=2 launches=1 kernel=vpp_rois_sized<...> shape=8x16 lds=.. grid=..
+ * sizes=<distinct output sizes> maxdst=<largest width>x<largest height> staged=<boxes whose every tile stages, all launches> vec=<boxes in vector launches> nt=..
+ * limit=48".  lds=, grid=, kernel= and nt= are the FIRST launch's (the first vector chunk, or the first element-wise chunk of a request without vector boxes);
+ * grid= is exactly the sum of its boxes' tile counts, ceil(w / 32) * ceil(h / 32) each.  `aligned_outputs` != 0 takes every output as 16-byte aligned. */
+#define TSVPP_MAX_ROIS_SIZED 48 /* boxes per launch; more are split */
+typedef struct tsvpp_roi_sized {
+    int32_t frame, left, top, right, bottom; /* tsvpp_roi's fields and rules */
+    int32_t dst_width, dst_height;           /* THIS box's output size: > 0, even */
+} tsvpp_roi_sized;                           /* 28 bytes */
+/* bytes of one output of the given size: tsvpp_out_bytes(p, w, h) with p->dst_* = w, h (spec == NULL), or the tensor form's channels * w * h * element size; 0 for
+ * what the entry points refuse (a null `p`, AREA, a format outside the list, a size that is not positive and even, 4 GiB or more -- the tensor form: as fp32 --,
+ * non-zero p->dst_* or p->crop_*, rules 2 and 3 of the tensor block) */
+size_t tsvpp_rois_sized_bytes(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int dst_width, int dst_height);
+int tsvpp_convert_rois_sized(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi_sized *rois, const tsvpp_params *p,
+                             void *const *outs, void *stream);
+int tsvpp_describe_rois_sized(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi_sized *rois, int aligned_outputs,
+                              char *buf, size_t buf_len);
+int tsvpp_convert_rois_sized_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi_sized *rois, const tsvpp_params *p,
+                                    const tsvpp_tensor_spec *spec, void *const *outs, void *stream);
+int tsvpp_describe_rois_sized_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_rois,
+                                     const tsvpp_roi_sized *rois, int aligned_outputs, char *buf, size_t buf_len);
+/* DEBUG ONLY (tests), host only: the (box, tile column, tile row) and the tile's first output column / row that workgroup `wg` of the FIRST launch of this request
+ * takes -- the same __host__ __device__ function the kernel calls (sized_tile, csrc/vpp_rois_sized.h).  out5 = { box, txi, tyi, j_first, i_first }; `box` indexes
+ * `rois`.  The request's status if it is not TSVPP_OK; TSVPP_ERROR for a null `out5` or wg outside [0, grid). */
+int tsvpp_rois_sized_tile(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi_sized *rois, int aligned_outputs, unsigned wg,
+                          int32_t *out5);
 
 /* ---- affine warps (not in the reference) ---------------------------------------------------------------------------------------------------------------------
  * The second stage behind a detector when an axis-aligned box is not enough: a face aligned to 112 x 112 by a similarity transform, a rotated OCR / aerial box,

@@ -211,6 +211,34 @@ int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp
     return convertRois(false, true, spec, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
 }
 
+// ConvertRoisSized and its tensor overload (`spec` non-null: tsvpp_convert_rois_sized_tensor)
+static int convertRoisSized(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois,
+                            int nRois, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName) {
+    if (isClosed || !inputs || nInputs <= 0 || !rois || nRois <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
+    void *stream = nullptr;
+    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    std::vector<tsvpp_nv12> frames((size_t)nInputs);
+    for (int f = 0; f < nInputs; f++) {
+        const AVFrame *in = inputs[f];
+        if (!in) CHECK_STATUS(VREADER_ERROR);
+        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
+    }
+    const tsvpp_params p = flatten(options); // options.resize.width / height must be 0 (the sizes are the boxes'), options.crop empty
+    if (tensor) CHECK_STATUS(tsvpp_convert_rois_sized_tensor(ctx, nInputs, frames.data(), nRois, rois, &p, spec, deviceOuts, stream));
+    else CHECK_STATUS(tsvpp_convert_rois_sized(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
+    return VREADER_OK;
+}
+
+int VideoProcessor::ConvertRoisSized(AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                     std::string consumerName) {
+    return convertRoisSized(false, nullptr, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+}
+
+int VideoProcessor::ConvertRoisSized(AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                     const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertRoisSized(true, spec, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+}
+
 int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                                      std::string consumerName) {
     return convertLetterbox(false, nullptr, ctx, isClosed, inputs, n, rects, padY, padU, padV, deviceOuts, options, consumerName);

@@ -136,6 +136,15 @@ public:
                     const tsvpp_tensor_spec *spec, std::string consumerName);
     int ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                          const tsvpp_tensor_spec *spec, std::string consumerName);
+    // Boxes that each go to their OWN output size (tsvpp_convert_rois_sized, include/tsvpp.h; not in the reference): text lines of one height and their own widths,
+    // the levels of a pyramid, the inputs of several heads behind one detector pass.  rois[i] carries the box and its dst_width x dst_height; deviceOuts[i] holds
+    // tsvpp_rois_sized_bytes bytes.  options.resize.width and height must be 0 (the sizes are the boxes') and options.crop empty; options.resize.type is NEAREST,
+    // BILINEAR or BICUBIC (AREA is refused).  One kernel launch per TSVPP_MAX_ROIS_SIZED boxes of a store class on the consumer's stream; the inputs are NOT
+    // consumed.  Same status convention as ConvertInto.  With a tensor spec: tsvpp_convert_rois_sized_tensor.
+    int ConvertRoisSized(AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                         std::string consumerName);
+    int ConvertRoisSized(AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                         const tsvpp_tensor_spec *spec, std::string consumerName);
     // Rotated and affine-warped boxes (tsvpp_convert_warp, include/tsvpp.h; not in the reference): warps[i] samples inputs[warps[i].frame] BILINEAR through its
     // output -> source matrix into options.resize.width x height, colour-converted and written to deviceOuts[i], one kernel launch per TSVPP_MAX_WARPS outputs on the
     // consumer's stream.  borderY = borderU = borderV = -1 replicates the frame's edge; else each is 0..255, the sample outside the frame.  options.resize.type must

@@ -5,6 +5,7 @@
 //   tsvpp_table.cpp  persistent frame tables
 //   tsvpp_tiles.h    what the two files below share (templates): the launch fill, the staging budget, the convert and describe skeletons of the tile paths
 //   tsvpp_rois.cpp   regions of interest (both entry points: NEAREST / BILINEAR / BICUBIC and AREA)
+//   tsvpp_rois_sized.cpp regions of interest, each to its own output size (a skeleton of its own: the boxes of a call are split by store class)
 //   tsvpp_letterbox.cpp  aspect-preserving resize into a padded canvas
 // (the tensor entry points -- fp16 / bf16 / fp32 with mean and scale -- live with the path they extend: tsvpp_rois.cpp, tsvpp_letterbox.cpp)
 #pragma once
@@ -265,6 +266,8 @@ int make_plan(const tsvpp_params *p, int in_w, int in_h, Plan &pl);
 // plane span at or above TSVPP_SOURCE_SPAN_LIMIT as seen from the plan's source origin
 int plan_source_status(const Plan &pl, int in_w, int pitch_y, int pitch_uv);
 int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi *rois, RoiPlan &pl, bool area = false);
+// (tsvpp_convert_rois_sized / tsvpp_describe_rois_sized; RoiPlan: dst_w x dst_h stay 0, the sizes are the boxes')
+int rois_sized_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi_sized *rois, RoiPlan &pl);
 // (tsvpp_convert_letterbox / tsvpp_describe_letterbox; RoiPlan: the canvas is its dst_w x dst_h).  letterbox_rect_of: frame k's rectangle, the caller's or the default
 int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);
 tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int k, int dst_w, int dst_h);

@@ -123,15 +123,18 @@ bool color_flavour(int fourcc, int planes, bool f32, OutKind &out, int &swap_rb)
 
 // ---- what rois_plan and letterbox_plan share (the caller has tested `p` and `frames` for null) ----
 // TSVPP_ERROR class: parameters and frames that describe no request at all
-int tile_request_error(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames) {
-    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the boxes are the crops / the whole frame goes into the rectangle
-    if (p->dst_width <= 0 || p->dst_height <= 0) return TSVPP_ERROR;
+int tile_frames_error(int n_frames, const tsvpp_nv12 *frames) {
     for (int f = 0; f < n_frames; f++) {
         const tsvpp_nv12 &fr = frames[f];
         if (fr.width <= 0 || fr.height <= 0) return TSVPP_ERROR;
         if (pitch_or_width(fr.pitch_y, fr.width) < fr.width || pitch_or_width(fr.pitch_uv, fr.width) < fr.width) return TSVPP_ERROR;
     }
     return TSVPP_OK;
+}
+int tile_request_error(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames) {
+    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the boxes are the crops / the whole frame goes into the rectangle
+    if (p->dst_width <= 0 || p->dst_height <= 0) return TSVPP_ERROR;
+    return tile_frames_error(n_frames, frames);
 }
 // TSVPP_UNSUPPORTED class: sizes NV12 has no answer for
 int tile_request_odd(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames) {
@@ -150,18 +153,27 @@ int tile_frame_spans(int n_frames, const tsvpp_nv12 *frames) {
 }
 // TSVPP_UNSUPPORTED class: the resize type (`area`: the entry point answers AREA and nothing else), the output flavour and size, the grid of launches of up to
 // `max_items` items
-int tile_output_plan(const tsvpp_params *p, bool area, int max_items, RoiPlan &pl) {
+// ... its two halves: the resize type and the output flavour of the request,
+int tile_output_flavour(const tsvpp_params *p, bool area, RoiPlan &pl) {
     if (!resize_mode(p->resize_type, pl.mode) || (pl.mode == M_AREA_DOWN) != area) return TSVPP_UNSUPPORTED;
     if (p->planes != TSVPP_PLANAR && p->planes != TSVPP_MERGED) return TSVPP_UNSUPPORTED;
-    const bool f32 = p->normalization != 0;
-    if (!color_flavour(p->fourcc, p->planes, f32, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV: not yet
+    if (!color_flavour(p->fourcc, p->planes, p->normalization != 0, pl.out, pl.swap_rb)) return TSVPP_UNSUPPORTED; // NV12, UYVY, YUV444, HSV: not yet
+    return TSVPP_OK;
+}
+// ... and one output of dst_w x dst_h in that flavour: its bytes, and the grid of a launch of `max_items` of them
+int tile_output_size(const tsvpp_params *p, int dst_w, int dst_h, int max_items, size_t &out_bytes) {
     const int channels = p->fourcc == TSVPP_Y800 ? 1 : 3;
+    out_bytes = (size_t)channels * (size_t)dst_w * (size_t)dst_h * (p->normalization != 0 ? sizeof(float) : 1);
+    if (out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
+    // one workgroup per output tile and item
+    if ((long)((dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * max_items >= (1L << 31)) return TSVPP_UNSUPPORTED;
+    return TSVPP_OK;
+}
+int tile_output_plan(const tsvpp_params *p, bool area, int max_items, RoiPlan &pl) {
+    if (tile_output_flavour(p, area, pl) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     pl.dst_w = p->dst_width;
     pl.dst_h = p->dst_height;
-    pl.out_bytes = (size_t)channels * (size_t)pl.dst_w * (size_t)pl.dst_h * (f32 ? sizeof(float) : 1);
-    if (pl.out_bytes >= ((size_t)1 << 32)) return TSVPP_UNSUPPORTED; // kernels use 32-bit offsets inside an output
-    // one workgroup per output tile and item
-    if ((long)((pl.dst_w + ROI_TILE_W - 1) / ROI_TILE_W) * ((pl.dst_h + ROI_TILE_H - 1) / ROI_TILE_H) * max_items >= (1L << 31)) return TSVPP_UNSUPPORTED;
+    if (tile_output_size(p, pl.dst_w, pl.dst_h, max_items, pl.out_bytes) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     pl.down = pl.taps_x = pl.taps_y = 0;
     return TSVPP_OK;
 }
@@ -276,6 +288,45 @@ int rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
             pl.taps_x = tx > pl.taps_x ? tx : pl.taps_x;
             pl.taps_y = ty > pl.taps_y ? ty : pl.taps_y;
         }
+    }
+    return TSVPP_OK;
+}
+
+// tsvpp_convert_rois_sized and its siblings (include/tsvpp.h): rois_plan's rules in rois_plan's order -- every TSVPP_ERROR condition over all boxes, then every
+// TSVPP_UNSUPPORTED one -- with the output size taken per box.  pl.dst_w / dst_h stay 0 (there is no one size), pl.out_bytes is the largest output's.
+int rois_sized_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_rois, const tsvpp_roi_sized *rois, RoiPlan &pl) {
+    // TSVPP_ERROR: arguments that describe no request at all
+    if (!p || !frames || !rois || n_frames <= 0 || n_rois <= 0) return TSVPP_ERROR;
+    if (p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return TSVPP_ERROR; // the boxes are the crops
+    if (p->dst_width || p->dst_height) return TSVPP_ERROR;                                  // the sizes are the boxes': a caller who sets these believes they apply
+    if (tile_frames_error(n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
+    for (int i = 0; i < n_rois; i++) {
+        const tsvpp_roi_sized &b = rois[i];
+        if (b.frame < 0 || b.frame >= n_frames) return TSVPP_ERROR;
+        const tsvpp_nv12 &fr = frames[b.frame];
+        if (b.left < 0 || b.top < 0 || b.right <= b.left || b.bottom <= b.top || b.right > fr.width || b.bottom > fr.height) return TSVPP_ERROR;
+        if (b.dst_width <= 0 || b.dst_height <= 0) return TSVPP_ERROR;
+    }
+    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
+    for (int f = 0; f < n_frames; f++)
+        if ((frames[f].width | frames[f].height) & 1) return TSVPP_UNSUPPORTED;
+    for (int i = 0; i < n_rois; i++)
+        if (((rois[i].right - rois[i].left) | (rois[i].bottom - rois[i].top) | rois[i].dst_width | rois[i].dst_height) & 1) return TSVPP_UNSUPPORTED;
+    for (int i = 0; i < n_rois; i++) { // the source limit, per box: the kernel is handed the planes advanced to the box's origin
+        const tsvpp_nv12 &fr = frames[rois[i].frame];
+        if (source_span_status(rois[i].right - rois[i].left, rois[i].bottom - rois[i].top, pitch_or_width(fr.pitch_y, fr.width),
+                               pitch_or_width(fr.pitch_uv, fr.width)) != TSVPP_OK)
+            return TSVPP_UNSUPPORTED;
+    }
+    // AREA: its kernel generates weight rows per tile behind a serial chain over the output columns -- the wrong shape for wide strips, a follow-up
+    if (tile_output_flavour(p, false, pl) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+    pl.dst_w = pl.dst_h = 0;
+    pl.out_bytes = 0;
+    pl.down = pl.taps_x = pl.taps_y = 0;
+    for (int i = 0; i < n_rois; i++) {
+        size_t bytes;
+        if (tile_output_size(p, rois[i].dst_width, rois[i].dst_height, TSVPP_MAX_ROIS_SIZED, bytes) != TSVPP_OK) return TSVPP_UNSUPPORTED;
+        pl.out_bytes = bytes > pl.out_bytes ? bytes : pl.out_bytes;
     }
     return TSVPP_OK;
 }
@@ -423,6 +474,18 @@ size_t tsvpp_tensor_bytes(const tsvpp_params *p, const tsvpp_tensor_spec *spec) 
     const size_t elems = (size_t)(p->fourcc == TSVPP_Y800 ? 1 : 3) * (size_t)p->dst_width * (size_t)p->dst_height;
     if (elems * sizeof(float) >= ((size_t)1 << 32)) return 0; // the plans' limit, which is stated on fp32
     return elems * tensor_elem_bytes(spec->dtype);
+}
+
+size_t tsvpp_rois_sized_bytes(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int dst_width, int dst_height) {
+    if (!p || p->dst_width || p->dst_height || p->crop_left || p->crop_top || p->crop_right || p->crop_bottom) return 0;
+    if (dst_width <= 0 || dst_height <= 0 || ((dst_width | dst_height) & 1)) return 0;
+    RoiPlan pl;
+    size_t bytes;
+    if (tile_output_flavour(p, false, pl) != TSVPP_OK) return 0;
+    if (!spec) return tile_output_size(p, dst_width, dst_height, TSVPP_MAX_ROIS_SIZED, bytes) == TSVPP_OK ? bytes : 0;
+    if (tensor_spec_status(p, spec) != TSVPP_OK) return 0; // (normalization != 0 from here on: `bytes` is the fp32 size the plan's limit is stated on)
+    if (tile_output_size(p, dst_width, dst_height, TSVPP_MAX_ROIS_SIZED, bytes) != TSVPP_OK) return 0;
+    return bytes / sizeof(float) * tensor_elem_bytes(spec->dtype);
 }
 
 float tsvpp_channels(int fourcc) {

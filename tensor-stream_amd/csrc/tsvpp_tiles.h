@@ -23,7 +23,8 @@
 namespace tsvpp {
 
 // 4 k + 2 columns, narrower than a tile: no tile column to shift, so no vector stores
-inline bool narrow_tail(const RoiPlan &pl) { return (pl.dst_w & 3) != 0 && pl.dst_w < ROI_TILE_W; }
+inline bool narrow_tail(int dst_w) { return (dst_w & 3) != 0 && dst_w < ROI_TILE_W; }
+inline bool narrow_tail(const RoiPlan &pl) { return narrow_tail(pl.dst_w); }
 
 // What the staging budget needs to know of one item: its sampler, source size and ratios, and -- a path with kInnerRect -- the rectangle of the output its
 // samples fill, the inner rectangle of a letterbox frame.  A box fills the whole output: the ROI paths say kInnerRect = false and their loop does not ask (with
@@ -63,38 +64,44 @@ template <class PATH> int tile_fill(const PATH &path, const Knobs &kn, const Roi
 }
 
 // ... of a path whose tiles tap a column span times a row span of the source: an item stages if the largest footprint among its tiles fits the budget
+// The largest staged footprint among the tiles of ONE item whose output is dst_w x dst_h in tiles_x x tiles_y tiles: its LDS bytes, from the numbers the kernel
+// computes for the tiles that touch the item's rectangle (columns and rows are independent: the maximum over tiles is the maximum of each); `ok`: the staging
+// loop can serve every such tile (roi_stageable).  The tile paths ask with their launch's output, tsvpp_rois_sized.cpp with each box's own.
+template <bool INNER_RECT>
+inline long tile_item_need(const TileItem &it, int tiles_x, int tiles_y, int dst_w, int dst_h, int last_col0, bool luma_only, bool &ok) {
+    RoiFootprint f;
+    int cy = 0, cuv = 0, ny = 0, nuv = 0, lo, hi;
+    for (int tx = 0; tx < tiles_x; tx++) {
+        lo = roi_tile_col0(tx, dst_w, last_col0);
+        hi = tile_last(lo, ROI_TILE_W, dst_w);
+        if constexpr (INNER_RECT) {
+            tile_inner_range(lo, hi, it.left, it.width, lo, hi);
+            if (lo > hi) continue;
+        }
+        tile_span_x(it.mode, lo, hi, it.src_w, it.xr, f);
+        cy = std::max(cy, roi_chunks(f.xhi - f.xlo + 1));
+        cuv = std::max(cuv, roi_chunks(2 * (f.cxhi - f.cxlo + 1)));
+    }
+    for (int ty = 0; ty < tiles_y; ty++) {
+        lo = ty * ROI_TILE_H;
+        hi = tile_last(lo, ROI_TILE_H, dst_h);
+        if constexpr (INNER_RECT) {
+            tile_inner_range(lo, hi, it.top, it.height, lo, hi);
+            if (lo > hi) continue;
+        }
+        tile_span_y(it.mode, lo, hi, it.src_h, it.yr, f);
+        ny = std::max(ny, f.yhi - f.ylo + 1);
+        nuv = std::max(nuv, luma_only ? 0 : f.cyhi - f.cylo + 1);
+    }
+    ok = cy <= ROI_THREADS && cuv <= ROI_THREADS;
+    return 16L * ((long)ny * cy + (long)nuv * cuv);
+}
+
 template <class PATH> int tile_separable_budget(const PATH &path, const RoiPlan &pl, typename PATH::Launch &L, int cnt, int budget, bool luma_only) {
     int staged = 0, lds = 0;
     for (int i = 0; i < cnt; i++) {
-        const TileItem it = path.item(pl, L, i);
-        // from the numbers the kernel computes for the tiles that touch the item's rectangle (columns and rows are independent: the maximum over tiles is the
-        // maximum of each)
-        RoiFootprint f;
-        int cy = 0, cuv = 0, ny = 0, nuv = 0, lo, hi;
-        for (int tx = 0; tx < L.tiles_x; tx++) {
-            lo = roi_tile_col0(tx, pl.dst_w, L.last_col0);
-            hi = tile_last(lo, ROI_TILE_W, pl.dst_w);
-            if constexpr (PATH::kInnerRect) {
-                tile_inner_range(lo, hi, it.left, it.width, lo, hi);
-                if (lo > hi) continue;
-            }
-            tile_span_x(it.mode, lo, hi, it.src_w, it.xr, f);
-            cy = std::max(cy, roi_chunks(f.xhi - f.xlo + 1));
-            cuv = std::max(cuv, roi_chunks(2 * (f.cxhi - f.cxlo + 1)));
-        }
-        for (int ty = 0; ty < L.tiles_y; ty++) {
-            lo = ty * ROI_TILE_H;
-            hi = tile_last(lo, ROI_TILE_H, pl.dst_h);
-            if constexpr (PATH::kInnerRect) {
-                tile_inner_range(lo, hi, it.top, it.height, lo, hi);
-                if (lo > hi) continue;
-            }
-            tile_span_y(it.mode, lo, hi, it.src_h, it.yr, f);
-            ny = std::max(ny, f.yhi - f.ylo + 1);
-            nuv = std::max(nuv, luma_only ? 0 : f.cyhi - f.cylo + 1);
-        }
-        const bool ok = cy <= ROI_THREADS && cuv <= ROI_THREADS;
-        const long need = 16L * ((long)ny * cy + (long)nuv * cuv);
+        bool ok;
+        const long need = tile_item_need<PATH::kInnerRect>(path.item(pl, L, i), L.tiles_x, L.tiles_y, pl.dst_w, pl.dst_h, L.last_col0, luma_only, ok);
         if (ok && need <= budget) {
             staged++;
             lds = std::max(lds, (int)need);

@@ -11,6 +11,7 @@ LIB_PATH = os.path.normpath(os.path.join(_PKG, "..", "lib", "libtsvpp.so"))
 TSVPP_MAX_BATCH = 128
 TSVPP_MAX_ROIS = 64  # boxes per launch of tsvpp_convert_rois (their records travel in the kernarg segment)
 TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
+TSVPP_MAX_ROIS_SIZED = 48  # ... of tsvpp_convert_rois_sized (64-byte records)
 TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
 TSVPP_MAX_WARPS = 32  # outputs per launch of tsvpp_convert_warp
 TSVPP_MAX_PERSP = 32  # outputs per launch of tsvpp_convert_perspective
@@ -42,6 +43,12 @@ class Roi(ctypes.Structure):
     """struct tsvpp_roi: box [left, right) x [top, bottom) of frame `frame` (tsvpp_convert_rois)."""
     _fields_ = [("frame", ctypes.c_int32), ("left", ctypes.c_int32), ("top", ctypes.c_int32),
                 ("right", ctypes.c_int32), ("bottom", ctypes.c_int32)]
+
+
+class RoiSized(ctypes.Structure):
+    """struct tsvpp_roi_sized: tsvpp_roi's box, then THIS box's output size (tsvpp_convert_rois_sized)."""
+    _fields_ = [("frame", ctypes.c_int32), ("left", ctypes.c_int32), ("top", ctypes.c_int32),
+                ("right", ctypes.c_int32), ("bottom", ctypes.c_int32), ("dst_width", ctypes.c_int32), ("dst_height", ctypes.c_int32)]
 
 
 class Rect(ctypes.Structure):
@@ -93,6 +100,8 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables",
            "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox",
            "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor",
+           "tsvpp_rois_sized_bytes", "tsvpp_convert_rois_sized", "tsvpp_describe_rois_sized", "tsvpp_convert_rois_sized_tensor", "tsvpp_describe_rois_sized_tensor",
+           "tsvpp_rois_sized_tile",
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
            "tsvpp_convert_perspective", "tsvpp_describe_perspective", "tsvpp_convert_perspective_tensor", "tsvpp_describe_perspective_tensor", "tsvpp_persp_from_quad",
            "tsvpp_persp_footprint",
@@ -178,6 +187,19 @@ def lib():
     L.tsvpp_convert_letterbox_tensor.restype = i32
     L.tsvpp_describe_letterbox_tensor.argtypes = [pp, ps, i32, pn, pc, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_describe_letterbox_tensor.restype = i32
+    pz = ctypes.POINTER(RoiSized)
+    L.tsvpp_rois_sized_bytes.argtypes = [pp, ps, i32, i32]
+    L.tsvpp_rois_sized_bytes.restype = ctypes.c_size_t
+    L.tsvpp_convert_rois_sized.argtypes = [vp, i32, pn, i32, pz, pp, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_rois_sized.restype = i32
+    L.tsvpp_describe_rois_sized.argtypes = [pp, i32, pn, i32, pz, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_rois_sized.restype = i32
+    L.tsvpp_convert_rois_sized_tensor.argtypes = [vp, i32, pn, i32, pz, pp, ps, ctypes.POINTER(vp), vp]
+    L.tsvpp_convert_rois_sized_tensor.restype = i32
+    L.tsvpp_describe_rois_sized_tensor.argtypes = [pp, ps, i32, pn, i32, pz, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_rois_sized_tensor.restype = i32
+    L.tsvpp_rois_sized_tile.argtypes = [pp, i32, pn, i32, pz, i32, ctypes.c_uint, ctypes.POINTER(ctypes.c_int32)]
+    L.tsvpp_rois_sized_tile.restype = i32
     pw = ctypes.POINTER(Warp)
     L.tsvpp_convert_warp.argtypes = [vp, i32, pn, i32, pw, pp, i32, i32, i32, ctypes.POINTER(vp), vp]
     L.tsvpp_convert_warp.restype = i32

@@ -297,6 +297,50 @@ class VideoProcessor:
             N.check(self._lib.tsvpp_convert_rois_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), outs, stream))
         return out
 
+    def convert_rois_sized(self, ys, uvs, rois, params, sizes, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_rois with the output size PER BOX (tsvpp_convert_rois_sized): text lines of one height and their own widths (sizes_for_height), the levels of
+        a pyramid (pyramid_sizes), the inputs of several heads behind one detector pass -- one call, one launch per 48 boxes of a store class.  ys / uvs / rois /
+        width / height: as convert_rois; sizes: one (w, h) per box, positive and even; params: resize type (NEAREST / BILINEAR / BICUBIC; AREA is refused), pixel
+        format, planes and normalization -- its width and height MUST be 0, the sizes are the boxes'.  Returns a LIST of tensors, box i's of
+        output_shape(params, w_i, h_i): without `out` they are views into ONE allocation, each starting at a multiple of 256 bytes (so every box takes the vector
+        stores); with `out`, a list of the caller's tensors, each contiguous and of its box's size, is filled (a tensor that is not 16-byte aligned takes the
+        element-wise kernel; the call splits its boxes by that).  On torch's current stream.  Output i equals, bit for bit, convert_rois of box i alone at size i.
+        dtype / mean / std (see tensor_spec): as convert_rois, through tsvpp_convert_rois_sized_tensor."""
+        spec = tensor_spec(dtype, mean, std)
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        ys, uvs, boxes = _normalize_rois(ys, uvs, rois)
+        sizes = _normalize_sizes(sizes, len(boxes))
+        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
+        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
+        n = len(boxes)
+        if n == 0:
+            raise RuntimeError("-3: convert_rois_sized needs at least one box")
+        if out is None:
+            tdt = _torch_dtype(spec) if spec is not None else (torch.float32 if p.normalization else torch.uint8)
+            esz = torch.empty((), dtype=tdt).element_size()
+            shapes = [output_shape(p, w, h) for (w, h) in sizes]
+            offs, total = [], 0
+            for sh in shapes:  # every box at a multiple of 256 bytes
+                offs.append(total // esz)
+                total += (int(np.prod(sh)) * esz + 255) // 256 * 256
+            flat = torch.empty(max(total // esz, 1), dtype=tdt, device=f"cuda:{self.device}")
+            out = [flat[o:o + int(np.prod(sh))].view(sh) for o, sh in zip(offs, shapes)]
+        else:
+            if len(out) != n:
+                raise ValueError(f"{len(out)} outputs for {n} boxes")
+            for i, (o, (w, h)) in enumerate(zip(out, sizes)):  # a tensor of another size would be written past its end
+                need = self._lib.tsvpp_rois_sized_bytes(ctypes.byref(p), None if spec is None else ctypes.byref(spec), w, h)
+                if need and o.numel() * o.element_size() != need:
+                    raise ValueError(f"output {i} holds {o.numel() * o.element_size()} bytes, box {i} at {w} x {h} needs {need}")
+        recs = (N.RoiSized * n)(*[N.RoiSized(*b, *s) for b, s in zip(boxes, sizes)])
+        outs = (ctypes.c_void_p * n)(*[o.data_ptr() for o in out])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if spec is None:
+            N.check(self._lib.tsvpp_convert_rois_sized(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), outs, stream))
+        else:
+            N.check(self._lib.tsvpp_convert_rois_sized_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), outs, stream))
+        return out
+
     def convert_letterbox(self, ys, uvs, params, pad=(114, 128, 128), rects=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """The frame in front of a detector (tsvpp_convert_letterbox): every frame is resized with its aspect kept into an inner rectangle of ONE canvas of params'
         width x height, the rest of the canvas is `pad`, one launch per 32 frames.  ys / uvs: 3-D uint8 tensors (n, rows, pitch) or lists of 2-D tensors -- the
@@ -582,6 +626,63 @@ def describe_rois(params, frames, rois, aligned_outputs=True, dtype=None, mean=N
 def describe_rois_area(params, frames, rois, aligned_outputs=True, dtype=None, mean=None, std=None):
     """describe_rois for convert_rois_area (tsvpp_describe_rois_area): the same keys, then down (boxes on the down-scale path) and taps ("<x>x<y>", the largest)."""
     return _describe_rois(N.lib().tsvpp_describe_rois_area, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
+
+
+def _normalize_sizes(sizes, n):
+    sizes = [tuple(int(v) for v in s) for s in sizes]
+    if len(sizes) != n or any(len(s) != 2 for s in sizes):
+        raise ValueError(f"{n} boxes need {n} sizes (width, height)")
+    return sizes
+
+
+def describe_rois_sized(params, frames, rois, sizes, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_rois_sized of this request would launch, as a dict (tsvpp_describe_rois_sized: mode, out, dst="var", rois, frames, launches, kernel, shape,
+    lds, grid, sizes, maxdst, staged, vec, nt, limit) -- host logic only, works without a GPU.  frames: as describe_rois; rois / sizes: as convert_rois_sized;
+    aligned_outputs: every output 16-byte aligned (what convert_rois_sized allocates) or none.  dtype / mean / std: the tensor form."""
+    spec = tensor_spec(dtype, mean, std)
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
+    _, _, boxes = _normalize_rois([None] * len(recs), [None] * len(recs), rois)
+    sizes = _normalize_sizes(sizes, len(boxes))
+    fr = (N.NV12 * len(recs))(*recs)
+    bx = (N.RoiSized * max(len(boxes), 1))(*[N.RoiSized(*b, *s) for b, s in zip(boxes, sizes)])
+    buf = ctypes.create_string_buffer(512)
+    if spec is None:
+        N.check(N.lib().tsvpp_describe_rois_sized(ctypes.byref(p), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(N.lib().tsvpp_describe_rois_sized_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def sizes_for_height(boxes, height, max_width=None, multiple=2):
+    """Output sizes for text lines (convert_rois_sized): every box goes to `height` rows and to the width that keeps its aspect, rounded to the nearest multiple
+    of `multiple` (m, even; ties go up) and at least m.  boxes: (left, top, right, bottom) or (frame, left, top, right, bottom).  Integers only, with
+    bw = right - left and bh = bottom - top:
+        w = m * max(1, (2 * bw * height + bh * m) // (2 * bh * m))
+    clipped to `max_width` rounded down to a multiple of m (if given).  Returns a list of (w, height).  A 200 x 40 box to height 32, m = 2:
+    (2 * 200 * 32 + 40 * 2) // (2 * 40 * 2) = 12880 // 160 = 80, w = 160."""
+    m, height = int(multiple), int(height)
+    if m <= 0 or m & 1:
+        raise ValueError(f"multiple must be positive and even, not {multiple}")
+    cap = None if max_width is None else int(max_width) // m * m
+    if cap is not None and cap < m:
+        raise ValueError(f"max_width {max_width} is below the multiple {m}")
+    out = []
+    for b in boxes:
+        b = tuple(int(v) for v in b)[-4:]
+        bw, bh = b[2] - b[0], b[3] - b[1]
+        if bw <= 0 or bh <= 0:
+            raise ValueError(f"empty box {b}")
+        w = m * max(1, (2 * bw * height + bh * m) // (2 * bh * m))
+        out.append((w if cap is None else min(w, cap), height))
+    return out
+
+
+def pyramid_sizes(w, h, levels):
+    """The sizes of a dyadic pyramid or preview ladder (convert_rois_sized with the whole frame as every box): level k is
+        (max(2, (w >> k) & ~1), max(2, (h >> k) & ~1))
+    for k = 0 .. levels - 1; level 0 is the frame's own size rounded down to even.  pyramid_sizes(1920, 1080, 4) = [(1920, 1080), (960, 540), (480, 270), (240, 134)]."""
+    return [(max(2, (int(w) >> k) & ~1), max(2, (int(h) >> k) & ~1)) for k in range(int(levels))]
 
 
 def _geometry_records(frames):

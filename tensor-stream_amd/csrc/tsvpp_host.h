@@ -3,11 +3,16 @@
 //   tsvpp_area.cpp   AREA weight tables, their device cache, the AREA fields of a launch descriptor
 //   tsvpp_api.cpp    contexts, streams, knobs, the conversion itself and its replay cache, tsvpp_describe
 //   tsvpp_table.cpp  persistent frame tables
-//   tsvpp_tiles.h    what the two files below share (templates): the launch fill, the staging budget, the convert and describe skeletons of the tile paths
+//   tsvpp_tiles.h    what the tile paths below share (templates): the launch fill, the staging budgets, the convert and describe skeletons; and what the four
+//                    coordinate paths share beyond that (CoordRequest: request fields, border, record and launch fill, the pair of launchers)
 //   tsvpp_rois.cpp   regions of interest (both entry points: NEAREST / BILINEAR / BICUBIC and AREA)
 //   tsvpp_rois_sized.cpp regions of interest, each to its own output size (a skeleton of its own: the boxes of a call are split by store class)
 //   tsvpp_letterbox.cpp  aspect-preserving resize into a padded canvas
-// (the tensor entry points -- fp16 / bf16 / fp32 with mean and scale -- live with the path they extend: tsvpp_rois.cpp, tsvpp_letterbox.cpp)
+//   tsvpp_warp.cpp   affine warps        } the coordinate paths: one path with a different source coordinate.  Each file holds its record's geometry, its
+//   tsvpp_persp.cpp  homographies        } footprint function or LDS hint, its labels, its entry points and its host-only helpers; the request skeleton they
+//   tsvpp_remap.cpp  coordinate maps     } share is coord_plan (tsvpp_plan.cpp)
+//   tsvpp_mesh.cpp   control-grid warps  }
+// (the tensor entry points -- fp16 / bf16 / fp32 with mean and scale -- live with the path they extend: tsvpp_rois.cpp, tsvpp_letterbox.cpp, tsvpp_warp.cpp, ...)
 #pragma once
 #include <hip/hip_runtime.h>
 

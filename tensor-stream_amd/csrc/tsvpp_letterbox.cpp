@@ -13,6 +13,7 @@ struct LbPath {
     using Launch = LbLaunch;
     static constexpr bool kInnerRect = true; // a frame fills its inner rectangle: tiles that miss it stage nothing
     static constexpr bool kOwnBudget = false;
+    static constexpr bool kCountsStaged = true;
     bool tensor;
     const tsvpp_params *p;
     const tsvpp_tensor_spec *spec;

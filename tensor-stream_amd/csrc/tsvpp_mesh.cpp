@@ -1,8 +1,8 @@
 // tsvpp_mesh.cpp -- sparse control-grid warps (include/tsvpp.h): tsvpp_convert_mesh / tsvpp_describe_mesh, their tensor forms (`spec`, null for the first pair;
 // kernel vpp_mesh_tensor.hip) and the host-only functions on HOST copies of a mesh and a map: tsvpp_mesh_dims, tsvpp_mesh_expand, tsvpp_mesh_from_map,
-// tsvpp_mesh_error, tsvpp_mesh_lds_need; TSVPP_MAX_MESHES outputs per launch, kernel vpp_mesh.hip.  Modelled on tsvpp_remap.cpp, whose skeletons it shares
-// (tsvpp_tiles.h): MeshPath says what differs -- the request rules (mesh_plan, tsvpp_plan.cpp) and the record.  The launch's LDS is the budget or the caller's
-// hint, exactly as there: the meshes live in device memory and the host plans nothing per tile.
+// tsvpp_mesh_error, tsvpp_mesh_lds_need; TSVPP_MAX_MESHES outputs per launch, kernel vpp_mesh.hip.  The body is tsvpp_tiles.h's, and so is what the four
+// coordinate paths share (CoordRequest): MeshPath says what differs -- the request rules (mesh_plan, tsvpp_plan.cpp) and the record.  The launch's LDS is the
+// budget or the caller's hint (coord_hint_budget), as the dense call's: the meshes live in device memory and the host plans nothing per tile.
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -15,65 +15,41 @@ using namespace tsvpp;
 namespace {
 
 // The request of one call, as tsvpp_tiles.h asks for it
-struct MeshPath {
+struct MeshPath : CoordRequest {
     using Launch = MeshLaunch;
-    static constexpr bool kOwnBudget = true;
-    bool tensor;
-    const tsvpp_params *p;
-    const tsvpp_tensor_spec *spec;
-    int n_frames;
-    const tsvpp_nv12 *frames; // (may carry null planes: the describe calls)
+    static constexpr bool kCountsStaged = false;
     int n_meshes;
     const tsvpp_mesh *meshes; // (may carry null xy: the describe calls)
     int n;
     const tsvpp_remap *remaps;
-    int border_y, border_u, border_v;
 
-    bool border() const { return border_y >= 0; }
     int plan(RoiPlan &pl) const { return mesh_plan(p, n_frames, frames, n_meshes, meshes, n, remaps, border_y, border_u, border_v, pl); }
     int items() const { return n; }
     int limit(const RoiPlan &) const { return (int)TSVPP_MAX_MESHES; }
-    // (leaves the launch's hint in L.lds_bytes -- the largest over the meshes it uses, INT_MAX for a mesh without one -- for stage_budget, which tile_fill calls next)
+    int grids() const { return n_meshes; }
+    const void *grid_xy(int m) const { return meshes[m].xy; }
+    // (leaves the launch's hint in L.lds_bytes -- the largest over the meshes it uses -- for stage_budget, which tile_fill calls next)
     void fill_items(const RoiPlan &pl, void *const *outs, int base, int cnt, MeshLaunch &L) const {
-        L.n_remaps = cnt;
-        L.border_y = (float)border_y;
-        L.border_u = (float)border_u;
-        L.border_v = (float)border_v;
+        fill_launch(cnt, L);
         int hint = 0;
         for (int i = 0; i < cnt; i++) {
-            const tsvpp_remap &q = remaps[base + i];
-            const tsvpp_nv12 &fr = frames[q.frame];
-            const tsvpp_mesh &m = meshes[q.map];
+            const tsvpp_mesh &m = meshes[remaps[base + i].map];
             MeshRec &r = L.r[i];
-            r.y = (uint64_t)(uintptr_t)fr.y;
-            r.uv = (uint64_t)(uintptr_t)fr.uv;
-            r.out = outs ? (uint64_t)(uintptr_t)outs[base + i] : 0;
+            fill_rec(remaps[base + i].frame, outs ? outs[base + i] : nullptr, r);
             r.xy = (uint64_t)(uintptr_t)m.xy;
-            r.pitch_y = pitch_or_width(fr.pitch_y, fr.width);
-            r.pitch_uv = pitch_or_width(fr.pitch_uv, fr.width);
-            r.src_w = fr.width;
-            r.src_h = fr.height;
             r.mesh_pitch = m.pitch ? m.pitch : 8 * mesh_points(pl.dst_w, m.log2_cw);
             r.log2_cw = m.log2_cw;
             r.log2_ch = m.log2_ch;
             r.pad_ = 0;
-            hint = std::max(hint, m.lds_bytes > 0 ? m.lds_bytes : INT_MAX);
+            hint = coord_hint(hint, m.lds_bytes);
         }
         L.lds_bytes = hint;
     }
-    // The launch's dynamic LDS: the hint, capped by what the workgroup's budget leaves behind the reduction's words (RemapPath::stage_budget)
-    int stage_budget(const RoiPlan &, MeshLaunch &L, int budget, bool) const {
-        budget -= REMAP_REDUCE_LDS;
-        L.lds_bytes = budget > 0 ? std::min(L.lds_bytes, budget) : 0;
-        return L.lds_bytes > 0 ? L.n_remaps : 0;
-    }
-    int front_lds(const MeshLaunch &) const { return 0; }
-    // (vpp_mesh.hip and its tensor twin) one launch group, or only its kernel's name
+    int stage_budget(const RoiPlan &, MeshLaunch &L, int budget, bool) const { return coord_hint_budget(L, budget, REMAP_REDUCE_LDS); }
     hipError_t launch(const RoiPlan &pl, bool vec, bool, const MeshLaunch &L, hipStream_t stream, char *name, size_t name_len, bool dry_run) const {
-        const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n_remaps);
-        return (tensor ? launch_mesh_tensor : launch_mesh)(pl.out, vec, L.lds_bytes > 0, border(), L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
+        return launch_with(launch_mesh, launch_mesh_tensor, pl, vec, L, stream, name, name_len, dry_run);
     }
-    const char *mode_name() const { return "mesh_bilinear"; }
+    const char *mode_name(const RoiPlan &) const { return "mesh_bilinear"; }
     void counts(char *buf, size_t len) const {
         std::snprintf(buf, len, "remaps=%d meshes=%d cell=%dx%d frames=%d", n, n_meshes, 1 << meshes[0].log2_cw, 1 << meshes[0].log2_ch, n_frames);
     }
@@ -81,20 +57,6 @@ struct MeshPath {
         std::snprintf(buf, len, "tsvpp_convert_mesh%s n=%d meshes=%d frames=%d ->%dx%d fourcc=%d stream=%p", tensor ? "_tensor" : "", n, n_meshes, n_frames, pl.dst_w, pl.dst_h, p->fourcc, stream);
     }
 };
-
-// tile_convert behind the one rule it does not know: a mesh the kernel can address
-int mesh_convert(const MeshPath &path, tsvpp_ctx *ctx, void *const *outs, void *stream) {
-    RoiPlan pl;
-    const int sts = tile_request(path, pl);
-    if (sts == TSVPP_OK) {
-        for (int m = 0; m < path.n_meshes; m++)
-            if (!path.meshes[m].xy || ((uintptr_t)path.meshes[m].xy & 7)) {
-                clear_last_launch();
-                return TSVPP_ERROR;
-            }
-    }
-    return tile_convert(path, ctx, outs, stream);
-}
 
 // ---- HOST copies ----
 // A grid of (x, y) fp32 pairs, rows `pitch` bytes apart: a control grid or a dense map
@@ -148,22 +110,22 @@ extern "C" {
 
 int tsvpp_convert_mesh(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
                        const tsvpp_params *p, int border_y, int border_u, int border_v, void *const *outs, void *stream) {
-    return mesh_convert(MeshPath{ false, p, nullptr, n_frames, frames, n_meshes, meshes, n, remaps, border_y, border_u, border_v }, ctx, outs, stream);
+    return coord_grid_convert(MeshPath{ { false, p, nullptr, n_frames, frames, border_y, border_u, border_v }, n_meshes, meshes, n, remaps }, ctx, outs, stream);
 }
 
 int tsvpp_describe_mesh(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
                         int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
-    return tile_describe_unplanned(MeshPath{ false, p, nullptr, n_frames, frames, n_meshes, meshes, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+    return tile_describe(MeshPath{ { false, p, nullptr, n_frames, frames, border_y, border_u, border_v }, n_meshes, meshes, n, remaps }, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_convert_mesh_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
                               const tsvpp_params *p, const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream) {
-    return mesh_convert(MeshPath{ true, p, spec, n_frames, frames, n_meshes, meshes, n, remaps, border_y, border_u, border_v }, ctx, outs, stream);
+    return coord_grid_convert(MeshPath{ { true, p, spec, n_frames, frames, border_y, border_u, border_v }, n_meshes, meshes, n, remaps }, ctx, outs, stream);
 }
 
 int tsvpp_describe_mesh_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes,
                                int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
-    return tile_describe_unplanned(MeshPath{ true, p, spec, n_frames, frames, n_meshes, meshes, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+    return tile_describe(MeshPath{ { true, p, spec, n_frames, frames, border_y, border_u, border_v }, n_meshes, meshes, n, remaps }, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_mesh_dims(int dst_w, int dst_h, int log2_cw, int log2_ch, int *cols, int *rows) {

@@ -359,30 +359,49 @@ int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsv
     return tile_output_plan(p, false, TSVPP_MAX_LETTERBOX, pl);
 }
 
-// The request rules of the matrix paths, once: REC is tsvpp_warp (K = 6 entries) or tsvpp_persp (K = 9); `limit` = outputs per launch
-template <class REC, int K>
-int matrix_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const REC *recs, float (REC::*entries)[K], int border_y, int border_u,
-                int border_v, int limit, RoiPlan &pl) {
+// The border of the coordinate paths: (-1, -1, -1) replicates the frame's edge, anything else is a sample, each value 0..255
+static bool coord_border_ok(int border_y, int border_u, int border_v) {
+    if (border_y == -1 && border_u == -1 && border_v == -1) return true;
+    return border_y >= 0 && border_y <= 255 && border_u >= 0 && border_u <= 255 && border_v >= 0 && border_v <= 255;
+}
+
+// The request skeleton of the four coordinate paths (warp_plan, persp_plan, remap_plan, mesh_plan), once: the rules they share, in the one order that decides
+// which status a request with two faults gets.  A path passes what it alone knows: `given` -- its own arrays are there and not empty; index_ok(i) -- item i names
+// a frame (and a map, a mesh) of the request; path_error() / path_unsupported() -- whether one of its own TSVPP_ERROR / TSVPP_UNSUPPORTED rules is broken.
+// `limit` = outputs per launch
+template <class INDEX, class ERR, class UNS>
+int coord_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, bool given, int n, int border_y, int border_u, int border_v, int limit, RoiPlan &pl,
+               INDEX index_ok, ERR path_error, UNS path_unsupported) {
     // TSVPP_ERROR: arguments that describe no request at all
-    if (!p || !frames || !recs || n_frames <= 0 || n <= 0) return TSVPP_ERROR;
+    if (!p || !frames || n_frames <= 0 || !given || n <= 0) return TSVPP_ERROR;
     if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
     for (int i = 0; i < n; i++)
-        if (recs[i].frame < 0 || recs[i].frame >= n_frames) return TSVPP_ERROR;
-    const bool replicate = border_y == -1 && border_u == -1 && border_v == -1;
-    if (!replicate && (border_y < 0 || border_y > 255 || border_u < 0 || border_u > 255 || border_v < 0 || border_v > 255)) return TSVPP_ERROR;
-    for (int i = 0; i < n; i++)
-        for (int k = 0; k < K; k++)
-            if (!std::isfinite((recs[i].*entries)[k])) return TSVPP_ERROR;
+        if (!index_ok(i)) return TSVPP_ERROR;
+    if (!coord_border_ok(border_y, border_u, border_v)) return TSVPP_ERROR;
+    if (path_error()) return TSVPP_ERROR;
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    // NEAREST, BICUBIC and AREA warps: follow-ups
+    // NEAREST, BICUBIC and AREA through a coordinate: follow-ups
     if (tile_output_plan(p, false, limit, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
-    // with every entry inside 2^24 and indices below 2^31 no numerator or denominator overflows: every one is finite
-    for (int i = 0; i < n; i++)
-        for (int k = 0; k < K; k++)
-            if (std::fabs((recs[i].*entries)[k]) > 16777216.0f) return TSVPP_UNSUPPORTED;
-    return TSVPP_OK;
+    return path_unsupported() ? TSVPP_UNSUPPORTED : TSVPP_OK;
+}
+
+// ... of the matrix paths: REC is tsvpp_warp (K = 6 entries) or tsvpp_persp (K = 9).  `any` = some entry of some matrix satisfies the predicate
+template <class REC, int K>
+int matrix_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const REC *recs, float (REC::*entries)[K], int border_y, int border_u,
+                int border_v, int limit, RoiPlan &pl) {
+    const auto any = [&](auto pred) {
+        for (int i = 0; i < n; i++)
+            for (int k = 0; k < K; k++)
+                if (pred((recs[i].*entries)[k])) return true;
+        return false;
+    };
+    return coord_plan(
+        p, n_frames, frames, recs != nullptr, n, border_y, border_u, border_v, limit, pl, [&](int i) { return recs[i].frame >= 0 && recs[i].frame < n_frames; },
+        [&] { return any([](float v) { return !std::isfinite(v); }); },
+        // with every entry inside 2^24 and indices below 2^31 no numerator or denominator overflows: every one is finite
+        [&] { return any([](float v) { return std::fabs(v) > 16777216.0f; }); });
 }
 
 int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl) {
@@ -403,52 +422,45 @@ int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, in
     return TSVPP_OK;
 }
 
+// item i of a map path names a frame and a grid (a map, a mesh) of the request
+static bool remap_index_ok(const tsvpp_remap &r, int n_frames, int n_grids) { return r.frame >= 0 && r.frame < n_frames && r.map >= 0 && r.map < n_grids; }
+
 int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y,
                int border_u, int border_v, RoiPlan &pl) {
-    // TSVPP_ERROR: arguments that describe no request at all
-    if (!p || !frames || !maps || !remaps || n_frames <= 0 || n_maps <= 0 || n <= 0) return TSVPP_ERROR;
-    if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
-    for (int i = 0; i < n; i++)
-        if (remaps[i].frame < 0 || remaps[i].frame >= n_frames || remaps[i].map < 0 || remaps[i].map >= n_maps) return TSVPP_ERROR;
-    const bool replicate = border_y == -1 && border_u == -1 && border_v == -1;
-    if (!replicate && (border_y < 0 || border_y > 255 || border_u < 0 || border_u > 255 || border_v < 0 || border_v > 255)) return TSVPP_ERROR;
-    for (int m = 0; m < n_maps; m++) {
-        if (maps[m].pitch != 0 && ((long)maps[m].pitch < 8L * p->dst_width || (maps[m].pitch & 7))) return TSVPP_ERROR;
-        if (maps[m].pitch == 0 && 8L * p->dst_width > 0x7fffffffL) return TSVPP_ERROR; // (the tight pitch travels in 32 bits)
-        if (maps[m].lds_bytes < 0) return TSVPP_ERROR;
-    }
-    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
-    if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    if (tile_output_plan(p, false, TSVPP_MAX_REMAPS, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
-    return TSVPP_OK;
+    return coord_plan(
+        p, n_frames, frames, maps && remaps && n_maps > 0, n, border_y, border_u, border_v, TSVPP_MAX_REMAPS, pl,
+        [&](int i) { return remap_index_ok(remaps[i], n_frames, n_maps); },
+        [&] {
+            for (int m = 0; m < n_maps; m++) {
+                if (maps[m].pitch != 0 && ((long)maps[m].pitch < 8L * p->dst_width || (maps[m].pitch & 7))) return true;
+                if (maps[m].pitch == 0 && 8L * p->dst_width > 0x7fffffffL) return true; // (the tight pitch travels in 32 bits)
+                if (maps[m].lds_bytes < 0) return true;
+            }
+            return false;
+        },
+        [] { return false; });
 }
 
 int mesh_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps, int border_y,
               int border_u, int border_v, RoiPlan &pl) {
-    // TSVPP_ERROR: arguments that describe no request at all
-    if (!p || !frames || !meshes || !remaps || n_frames <= 0 || n_meshes <= 0 || n <= 0) return TSVPP_ERROR;
-    if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
-    for (int i = 0; i < n; i++)
-        if (remaps[i].frame < 0 || remaps[i].frame >= n_frames || remaps[i].map < 0 || remaps[i].map >= n_meshes) return TSVPP_ERROR;
-    const bool replicate = border_y == -1 && border_u == -1 && border_v == -1;
-    if (!replicate && (border_y < 0 || border_y > 255 || border_u < 0 || border_u > 255 || border_v < 0 || border_v > 255)) return TSVPP_ERROR;
-    for (int m = 0; m < n_meshes; m++) {
-        // (a cell size outside the range has no column count to hold a pitch against: its answer is TSVPP_UNSUPPORTED, below)
-        const bool cell = meshes[m].log2_cw >= MESH_LOG2_MIN && meshes[m].log2_cw <= MESH_LOG2_MAX;
-        if (meshes[m].pitch & 7) return TSVPP_ERROR;
-        if (cell && meshes[m].pitch != 0 && (long)meshes[m].pitch < 8L * mesh_points(p->dst_width, meshes[m].log2_cw)) return TSVPP_ERROR;
-        if (meshes[m].lds_bytes < 0) return TSVPP_ERROR;
-    }
-    // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
-    if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    if (tile_output_plan(p, false, TSVPP_MAX_MESHES, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
-    for (int m = 0; m < n_meshes; m++) {
-        if (meshes[m].log2_cw < MESH_LOG2_MIN || meshes[m].log2_cw > MESH_LOG2_MAX) return TSVPP_UNSUPPORTED;
-        if (meshes[m].log2_ch < MESH_LOG2_MIN || meshes[m].log2_ch > MESH_LOG2_MAX) return TSVPP_UNSUPPORTED;
-    }
-    return TSVPP_OK;
+    const auto cell_ok = [](int l) { return l >= MESH_LOG2_MIN && l <= MESH_LOG2_MAX; };
+    return coord_plan(
+        p, n_frames, frames, meshes && remaps && n_meshes > 0, n, border_y, border_u, border_v, TSVPP_MAX_MESHES, pl,
+        [&](int i) { return remap_index_ok(remaps[i], n_frames, n_meshes); },
+        [&] {
+            for (int m = 0; m < n_meshes; m++) {
+                // (a cell size outside the range has no column count to hold a pitch against: its answer is TSVPP_UNSUPPORTED, below)
+                if (meshes[m].pitch & 7) return true;
+                if (cell_ok(meshes[m].log2_cw) && meshes[m].pitch != 0 && (long)meshes[m].pitch < 8L * mesh_points(p->dst_width, meshes[m].log2_cw)) return true;
+                if (meshes[m].lds_bytes < 0) return true;
+            }
+            return false;
+        },
+        [&] {
+            for (int m = 0; m < n_meshes; m++)
+                if (!cell_ok(meshes[m].log2_cw) || !cell_ok(meshes[m].log2_ch)) return true;
+            return false;
+        });
 }
 
 // One spec check for both tensor paths. The caller has the plan's status already (it wins); what is left is about the spec and about what the tensor stores cover.

@@ -1,8 +1,8 @@
 // tsvpp_remap.cpp -- per-pixel coordinate maps (include/tsvpp.h): tsvpp_convert_remap / tsvpp_describe_remap, their tensor forms (`spec`, null for the first pair;
 // kernel vpp_remap_tensor.hip) and the two host-only functions on a HOST copy of a map, tsvpp_remap_footprint and tsvpp_remap_lds_need; TSVPP_MAX_REMAPS outputs
-// per launch, kernel vpp_remap.hip.  The launch fields and the convert skeleton are tsvpp_tiles.h's; RemapPath below says what differs: the request rules
-// (remap_plan, tsvpp_plan.cpp), the record, and the LDS of a launch -- the maps live in device memory, so there is NO per-tile loop on the convert path: the launch
-// asks for the budget or for the caller's hint, and every workgroup finds its own footprint.
+// per launch, kernel vpp_remap.hip.  The body is tsvpp_tiles.h's, and so is what the four coordinate paths share (CoordRequest); RemapPath below says what
+// differs: the request rules (remap_plan, tsvpp_plan.cpp), the record, and where a launch's LDS hint comes from -- the maps live in device memory, so there is
+// NO per-tile loop on the convert path: the launch asks for the budget or for the caller's hint (coord_hint_budget), and every workgroup finds its own footprint.
 #include <climits>
 #include <cmath>
 
@@ -14,83 +14,44 @@ using namespace tsvpp;
 namespace {
 
 // The request of one call, as tsvpp_tiles.h asks for it
-struct RemapPath {
+struct RemapPath : CoordRequest {
     using Launch = RemapLaunch;
-    static constexpr bool kOwnBudget = true;
-    bool tensor;
-    const tsvpp_params *p;
-    const tsvpp_tensor_spec *spec;
-    int n_frames;
-    const tsvpp_nv12 *frames; // (may carry null planes: the describe calls)
+    static constexpr bool kCountsStaged = false;
     int n_maps;
     const tsvpp_map *maps;    // (may carry null xy: the describe calls)
     int n;
     const tsvpp_remap *remaps;
-    int border_y, border_u, border_v;
 
-    bool border() const { return border_y >= 0; }
     int plan(RoiPlan &pl) const { return remap_plan(p, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v, pl); }
     int items() const { return n; }
     int limit(const RoiPlan &) const { return (int)TSVPP_MAX_REMAPS; }
-    // (leaves the launch's hint in L.lds_bytes -- the largest over the maps it uses, INT_MAX for a map without one -- for stage_budget, which tile_fill calls next)
+    int grids() const { return n_maps; }
+    const void *grid_xy(int m) const { return maps[m].xy; }
+    // (leaves the launch's hint in L.lds_bytes -- the largest over the maps it uses -- for stage_budget, which tile_fill calls next)
     void fill_items(const RoiPlan &pl, void *const *outs, int base, int cnt, RemapLaunch &L) const {
-        L.n_remaps = cnt;
-        L.border_y = (float)border_y;
-        L.border_u = (float)border_u;
-        L.border_v = (float)border_v;
+        fill_launch(cnt, L);
         int hint = 0;
         for (int i = 0; i < cnt; i++) {
-            const tsvpp_remap &q = remaps[base + i];
-            const tsvpp_nv12 &fr = frames[q.frame];
-            const tsvpp_map &m = maps[q.map];
+            const tsvpp_map &m = maps[remaps[base + i].map];
             RemapRec &r = L.r[i];
-            r.y = (uint64_t)(uintptr_t)fr.y;
-            r.uv = (uint64_t)(uintptr_t)fr.uv;
-            r.out = outs ? (uint64_t)(uintptr_t)outs[base + i] : 0;
+            fill_rec(remaps[base + i].frame, outs ? outs[base + i] : nullptr, r);
             r.xy = (uint64_t)(uintptr_t)m.xy;
-            r.pitch_y = pitch_or_width(fr.pitch_y, fr.width);
-            r.pitch_uv = pitch_or_width(fr.pitch_uv, fr.width);
-            r.src_w = fr.width;
-            r.src_h = fr.height;
             r.map_pitch = m.pitch ? m.pitch : 8 * pl.dst_w;
             r.pad_ = 0;
-            hint = std::max(hint, m.lds_bytes > 0 ? m.lds_bytes : INT_MAX);
+            hint = coord_hint(hint, m.lds_bytes);
         }
         L.lds_bytes = hint;
     }
-    // The launch's dynamic LDS: the hint, capped by what the workgroup's budget leaves behind the reduction's words.  The kernel decides per tile
-    // (need <= L.lds_bytes).  Returns the outputs that MAY stage: all of the launch or none
-    int stage_budget(const RoiPlan &, RemapLaunch &L, int budget, bool) const {
-        budget -= REMAP_REDUCE_LDS;
-        L.lds_bytes = budget > 0 ? std::min(L.lds_bytes, budget) : 0;
-        return L.lds_bytes > 0 ? L.n_remaps : 0;
-    }
-    int front_lds(const RemapLaunch &) const { return 0; }
-    // (vpp_remap.hip and its tensor twin) one launch group, or only its kernel's name
+    int stage_budget(const RoiPlan &, RemapLaunch &L, int budget, bool) const { return coord_hint_budget(L, budget, REMAP_REDUCE_LDS); }
     hipError_t launch(const RoiPlan &pl, bool vec, bool, const RemapLaunch &L, hipStream_t stream, char *name, size_t name_len, bool dry_run) const {
-        const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n_remaps);
-        return (tensor ? launch_remap_tensor : launch_remap)(pl.out, vec, L.lds_bytes > 0, border(), L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
+        return launch_with(launch_remap, launch_remap_tensor, pl, vec, L, stream, name, name_len, dry_run);
     }
-    const char *mode_name() const { return "remap_bilinear"; }
+    const char *mode_name(const RoiPlan &) const { return "remap_bilinear"; }
     void counts(char *buf, size_t len) const { std::snprintf(buf, len, "remaps=%d maps=%d frames=%d", n, n_maps, n_frames); }
     void label(char *buf, size_t len, const RoiPlan &pl, void *stream) const {
         std::snprintf(buf, len, "tsvpp_convert_remap%s n=%d maps=%d frames=%d ->%dx%d fourcc=%d stream=%p", tensor ? "_tensor" : "", n, n_maps, n_frames, pl.dst_w, pl.dst_h, p->fourcc, stream);
     }
 };
-
-// tile_convert behind the one rule it does not know: a map the kernel can address
-int remap_convert(const RemapPath &path, tsvpp_ctx *ctx, void *const *outs, void *stream) {
-    RoiPlan pl;
-    const int sts = tile_request(path, pl);
-    if (sts == TSVPP_OK) {
-        for (int m = 0; m < path.n_maps; m++)
-            if (!path.maps[m].xy || ((uintptr_t)path.maps[m].xy & 7)) {
-                clear_last_launch();
-                return TSVPP_ERROR;
-            }
-    }
-    return tile_convert(path, ctx, outs, stream);
-}
 
 // ---- a HOST copy of a map ----
 struct HostMap {
@@ -138,22 +99,22 @@ extern "C" {
 
 int tsvpp_convert_remap(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
                         const tsvpp_params *p, int border_y, int border_u, int border_v, void *const *outs, void *stream) {
-    return remap_convert(RemapPath{ false, p, nullptr, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, ctx, outs, stream);
+    return coord_grid_convert(RemapPath{ { false, p, nullptr, n_frames, frames, border_y, border_u, border_v }, n_maps, maps, n, remaps }, ctx, outs, stream);
 }
 
 int tsvpp_describe_remap(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
                          int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
-    return tile_describe_unplanned(RemapPath{ false, p, nullptr, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+    return tile_describe(RemapPath{ { false, p, nullptr, n_frames, frames, border_y, border_u, border_v }, n_maps, maps, n, remaps }, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_convert_remap_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
                                const tsvpp_params *p, const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream) {
-    return remap_convert(RemapPath{ true, p, spec, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, ctx, outs, stream);
+    return coord_grid_convert(RemapPath{ { true, p, spec, n_frames, frames, border_y, border_u, border_v }, n_maps, maps, n, remaps }, ctx, outs, stream);
 }
 
 int tsvpp_describe_remap_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps,
                                 int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
-    return tile_describe_unplanned(RemapPath{ true, p, spec, n_frames, frames, n_maps, maps, n, remaps, border_y, border_u, border_v }, aligned_outputs, buf, buf_len);
+    return tile_describe(RemapPath{ { true, p, spec, n_frames, frames, border_y, border_u, border_v }, n_maps, maps, n, remaps }, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_remap_footprint(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last,
@@ -164,8 +125,7 @@ int tsvpp_remap_footprint(const float *host_xy, int pitch, int dst_w, int dst_h,
     if ((j_first & 1) || (i_first & 1) || !(j_last & 1) || !(i_last & 1)) return TSVPP_ERROR; // whole pairs: even first, odd last
     RoiFootprint f;
     host_footprint(m, j_first, j_last, i_first, i_last, f);
-    const int32_t v[8] = { f.xlo, f.xhi, f.ylo, f.yhi, f.cxlo, f.cxhi, f.cylo, f.cyhi };
-    for (int k = 0; k < 8; k++) out8[k] = v[k];
+    footprint_export(f, out8);
     return TSVPP_OK;
 }
 

@@ -14,6 +14,7 @@ struct RoiPath {
     using Launch = RoiLaunch;
     static constexpr bool kInnerRect = false; // a box fills the whole output
     static constexpr bool kOwnBudget = false;
+    static constexpr bool kCountsStaged = true;
     bool area, tensor;
     const tsvpp_params *p;
     const tsvpp_tensor_spec *spec;

@@ -1,10 +1,13 @@
 // tsvpp_tiles.h -- the host side of the tile paths, once (tsvpp_rois.cpp: boxes, NEAREST / BILINEAR / BICUBIC and AREA; tsvpp_letterbox.cpp: frames into a padded
-// canvas; both with their tensor forms).  All of them launch one 32 x 32 output tile per workgroup (vpp_tile_core.h) for up to a fixed number of items -- boxes,
-// frames -- per launch.  Here: the launch fields they share, the staging budget, and the skeletons of the convert and the describe call.  A path is a small struct
-// that holds its request and answers what differs:
-//     using Launch                          RoiLaunch / LbLaunch / WarpLaunch
+// canvas; the coordinate paths tsvpp_warp.cpp, tsvpp_persp.cpp, tsvpp_remap.cpp, tsvpp_mesh.cpp; all with their tensor forms).  All of them launch one 32 x 32
+// output tile per workgroup (vpp_tile_core.h) for up to a fixed number of items -- boxes, frames, outputs -- per launch.  Here: the launch fields they share, the
+// staging budgets, and the skeletons of the convert and the describe call; behind them what the four coordinate paths share beyond that (CoordRequest).  A path
+// is a small struct that holds its request and answers what differs:
+//     using Launch                          RoiLaunch / LbLaunch / WarpLaunch / ...
 //     kOwnBudget                            false: a tile's footprint is a column span times a row span (item(), below); true: the path sizes the staged
 //                                           footprints itself -- stage_budget(pl, L, budget, luma_only) sets L.lds_bytes and returns the items that stage every tile
+//     kCountsStaged                         true: the host sees every footprint -- the describe line says staged= and lds= is everything the workgroup holds;
+//                                           false (coordinates in device memory): no staged=, lds= is the launch's dynamic LDS alone
 //     p, spec, tensor, n_frames, frames     the request (spec: null unless the tensor entry point was called -- where it may be null too: its TSVPP_ERROR)
 //     plan(pl), items(), limit(pl)          the request's status and RoiPlan; how many items it has; how many go into one launch
 //     fill_items(pl, outs, base, cnt, L)    the count, the records and the path's own fields of one launch group (outs: null in a dry run)
@@ -15,6 +18,7 @@
 //     mode_name(pl)                         the describe line's mode=
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 
 #include "tsvpp_host.h"
@@ -147,7 +151,8 @@ template <class PATH> int tile_convert(const PATH &path, tsvpp_ctx *ctx, void *c
     return TSVPP_OK;
 }
 
-// (`path` by value: its frames are replaced by a copy without planes)
+// (`path` by value: its frames are replaced by a copy without planes)  The line has two formats (kCountsStaged, above): a path whose coordinates live in device
+// memory cannot count what stages, and its lds= is non-zero iff the kernel is the staged one.
 template <class PATH> int tile_describe(PATH path, int aligned_outputs, char *buf, size_t buf_len) {
     if (!buf || buf_len == 0) return TSVPP_ERROR;
     buf[0] = 0;
@@ -161,7 +166,7 @@ template <class PATH> int tile_describe(PATH path, int aligned_outputs, char *bu
     path.frames = fr.data();
     const bool vec = aligned_outputs != 0 && !narrow_tail(pl);
     int staged = 0, lds0 = 0, grid0 = 0, launches = 0;
-    char kname[128] = "(none)", counts[64] = "", suffix[96] = "";
+    char kname[128] = "(none)", counts[96] = "", suffix[96] = "", staged_key[24] = "";
     typename PATH::Launch L;
     const int n = path.items(), limit = path.limit(pl);
     for (int base = 0; base < n; base += limit, launches++) {
@@ -169,7 +174,7 @@ template <class PATH> int tile_describe(PATH path, int aligned_outputs, char *bu
         const int s = tile_fill(path, kn, pl, nullptr, base, cnt, vec, L);
         staged += s;
         if (base == 0) {
-            lds0 = path.front_lds(L) + L.lds_bytes;
+            lds0 = PATH::kCountsStaged ? path.front_lds(L) + L.lds_bytes + roi_static_lds(pl.out, vec) : L.lds_bytes;
             grid0 = L.tiles_x * L.tiles_y * cnt;
             const hipError_t e = path.launch(pl, vec, s > 0, L, nullptr, kname, sizeof(kname), true);
             if (e != hipSuccess) return (int)e;
@@ -177,44 +182,118 @@ template <class PATH> int tile_describe(PATH path, int aligned_outputs, char *bu
     }
     path.counts(counts, sizeof(counts));
     path.suffix(suffix, sizeof(suffix), pl);
-    std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d %s launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d staged=%d tail=%d nt=%d limit=%d%s",
+    if (PATH::kCountsStaged) std::snprintf(staged_key, sizeof(staged_key), " staged=%d", staged);
+    std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d %s launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d%s tail=%d nt=%d limit=%d%s",
                   path.mode_name(pl), path.tensor ? tensor_out_name(path.spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w,
-                  pl.dst_h, counts, launches, kname, ROI_TX, ROI_TY, lds0 + roi_static_lds(pl.out, vec), grid0, L.tiles_x, L.tiles_y, staged, L.last_col0 > 0 ? 2 : 0, L.nt_stores,
-                  limit, suffix);
+                  pl.dst_h, counts, launches, kname, ROI_TX, ROI_TY, lds0, grid0, L.tiles_x, L.tiles_y, staged_key, L.last_col0 > 0 ? 2 : 0, L.nt_stores, limit, suffix);
     return TSVPP_OK;
 }
 
-// tile_describe for the paths whose coordinates live in device memory (tsvpp_remap.cpp, tsvpp_mesh.cpp): the line without staged= (the host cannot count what it
-// cannot see) and with lds= the dynamic LDS alone, non-zero iff the kernel is the staged one.  The path says mode_name() and counts() ("remaps=8 maps=1 frames=8")
-template <class PATH> int tile_describe_unplanned(PATH path, int aligned_outputs, char *buf, size_t buf_len) {
-    if (!buf || buf_len == 0) return TSVPP_ERROR;
-    buf[0] = 0;
-    RoiPlan pl;
-    const int sts = tile_request(path, pl);
-    if (sts != TSVPP_OK) return sts;
-    Knobs kn; // no context: no device, no streams
-    read_env_knobs(kn);
-    const bool vec = aligned_outputs != 0 && !narrow_tail(pl);
-    int lds0 = 0, grid0 = 0, launches = 0;
-    char kname[128] = "(none)", border[40] = "replicate", counts[96] = "";
-    typename PATH::Launch L;
-    const int limit = path.limit(pl);
-    for (int base = 0; base < path.n; base += limit, launches++) {
-        const int cnt = std::min(path.n - base, limit);
-        (void)tile_fill(path, kn, pl, nullptr, base, cnt, vec, L);
-        if (base == 0) {
-            lds0 = L.lds_bytes;
-            grid0 = L.tiles_x * L.tiles_y * cnt;
-            const hipError_t e = path.launch(pl, vec, lds0 > 0, L, nullptr, kname, sizeof(kname), true);
-            if (e != hipSuccess) return (int)e;
-        }
+// ---- the coordinate paths ----------------------------------------------------------------------------------------------------------------------------------
+// tsvpp_warp.cpp, tsvpp_persp.cpp, tsvpp_remap.cpp and tsvpp_mesh.cpp are one path with a different source coordinate: BILINEAR through a coordinate per output
+// pixel, a constant border or the replicated edge, a launch block that differs in its record alone (CoordLaunch, vpp_warp.h).  What they share beyond the
+// skeletons above is here; a path's own file keeps its record's geometry, its footprint function or hint, its labels and its entry points.
+
+// a launcher of vpp_warp.hip ... vpp_mesh_tensor.hip
+template <class LAUNCH>
+using CoordLauncher = hipError_t(OutKind, bool vec, bool staged, bool border, const LAUNCH &, unsigned grid, size_t lds_bytes, hipStream_t, char *name, size_t name_len, bool dry_run);
+
+// The request fields of a coordinate path and the answers that do not depend on the coordinate: the base of WarpPath, PerspPath, RemapPath, MeshPath
+struct CoordRequest {
+    static constexpr bool kOwnBudget = true;
+    bool tensor;
+    const tsvpp_params *p;
+    const tsvpp_tensor_spec *spec;
+    int n_frames;
+    const tsvpp_nv12 *frames; // (may carry null planes: the describe calls)
+    int border_y, border_u, border_v;
+
+    bool border() const { return border_y >= 0; }
+    template <class LAUNCH> int front_lds(const LAUNCH &) const { return 0; }
+    void suffix(char *buf, size_t len, const RoiPlan &) const {
+        if (border()) std::snprintf(buf, len, " border=%d,%d,%d", border_y, border_u, border_v);
+        else std::snprintf(buf, len, " border=replicate");
     }
-    if (path.border()) std::snprintf(border, sizeof(border), "%d,%d,%d", path.border_y, path.border_u, path.border_v);
-    path.counts(counts, sizeof(counts));
-    std::snprintf(buf, buf_len, "mode=%s out=%s dst=%dx%d %s launches=%d kernel=%s shape=%dx%d lds=%d grid=%d tiles=%dx%d tail=%d nt=%d limit=%d border=%s",
-                  path.mode_name(), path.tensor ? tensor_out_name(path.spec->dtype, pl.out == O_Y800_F32) : out_names[pl.out], pl.dst_w, pl.dst_h, counts, launches,
-                  kname, ROI_TX, ROI_TY, lds0, grid0, L.tiles_x, L.tiles_y, L.last_col0 > 0 ? 2 : 0, L.nt_stores, limit, border);
-    return TSVPP_OK;
+    // of one launch group: the count and the border sample
+    template <class LAUNCH> void fill_launch(int cnt, LAUNCH &L) const {
+        L.n = cnt;
+        L.border_y = (float)border_y;
+        L.border_u = (float)border_u;
+        L.border_v = (float)border_v;
+    }
+    // of one record: the planes, pitches and size of its frame, and its output (null in a dry run)
+    template <class REC> void fill_rec(int frame, void *out, REC &r) const {
+        const tsvpp_nv12 &fr = frames[frame];
+        r.y = (uint64_t)(uintptr_t)fr.y;
+        r.uv = (uint64_t)(uintptr_t)fr.uv;
+        r.out = (uint64_t)(uintptr_t)out;
+        r.pitch_y = pitch_or_width(fr.pitch_y, fr.width);
+        r.pitch_uv = pitch_or_width(fr.pitch_uv, fr.width);
+        r.src_w = fr.width;
+        r.src_h = fr.height;
+    }
+    // One launch group, or only its kernel's name, through the path's pair of launchers.  The staged kernel wherever ANY tile may stage (L.lds_bytes > 0): the
+    // kernel decides per tile, and what tile_fill counts is whole outputs
+    template <class LAUNCH>
+    hipError_t launch_with(CoordLauncher<LAUNCH> *colour, CoordLauncher<LAUNCH> *tensor_unit, const RoiPlan &pl, bool vec, const LAUNCH &L, hipStream_t stream, char *name,
+                           size_t name_len, bool dry_run) const {
+        const unsigned grid = (unsigned)(L.tiles_x * L.tiles_y * L.n);
+        return (tensor ? tensor_unit : colour)(pl.out, vec, L.lds_bytes > 0, border(), L, grid, (size_t)L.lds_bytes, stream, name, name_len, dry_run);
+    }
+};
+
+// The staging budget of a path whose host knows every coordinate (warp, perspective): FOOTPRINT(record, j0, j1, i0, i1, f) is the footprint function the kernel
+// evaluates, so these are every tile's numbers as the kernel will compute them.  The kernel decides per tile (need <= L.lds_bytes), so the launch takes the
+// largest box that fits the budget -- a launch may mix staged and gathering tiles -- and the count is of the outputs whose every tile stages.
+// (always_inline: this loop IS the host cost of a warp call with large outputs -- 2040 tiles per 1080p output.  Inlined, tile_fill compiles to the instructions
+// it had when each path carried its own copy of the loop, three field offsets apart; as a function of its own it did not.  profiles/coord_paths_ab.txt has
+// both measurements)
+template <auto FOOTPRINT, class LAUNCH> __attribute__((always_inline)) inline int coord_box_budget(const RoiPlan &pl, LAUNCH &L, int budget, bool luma_only) {
+    int staged = 0, lds = 0;
+    for (int i = 0; i < L.n; i++) {
+        bool all = true;
+        for (int ty = 0; ty < L.tiles_y; ty++)
+            for (int tx = 0; tx < L.tiles_x; tx++) {
+                const int j0 = roi_tile_col0(tx, pl.dst_w, L.last_col0), i0 = ty * ROI_TILE_H;
+                RoiFootprint f;
+                FOOTPRINT(L.r[i], j0, tile_last(j0, ROI_TILE_W, pl.dst_w), i0, tile_last(i0, ROI_TILE_H, pl.dst_h), f);
+                const int need = roi_lds_need(f, luma_only);
+                if (roi_stageable(f) && need <= budget) lds = std::max(lds, need);
+                else all = false;
+            }
+        staged += all ? 1 : 0;
+    }
+    L.lds_bytes = lds;
+    return staged;
+}
+
+// ... and of a path whose coordinates live in device memory (coordinate maps, control grids): no per-tile loop, every workgroup finds its own footprint.  The
+// launch's dynamic LDS is its hint -- which fill_items left in L.lds_bytes: coord_hint() over the grids the launch uses -- capped by what the workgroup's budget
+// leaves behind `reduce_lds`, the static words of the kernel's footprint reduction.  Returns the outputs that MAY stage: all of the launch or none
+inline int coord_hint(int hint, int lds_bytes) { return std::max(hint, lds_bytes > 0 ? lds_bytes : INT_MAX); } // (a grid without a hint: whatever the budget leaves)
+template <class LAUNCH> int coord_hint_budget(LAUNCH &L, int budget, int reduce_lds) {
+    budget -= reduce_lds;
+    L.lds_bytes = budget > 0 ? std::min(L.lds_bytes, budget) : 0;
+    return L.lds_bytes > 0 ? L.n : 0;
+}
+
+// tile_convert behind the one rule it does not know: grids -- path.grids() of them, grid m at path.grid_xy(m) -- the kernel can address
+template <class PATH> int coord_grid_convert(const PATH &path, tsvpp_ctx *ctx, void *const *outs, void *stream) {
+    RoiPlan pl;
+    if (tile_request(path, pl) == TSVPP_OK) {
+        for (int m = 0; m < path.grids(); m++)
+            if (!path.grid_xy(m) || ((uintptr_t)path.grid_xy(m) & 7)) {
+                clear_last_launch();
+                return TSVPP_ERROR;
+            }
+    }
+    return tile_convert(path, ctx, outs, stream);
+}
+
+// a footprint as the eight numbers the DEBUG exports hand out (tsvpp_warp_footprint, tsvpp_persp_footprint, tsvpp_remap_footprint)
+inline void footprint_export(const RoiFootprint &f, int32_t *out8) {
+    const int32_t v[8] = { f.xlo, f.xhi, f.ylo, f.yhi, f.cxlo, f.cxhi, f.cylo, f.cyhi };
+    for (int k = 0; k < 8; k++) out8[k] = v[k];
 }
 
 } // namespace tsvpp

@@ -21,20 +21,10 @@ struct MeshRec {
 };
 static_assert(sizeof(MeshRec) == 64, "MeshRec layout");
 
-// One launch: up to TSVPP_MAX_MESHES records, by value in the kernarg segment (2.2 KiB; HIP's hidden arguments take up to 256 bytes of the segment's 4 KiB).
-// Field for field RemapLaunch with MeshRec records: the parts of the dense kernel that read a launch block (remap_thread_tile) take either.
-struct MeshLaunch {
-    int32_t dst_w, dst_h;
-    int32_t swap_rb, color_g;
-    tsvpp_coeffs k;
-    int32_t tiles_x, tiles_y, n_remaps;
-    int32_t nt_stores, last_col0, u8_xchg;   // as LaunchDesc's
-    int32_t lds_bytes;                       // dynamic LDS of the launch: a tile whose footprint needs more gathers from global memory
-    float border_y, border_u, border_v;      // the constant-border kernels' sample, integer-valued (0..255)
-    MeshRec r[TSVPP_MAX_MESHES];
-    tsvpp_tensor_spec spec;                  // the tensor instantiations' dtype, mean[3], scale[3], once per launch; behind the records
-};
+// One launch: up to TSVPP_MAX_MESHES records (CoordLaunch, vpp_warp.h), 2.2 KiB of the kernarg segment
+using MeshLaunch = CoordLaunch<MeshRec, TSVPP_MAX_MESHES>;
 static_assert(sizeof(MeshLaunch) + 256 <= 4096, "MeshLaunch no longer fits the kernarg segment");
+static_assert(coord_launch_layout<MeshLaunch, 2168, 2136>, "MeshLaunch layout");
 
 constexpr int MESH_LOG2_MIN = 2, MESH_LOG2_MAX = 8;
 

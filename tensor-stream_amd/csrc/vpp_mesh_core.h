@@ -4,9 +4,8 @@
 //
 // It is the coordinate-map kernel (vpp_remap_core.h) with one function exchanged: mesh_load COMPUTES the sixteen luma entries of a thread tile from the control
 // points of its cells where remap_load reads them.  From the entries on -- remap_coords (chroma, clamp), remap_reduce, remap_footprint, stage_planes,
-// remap_thread_tile and the store -- it calls the dense kernel's functions, so it is the dense kernel on the expanded map E(mesh), bit for bit.  The kernel function
-// below repeats vpp_remap_kernel's few lines of orchestration rather than sharing them: with the body behind a common function the dense kernels' register
-// allocation changed, and they are to stay as they are (profiles/mesh_resources.txt).
+// remap_thread_tile and the store -- it IS the dense kernel, so it is the dense kernel on the expanded map E(mesh), bit for bit: both calls instantiate one kernel
+// template, vpp_coord_map_kernel, over the policy that names the load (MeshCoordLoad, below).
 #pragma once
 #include "vpp_remap_core.h"
 #include "vpp_mesh.h"
@@ -60,78 +59,19 @@ template <bool VEC> __device__ __forceinline__ void mesh_load(const uint8_t *xy,
     remap_coords<VEC>(ex, ey, dst_w, src_w, src_h, j0, c);
 }
 
-// (launch bounds: as vpp_remap_kernel's -- at most 128 VGPRs: profiles/mesh_resources.txt)
-template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL = EL_LIB>
-__global__ __launch_bounds__(ROI_THREADS, 4) void vpp_mesh_kernel(const MeshLaunch L) {
-    using T = typename OutT<OUT>::type;
-    typedef __attribute__((address_space(1))) uint8_t *GP; // the records hold GLOBAL addresses (PtrCol, vpp_kernels.h)
-    const TileIndex tix = tile_index(L.tiles_x, L.tiles_y);
-    const int item = tix.item, tyi = tix.tyi, txi = tix.txi;
-    if (item >= L.n_remaps) return;
-    const MeshRec &r = L.r[item]; // wave-uniform index: scalar loads
-
-    // the colour back end and the staging loop read their request from a LaunchDesc (the samplers' fields stay zero: the mesh is the sampler)
-    LaunchDesc d = {};
-    d.src_w = r.src_w;
-    d.src_h = r.src_h;
-    d.pitch_y = r.pitch_y;
-    d.pitch_uv = r.pitch_uv;
-    d.dst_w = L.dst_w;
-    d.dst_h = L.dst_h;
-    d.swap_rb = L.swap_rb;
-    d.color_g = L.color_g;
-    d.k = L.k;
-    d.tx = ROI_TX;
-    d.ty = ROI_TY;
-    d.tx_shift = ROI_TX_SHIFT;
-    d.rpt = 1;
-    d.nt_stores = L.nt_stores;
-    d.last_col0 = VEC ? L.last_col0 : 0;
-    d.u8_xchg = L.u8_xchg;
-    d.luma_only = kLumaOnly<OUT> ? 1 : 0;
-
-    const uint8_t *const plane_y = (const uint8_t *)(GP)(uintptr_t)r.y, *const plane_uv = (const uint8_t *)(GP)(uintptr_t)r.uv;
-    const uint8_t *const mesh_xy = (const uint8_t *)(GP)(uintptr_t)r.xy;
-    T *const out = (T *)(GP)(uintptr_t)r.out;
-    const int lx = threadIdx.x & (ROI_TX - 1), ly = threadIdx.x >> ROI_TX_SHIFT;
-    const int j_first = roi_tile_col0(txi, L.dst_w, d.last_col0), i_first = tyi * ROI_TILE_H;
-    const int j0 = j_first + lx * PXW, i0 = i_first + ly * PXH;
-    const bool active = j0 < L.dst_w && i0 < L.dst_h && !(VEC && is_row_tail(d, j0));
-
-    RemapCoords c;
-    mesh_load<VEC>(mesh_xy, r.mesh_pitch, r.log2_cw, r.log2_ch, L.dst_w, L.dst_h, r.src_w, r.src_h, i0, j0, c);
-
-    if constexpr (STAGED) {
-        // the tile's source bounding box, from the extremes of its own coordinates: the dense kernel's decision on E(mesh), which tsvpp_remap_footprint describes
-        __shared__ float red[2][8];
-        static_assert(sizeof(red) == REMAP_REDUCE_LDS, "the budget accounts for the reduction's words");
-        const RemapExtremes e = remap_reduce(c, active, red);
-        RoiFootprint f;
-        remap_footprint(e, r.src_w, r.src_h, f);
-        if (roi_stageable(f) && roi_lds_need(f, kLumaOnly<OUT>) <= L.lds_bytes) { // (wave-uniform)
-            const int span_y = f.xhi - f.xlo + 1, span_uv = 2 * (f.cxhi - f.cxlo + 1);
-            const int ny = f.yhi - f.ylo + 1, nuv = kLumaOnly<OUT> ? 0 : f.cyhi - f.cylo + 1;
-            d.lds_cpr_y = roi_chunks(span_y);
-            d.lds_cpr_uv = roi_chunks(span_uv);
-            d.lds_slot_y = 32 - __builtin_clz(((unsigned)d.lds_cpr_y - 1u) | 1u); // log2 of the lanes that serve one staged row (>= chunks per row)
-            d.lds_slot_uv = 32 - __builtin_clz(((unsigned)d.lds_cpr_uv - 1u) | 1u);
-            uint8_t *lds_y = lds_raw, *lds_uv = lds_raw + ny * d.lds_cpr_y * 16;
-            const uint8_t *ay, *auv;
-            LdsSrc s;
-            s.py_ = describe_plane(lds_y, plane_y, r.pitch_y, f.ylo, f.xlo, d.lds_cpr_y, ay);
-            s.puv_ = describe_plane(lds_uv, plane_uv, r.pitch_uv, f.cylo, 2 * f.cxlo, d.lds_cpr_uv, auv);
-            s.w = r.src_w;
-            s.h = r.src_h;
-            stage_planes<2, 1>(d, lds_y, ay, s.py_, ny, span_y, lds_uv, auv, s.puv_, nuv, span_uv, ROI_THREADS);
-            __syncthreads();
-            if (active) remap_thread_tile<OUT, VEC, BORDER, EL>(s, d, L, c, out, i0, j0);
-            return;
-        }
+// The control-grid call's policy for vpp_coord_map_kernel (vpp_remap_core.h): the coordinates of a thread tile are interpolated from record r's mesh
+struct MeshCoordLoad {
+    using Launch = MeshLaunch;
+    template <bool VEC> static __device__ __forceinline__ void load(const MeshRec &r, const uint8_t *xy, int dst_w, int dst_h, int i0, int j0, RemapCoords &c) {
+        mesh_load<VEC>(xy, r.mesh_pitch, r.log2_cw, r.log2_ch, dst_w, dst_h, r.src_w, r.src_h, i0, j0, c);
     }
-    if (!active) return;
-    GlobalSrc s;
-    tile_global_src(s, r, plane_y, plane_uv);
-    remap_thread_tile<OUT, VEC, BORDER, EL>(s, d, L, c, out, i0, j0);
-}
+};
+
+// The path's tag for launch_coord / launch_coord_tensor (vpp_tile_launch.h)
+struct MeshKernels {
+    using Launch = MeshLaunch;
+    static constexpr const char *kName = "vpp_mesh";
+    template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL> static constexpr auto kernel() { return &vpp_coord_map_kernel<MeshCoordLoad, OUT, VEC, STAGED, BORDER, EL>; }
+};
 
 } // namespace tsvpp

@@ -30,19 +30,10 @@ struct PerspRec {
 };
 static_assert(sizeof(PerspRec) == 112, "PerspRec layout");
 
-// One launch: up to TSVPP_MAX_PERSP records, by value in the kernarg segment (3.6 KiB; HIP's hidden arguments take up to 256 bytes of the segment's 4 KiB).
-struct PerspLaunch {
-    int32_t dst_w, dst_h;
-    int32_t swap_rb, color_g;
-    tsvpp_coeffs k;
-    int32_t tiles_x, tiles_y, n_persp;
-    int32_t nt_stores, last_col0, u8_xchg;   // as LaunchDesc's
-    int32_t lds_bytes;                       // dynamic LDS of the launch's staged footprints: a tile whose footprint needs more gathers from global memory
-    float border_y, border_u, border_v;      // the constant-border kernels' sample, integer-valued (0..255)
-    PerspRec r[TSVPP_MAX_PERSP];
-    tsvpp_tensor_spec spec;                  // the tensor instantiations' dtype, mean[3], scale[3], once per launch (vpp_tensor_store.h); behind the records
-};
+// One launch: up to TSVPP_MAX_PERSP records (CoordLaunch, vpp_warp.h), 3.6 KiB of the kernarg segment
+using PerspLaunch = CoordLaunch<PerspRec, TSVPP_MAX_PERSP>;
 static_assert(sizeof(PerspLaunch) + 256 <= 4096, "PerspLaunch no longer fits the kernarg segment");
+static_assert(coord_launch_layout<PerspLaunch, 3704, 3672>, "PerspLaunch layout");
 
 // The terms of both grids from the homography, each one fp32 operation with one rounding (the products by 0.5 and by 2 are exact)
 __host__ __device__ inline void persp_terms(const float h[9], PerspGrid &luma, PerspGrid &chroma) {

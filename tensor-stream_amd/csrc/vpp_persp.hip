@@ -20,22 +20,10 @@
 
 namespace tsvpp {
 
-// (the kernel: vpp_persp_core.h, shared with vpp_persp_tensor.hip)
-
+// (the kernel and its tag: vpp_persp_core.h, shared with vpp_persp_tensor.hip; the launcher: vpp_tile_launch.h)
 hipError_t launch_persp(OutKind out, bool vec, bool staged, bool border, const PerspLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
                         size_t name_len, bool dry_run) {
-    if (!tile_flavour(out)) return hipErrorNotSupported;
-    if (name && name_len) snprintf(name, name_len, "vpp_persp<%s,%s,%s,%s>", kOutNames[out], vec_name(vec), staged_name(staged), border_name(border));
-    if (dry_run) return hipSuccess;
-    return with_tile_flavour(out, [&](auto O) {
-        return with_vec_staged(vec, staged, [&](auto V, auto S) {
-            return with_border(border, [&](auto B) {
-                constexpr bool STAGED = decltype(S)::value; // (the gather kernel takes no dynamic LDS)
-                hipLaunchKernelGGL((vpp_persp_kernel<decltype(O)::value, decltype(V)::value, STAGED, decltype(B)::value>), dim3(grid), dim3(ROI_THREADS), STAGED ? lds_bytes : 0, stream, L);
-                return hipGetLastError();
-            });
-        });
-    });
+    return launch_coord<PerspKernels>(out, vec, staged, border, L, grid, lds_bytes, stream, name, name_len, dry_run);
 }
 
 } // namespace tsvpp

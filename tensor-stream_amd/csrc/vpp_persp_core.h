@@ -50,6 +50,8 @@ __device__ __forceinline__ void persp_thread_tile(const S &s, const LaunchDesc &
 }
 
 // (launch bounds: at least four waves per SIMD, i.e. at most 128 VGPRs -- four workgroups of the 40 KiB LDS budget per CU: profiles/persp_resources.txt)
+// A function of its own beside vpp_warp_kernel, whose lines it repeats: as one kernel template the two compile to other code -- about 830 fewer instruction
+// lines in each colour unit, about 900 with another opcode; the figures and the warning are at vpp_warp_kernel (vpp_warp_core.h).
 template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL = EL_LIB>
 __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_persp_kernel(const PerspLaunch L) {
     using T = typename OutT<OUT>::type;
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_persp_kernel(const PerspLa
     // workgroup -> (output, tile): all tiles of an output are neighbours in the grid, so the lines that adjacent tiles share meet in L2
     const TileIndex tix = tile_index(L.tiles_x, L.tiles_y);
     const int item = tix.item, tyi = tix.tyi, txi = tix.txi;
-    if (item >= L.n_persp) return;
+    if (item >= L.n) return;
     const PerspRec &r = L.r[item]; // wave-uniform index: scalar loads
 
     // the colour back end and the staging loop read their request from a LaunchDesc (the samplers' fields -- ratios, weights -- stay zero)
@@ -116,5 +118,12 @@ __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_persp_kernel(const PerspLa
     tile_global_src(s, r, plane_y, plane_uv);
     persp_thread_tile<OUT, VEC, BORDER, EL>(s, d, r, L, out, i0, j0);
 }
+
+// The path's tag for launch_coord / launch_coord_tensor (vpp_tile_launch.h)
+struct PerspKernels {
+    using Launch = PerspLaunch;
+    static constexpr const char *kName = "vpp_persp";
+    template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL> static constexpr auto kernel() { return &vpp_persp_kernel<OUT, VEC, STAGED, BORDER, EL>; }
+};
 
 } // namespace tsvpp

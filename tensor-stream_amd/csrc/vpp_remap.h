@@ -19,19 +19,11 @@ struct RemapRec {
 };
 static_assert(sizeof(RemapRec) == 56, "RemapRec layout");
 
-// One launch: up to TSVPP_MAX_REMAPS records, by value in the kernarg segment (1.9 KiB; HIP's hidden arguments take up to 256 bytes of the segment's 4 KiB).
-struct RemapLaunch {
-    int32_t dst_w, dst_h;
-    int32_t swap_rb, color_g;
-    tsvpp_coeffs k;
-    int32_t tiles_x, tiles_y, n_remaps;
-    int32_t nt_stores, last_col0, u8_xchg;   // as LaunchDesc's
-    int32_t lds_bytes;                       // dynamic LDS of the launch: a tile whose footprint needs more gathers from global memory
-    float border_y, border_u, border_v;      // the constant-border kernels' sample, integer-valued (0..255)
-    RemapRec r[TSVPP_MAX_REMAPS];
-    tsvpp_tensor_spec spec;                  // the tensor instantiations' dtype, mean[3], scale[3], once per launch; behind the records, as RoiLaunch's
-};
+// One launch: up to TSVPP_MAX_REMAPS records (CoordLaunch, vpp_warp.h), 1.9 KiB of the kernarg segment.  lds_bytes is the launch's hint or budget: the host
+// knows no footprint
+using RemapLaunch = CoordLaunch<RemapRec, TSVPP_MAX_REMAPS>;
 static_assert(sizeof(RemapLaunch) + 256 <= 4096, "RemapLaunch no longer fits the kernarg segment");
+static_assert(coord_launch_layout<RemapLaunch, 1912, 1880>, "RemapLaunch layout");
 
 // static LDS of the staged kernels' footprint reduction: eight extremes per wave (counts against the workgroup's LDS budget like roi_static_lds)
 constexpr int REMAP_REDUCE_LDS = 2 * 8 * 4;

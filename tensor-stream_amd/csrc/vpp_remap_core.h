@@ -2,6 +2,9 @@
 // with the library's colour back end (EL_LIB: every flavour of tsvpp_convert_remap) and vpp_remap_tensor.hip with the tensor store (EL_F32 / EL_HALF:
 // tsvpp_convert_remap_tensor, vpp_tensor_store.h).  Nothing but the store call differs between them.
 //
+// The kernel function is a template over a small policy -- the launch block and load(), which fills a thread tile's coordinates: RemapCoordLoad below READS
+// them (remap_load), MeshCoordLoad (vpp_mesh_core.h) COMPUTES them from control points (mesh_load).  Everything else is stated once for both calls.
+//
 // A thread's coordinates are read once -- the eight map entries of its 4 x 2 thread tile, 32 contiguous bytes per row, which also give its two chroma pairs --
 // clamped once, and kept in registers (20 values) across the footprint reduction and the staging barrier.  From the clamped coordinate on the sampler is the
 // affine kernel's (warp_luma / warp_chroma, vpp_warp_core.h).
@@ -144,17 +147,28 @@ __device__ __forceinline__ void remap_thread_tile(const S &s, const LaunchDesc &
     store_tile<OUT, VEC, EL>(Yf, Uf, Vf, d, L.spec, out, i0, j0, ncol);
 }
 
-// (launch bounds: at least four waves per SIMD, i.e. at most 128 VGPRs, as the affine kernel's: profiles/remap_resources.txt)
-template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL = EL_LIB>
-__global__ __launch_bounds__(ROI_THREADS, 4) void vpp_remap_kernel(const RemapLaunch L) {
+// The coordinate-map call's policy: the coordinates of the thread tile at output (i0, j0) of record r are map entries
+struct RemapCoordLoad {
+    using Launch = RemapLaunch;
+    template <bool VEC> static __device__ __forceinline__ void load(const RemapRec &r, const uint8_t *xy, int dst_w, int dst_h, int i0, int j0, RemapCoords &c) {
+        remap_load<VEC>(xy, r.map_pitch, dst_w, dst_h, r.src_w, r.src_h, i0, j0, c);
+    }
+};
+
+// The kernel of both calls: COORD is RemapCoordLoad or MeshCoordLoad (vpp_mesh_core.h).  An earlier attempt with the body behind a common FUNCTION changed the
+// dense kernels' register allocation; as a template over the policy the mesh kernels compile to the same instruction lines as the two functions did, and the
+// dense kernels to the same opcode sequence with two scalar registers exchanged in 50 lines (profiles/coord_paths_resources.txt).
+// (launch bounds: at least four waves per SIMD, i.e. at most 128 VGPRs, as the affine kernel's: profiles/remap_resources.txt, profiles/mesh_resources.txt)
+template <class COORD, int OUT, bool VEC, bool STAGED, bool BORDER, int EL = EL_LIB>
+__global__ __launch_bounds__(ROI_THREADS, 4) void vpp_coord_map_kernel(const typename COORD::Launch L) {
     using T = typename OutT<OUT>::type;
     typedef __attribute__((address_space(1))) uint8_t *GP; // the records hold GLOBAL addresses (PtrCol, vpp_kernels.h)
     const TileIndex tix = tile_index(L.tiles_x, L.tiles_y);
     const int item = tix.item, tyi = tix.tyi, txi = tix.txi;
-    if (item >= L.n_remaps) return;
-    const RemapRec &r = L.r[item]; // wave-uniform index: scalar loads
+    if (item >= L.n) return;
+    const auto &r = L.r[item]; // wave-uniform index: scalar loads
 
-    // the colour back end and the staging loop read their request from a LaunchDesc (the samplers' fields stay zero: the map is the sampler)
+    // the colour back end and the staging loop read their request from a LaunchDesc (the samplers' fields stay zero: the map, or the mesh, is the sampler)
     LaunchDesc d = {};
     d.src_w = r.src_w;
     d.src_h = r.src_h;
@@ -183,10 +197,11 @@ __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_remap_kernel(const RemapLa
     const bool active = j0 < L.dst_w && i0 < L.dst_h && !(VEC && is_row_tail(d, j0));
 
     RemapCoords c;
-    remap_load<VEC>(map_xy, r.map_pitch, L.dst_w, L.dst_h, r.src_w, r.src_h, i0, j0, c);
+    COORD::template load<VEC>(r, map_xy, L.dst_w, L.dst_h, i0, j0, c);
 
     if constexpr (STAGED) {
-        // the tile's source bounding box, from the extremes of its own coordinates (remap_footprint: the function tsvpp_remap_footprint evaluates on the host)
+        // the tile's source bounding box, from the extremes of its own coordinates (remap_footprint: the function tsvpp_remap_footprint evaluates on the host; a
+        // mesh's are those of its expanded map E(mesh))
         __shared__ float red[2][8];
         static_assert(sizeof(red) == REMAP_REDUCE_LDS, "the budget accounts for the reduction's words");
         const RemapExtremes e = remap_reduce(c, active, red);
@@ -217,5 +232,12 @@ __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_remap_kernel(const RemapLa
     tile_global_src(s, r, plane_y, plane_uv);
     remap_thread_tile<OUT, VEC, BORDER, EL>(s, d, L, c, out, i0, j0);
 }
+
+// The path's tag for launch_coord / launch_coord_tensor (vpp_tile_launch.h)
+struct RemapKernels {
+    using Launch = RemapLaunch;
+    static constexpr const char *kName = "vpp_remap";
+    template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL> static constexpr auto kernel() { return &vpp_coord_map_kernel<RemapCoordLoad, OUT, VEC, STAGED, BORDER, EL>; }
+};
 
 } // namespace tsvpp

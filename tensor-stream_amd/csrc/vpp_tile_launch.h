@@ -1,11 +1,15 @@
-// vpp_tile_launch.h -- what the six launchers of the tile kernels share (vpp_rois.hip, vpp_rois_area.hip, vpp_letterbox.hip and their *_tensor.hip twins): which
-// (mode, flavour, element) a kernel is instantiated for, the steps from those run-time values to template arguments, and the names describe reports.  Each step
-// hands std::integral_constant / std::bool_constant values to a callable, in the manner of with_out_kind (vpp_kernels.h); the .hip file nests the steps it needs
-// around its one hipLaunchKernelGGL line.  Anything not instantiated answers hipErrorNotSupported: a missing kernel is an error, never a fallback.
+// vpp_tile_launch.h -- what the launchers of the tile kernels share (vpp_rois.hip, vpp_rois_area.hip, vpp_letterbox.hip, the coordinate paths' vpp_warp.hip,
+// vpp_persp.hip, vpp_remap.hip, vpp_mesh.hip, and their *_tensor.hip twins): which (mode, flavour, element) a kernel is instantiated for, the steps from those
+// run-time values to template arguments, and the names describe reports.  Each step hands std::integral_constant / std::bool_constant values to a callable, in
+// the manner of with_out_kind (vpp_kernels.h); a .hip file nests the steps it needs around its one hipLaunchKernelGGL line -- the eight of the coordinate paths
+// nest the same ones, so their launcher is stated here, once for the colour units and once for the tensor units (launch_coord, launch_coord_tensor).  Anything
+// not instantiated answers hipErrorNotSupported: a missing kernel is an error, never a fallback.
 #pragma once
+#include <cstdio>
 #include <type_traits>
 
 #include "vpp_kernels.h"
+#include "vpp_rois.h"
 
 namespace tsvpp {
 
@@ -54,5 +58,44 @@ template <class F> inline hipError_t with_vec_staged(bool vec, bool staged, F &&
 }
 // f(BORDER) of the warp units
 template <class F> inline hipError_t with_border(bool border, F &&f) { return border ? f(std::true_type()) : f(std::false_type()); }
+
+// The launcher of a coordinate path's colour unit: launches -- or, with `dry_run`, only names -- the kernel of (out, vec, staged, border).  KERNELS is the path's
+// tag (beside its kernel: WarpKernels, vpp_warp_core.h, and so on): `Launch`, its launch block; `kName`, "vpp_warp"; kernel<OUT, VEC, STAGED, BORDER, EL>(), the
+// instantiation.  `name` receives what the describe call reports.
+template <class KERNELS>
+hipError_t launch_coord(OutKind out, bool vec, bool staged, bool border, const typename KERNELS::Launch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
+                        size_t name_len, bool dry_run) {
+    if (!tile_flavour(out)) return hipErrorNotSupported;
+    if (name && name_len) snprintf(name, name_len, "%s<%s,%s,%s,%s>", KERNELS::kName, kOutNames[out], vec_name(vec), staged_name(staged), border_name(border));
+    if (dry_run) return hipSuccess;
+    return with_tile_flavour(out, [&](auto O) {
+        return with_vec_staged(vec, staged, [&](auto V, auto S) {
+            return with_border(border, [&](auto B) {
+                constexpr bool STAGED = decltype(S)::value; // (the gather kernel takes no dynamic LDS)
+                hipLaunchKernelGGL((KERNELS::template kernel<decltype(O)::value, decltype(V)::value, STAGED, decltype(B)::value, EL_LIB>()), dim3(grid), dim3(ROI_THREADS), STAGED ? lds_bytes : 0, stream, L);
+                return hipGetLastError();
+            });
+        });
+    });
+}
+// ... and of its tensor unit: `out` is O_F32_PLANAR or O_Y800_F32, the element is L.spec.dtype's
+template <class KERNELS>
+hipError_t launch_coord_tensor(OutKind out, bool vec, bool staged, bool border, const typename KERNELS::Launch &L, unsigned grid, size_t lds_bytes, hipStream_t stream,
+                               char *name, size_t name_len, bool dry_run) {
+    const int dt = L.spec.dtype;
+    if (!tile_tensor(out, dt)) return hipErrorNotSupported;
+    if (name && name_len)
+        snprintf(name, name_len, "%s_tensor<%s,%s,%s,%s,%s>", KERNELS::kName, tensor_planes_name(out), tensor_el_name(dt), vec_name(vec), staged_name(staged), border_name(border));
+    if (dry_run) return hipSuccess;
+    return with_tile_tensor(out, dt, [&](auto O, auto E) {
+        return with_vec_staged(vec, staged, [&](auto V, auto S) {
+            return with_border(border, [&](auto B) {
+                constexpr bool STAGED = decltype(S)::value; // (the gather kernel takes no dynamic LDS)
+                hipLaunchKernelGGL((KERNELS::template kernel<decltype(O)::value, decltype(V)::value, STAGED, decltype(B)::value, decltype(E)::value>()), dim3(grid), dim3(ROI_THREADS), STAGED ? lds_bytes : 0, stream, L);
+                return hipGetLastError();
+            });
+        });
+    });
+}
 
 } // namespace tsvpp

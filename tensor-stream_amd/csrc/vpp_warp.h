@@ -2,6 +2,8 @@
 // tsvpp_convert_warp / tsvpp_describe_warp and their tensor forms).  The tile, the staging rules and the LDS accounting are the ROI kernel's (vpp_rois.h); what this
 // file adds is a source coordinate that depends on BOTH output indices.  Product code -- never includes anything from oracle/.
 #pragma once
+#include <cstddef>
+
 #include "vpp_rois.h"
 
 #pragma clang fp contract(off)
@@ -20,19 +22,25 @@ struct WarpRec {
 };
 static_assert(sizeof(WarpRec) == 72, "WarpRec layout");
 
-// One launch: up to TSVPP_MAX_WARPS records, by value in the kernarg segment (2.4 KiB; HIP's hidden arguments take up to 256 bytes of the segment's 4 KiB).
-struct WarpLaunch {
+// One launch of a coordinate path -- affine warp, perspective (vpp_persp.h), coordinate map (vpp_remap.h), control grid (vpp_mesh.h): up to N records of the
+// path's own type, by value in the kernarg segment (HIP's hidden arguments take up to 256 bytes of the segment's 4 KiB).  The paths differ in the record alone.
+template <class REC, int N> struct CoordLaunch {
     int32_t dst_w, dst_h;
     int32_t swap_rb, color_g;
     tsvpp_coeffs k;
-    int32_t tiles_x, tiles_y, n_warps;
+    int32_t tiles_x, tiles_y, n;             // n: the records in use
     int32_t nt_stores, last_col0, u8_xchg;   // as LaunchDesc's
     int32_t lds_bytes;                       // dynamic LDS of the launch's staged footprints: a tile whose footprint needs more gathers from global memory
     float border_y, border_u, border_v;      // the constant-border kernels' sample, integer-valued (0..255): what the sampler would hand the colour back end
-    WarpRec r[TSVPP_MAX_WARPS];
+    REC r[N];
     tsvpp_tensor_spec spec;                  // the tensor instantiations' dtype, mean[3], scale[3], once per launch (vpp_tensor_store.h); behind the records, as RoiLaunch's
 };
+// (the layout every path's block has had since it was written: size, offset of the records, offset of the spec)
+template <class L, size_t SIZE, size_t SPEC> constexpr bool coord_launch_layout = sizeof(L) == SIZE && offsetof(L, r) == 88 && offsetof(L, spec) == SPEC;
+
+using WarpLaunch = CoordLaunch<WarpRec, TSVPP_MAX_WARPS>; // 2.4 KiB
 static_assert(sizeof(WarpLaunch) + 256 <= 4096, "WarpLaunch no longer fits the kernarg segment");
+static_assert(coord_launch_layout<WarpLaunch, 2424, 2392>, "WarpLaunch layout");
 
 // The translations of a record from the matrix, each one fp32 operation (the multiplication by 0.5 is exact, so the chroma pair is rounded once as well)
 __host__ __device__ inline void warp_translations(float m2, float m5, WarpRec &r) {

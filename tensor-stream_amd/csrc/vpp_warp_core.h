@@ -76,6 +76,10 @@ __device__ __forceinline__ void warp_thread_tile(const S &s, const LaunchDesc &d
 
 // (launch bounds: at least four waves per SIMD, i.e. at most 128 VGPRs -- four workgroups of the 40 KiB LDS budget per CU.  With the rows fenced as above no
 // instantiation spills: profiles/warp_resources.txt)
+// This function and vpp_persp_kernel (vpp_persp_core.h) read alike and stay TWO functions.  As one kernel template over the thread-tile function -- and as one
+// over all four coordinate paths -- the compiler emitted other code: about 830 fewer instruction lines in each colour unit and about 900 lines with another
+// opcode (cross-compiled for gfx950 and diffed, never measured on a device: profiles/coord_paths_resources.txt).  Not to be tried again without a GPU to
+// measure on; the coordinate-map and control-grid kernels did fold into one (vpp_remap_core.h).
 template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL = EL_LIB>
 __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_warp_kernel(const WarpLaunch L) {
     using T = typename OutT<OUT>::type;
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_warp_kernel(const WarpLaun
     // workgroup -> (warp, tile): all tiles of an output are neighbours in the grid, so the lines that adjacent tiles share meet in L2
     const TileIndex tix = tile_index(L.tiles_x, L.tiles_y);
     const int item = tix.item, tyi = tix.tyi, txi = tix.txi;
-    if (item >= L.n_warps) return;
+    if (item >= L.n) return;
     const WarpRec &r = L.r[item]; // wave-uniform index: scalar loads
 
     // the colour back end and the staging loop read their request from a LaunchDesc (the samplers' fields -- ratios, weights -- stay zero: the warp has its own)
@@ -142,5 +146,12 @@ __global__ __launch_bounds__(ROI_THREADS, 4) void vpp_warp_kernel(const WarpLaun
     tile_global_src(s, r, plane_y, plane_uv);
     warp_thread_tile<OUT, VEC, BORDER, EL>(s, d, r, L, out, i0, j0);
 }
+
+// The path's tag for launch_coord / launch_coord_tensor (vpp_tile_launch.h)
+struct WarpKernels {
+    using Launch = WarpLaunch;
+    static constexpr const char *kName = "vpp_warp";
+    template <int OUT, bool VEC, bool STAGED, bool BORDER, int EL> static constexpr auto kernel() { return &vpp_warp_kernel<OUT, VEC, STAGED, BORDER, EL>; }
+};
 
 } // namespace tsvpp

@@ -11,22 +11,10 @@
 
 namespace tsvpp {
 
+// (the kernel and its tag: vpp_warp_core.h, shared with vpp_warp.hip; the launcher: vpp_tile_launch.h)
 hipError_t launch_warp_tensor(OutKind out, bool vec, bool staged, bool border, const WarpLaunch &L, unsigned grid, size_t lds_bytes, hipStream_t stream, char *name,
                               size_t name_len, bool dry_run) {
-    const int dt = L.spec.dtype;
-    if (!tile_tensor(out, dt)) return hipErrorNotSupported;
-    if (name && name_len)
-        snprintf(name, name_len, "vpp_warp_tensor<%s,%s,%s,%s,%s>", tensor_planes_name(out), tensor_el_name(dt), vec_name(vec), staged_name(staged), border_name(border));
-    if (dry_run) return hipSuccess;
-    return with_tile_tensor(out, dt, [&](auto O, auto E) {
-        return with_vec_staged(vec, staged, [&](auto V, auto S) {
-            return with_border(border, [&](auto B) {
-                constexpr bool STAGED = decltype(S)::value; // (the gather kernel takes no dynamic LDS)
-                hipLaunchKernelGGL((vpp_warp_kernel<decltype(O)::value, decltype(V)::value, STAGED, decltype(B)::value, decltype(E)::value>), dim3(grid), dim3(ROI_THREADS), STAGED ? lds_bytes : 0, stream, L);
-                return hipGetLastError();
-            });
-        });
-    });
+    return launch_coord_tensor<WarpKernels>(out, vec, staged, border, L, grid, lds_bytes, stream, name, name_len, dry_run);
 }
 
 } // namespace tsvpp

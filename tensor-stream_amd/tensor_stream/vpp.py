@@ -382,24 +382,11 @@ class VideoProcessor:
         outside the frame.  params' resize_type must be BILINEAR.  Returns (or fills `out`, indexed out[i]) a tensor of shape (n, ...frame shape) with
         convert_batch's padded frame stride, on torch's current stream.  dtype / mean / std: as convert_rois (tsvpp_convert_warp_tensor); the border sample goes
         through them like every sample."""
-        spec = tensor_spec(dtype, mean, std)
-        p = params.parameters if isinstance(params, FrameParameters) else params
-        ys, uvs, recs = _normalize_warps(ys, uvs, warps)
-        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
-        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
-        n = len(recs)
-        if n == 0:
-            raise RuntimeError("-3: convert_warp needs at least one matrix")
-        if out is None:
-            out = self._alloc_items(p, n, spec, "convert_warp needs an even, positive output size")
-        by, bu, bv = _border(border)
-        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if spec is None:
-            N.check(self._lib.tsvpp_convert_warp(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
-        else:
-            N.check(self._lib.tsvpp_convert_warp_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv, outs, stream))
-        return out
+        def items(p, ys, uvs):
+            ys, uvs, recs = _normalize_warps(ys, uvs, warps)
+            return ys, uvs, len(recs), (len(recs), recs)
+        return self._convert_coord("convert_warp", "matrix", (self._lib.tsvpp_convert_warp, self._lib.tsvpp_convert_warp_tensor), items, ys, uvs, params, border, out,
+                                   width, height, dtype, mean, std)
 
     def convert_remap(self, ys, uvs, maps, params, remaps=None, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """Per-pixel coordinate maps -- lens undistortion, rectification, unwraps, mesh warps (tsvpp_convert_remap): every output samples one frame BILINEAR where
@@ -409,25 +396,13 @@ class VideoProcessor:
         row stride of >= 2 * width elements becomes the pitch; each may be paired as (tensor, lds_bytes) with the hint of remap_lds_hint.  The tensors are read
         when the kernel runs: keep them alive, and a captured graph sees their updates.  remaps: a list of (frame, map); None with one map sends every frame
         through it in order, None with as many maps as frames pairs them up.  border, out, width, height, dtype / mean / std and the result: as convert_warp."""
-        spec = tensor_spec(dtype, mean, std)
-        p = params.parameters if isinstance(params, FrameParameters) else params
-        ys, uvs, _ = _normalize_rois(ys, uvs, [])
-        recs_m = _normalize_maps(maps, p.dst_width, p.dst_height, self.device)
-        recs = _normalize_remaps(remaps, len(ys), len(recs_m))
-        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
-        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
-        n = len(recs)
-        if out is None:
-            out = self._alloc_items(p, n, spec, "convert_remap needs an even, positive output size")
-        by, bu, bv = _border(border)
-        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if spec is None:
-            N.check(self._lib.tsvpp_convert_remap(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
-        else:
-            N.check(self._lib.tsvpp_convert_remap_tensor(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv,
-                                                         outs, stream))
-        return out
+        def items(p, ys, uvs):
+            ys, uvs, _ = _normalize_rois(ys, uvs, [])
+            recs_m = _normalize_maps(maps, p.dst_width, p.dst_height, self.device)
+            recs = _normalize_remaps(remaps, len(ys), len(recs_m))
+            return ys, uvs, len(recs), (len(recs_m), recs_m, len(recs), recs)
+        return self._convert_coord("convert_remap", None, (self._lib.tsvpp_convert_remap, self._lib.tsvpp_convert_remap_tensor), items, ys, uvs, params, border, out,
+                                   width, height, dtype, mean, std)
 
     def convert_mesh(self, ys, uvs, meshes, params, cell=(16, 16), remaps=None, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """Sparse control-grid warps -- a warp mesh per lens, per stabilised frame (tsvpp_convert_mesh): convert_remap with the coordinate interpolated from one
@@ -437,25 +412,13 @@ class VideoProcessor:
         >= 2 * cols elements becomes the pitch; each may be paired as (tensor, lds_bytes) with the hint of mesh_lds_hint.  cell: (cw, ch), powers of two 4..256,
         for all meshes or a list with one per mesh.  The tensors are read when the kernel runs: keep them alive, and a captured graph sees their updates.
         remaps: a list of (frame, mesh), None as for convert_remap.  Everything else: as convert_remap."""
-        spec = tensor_spec(dtype, mean, std)
-        p = params.parameters if isinstance(params, FrameParameters) else params
-        ys, uvs, _ = _normalize_rois(ys, uvs, [])
-        recs_m = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height, self.device)
-        recs = _normalize_remaps(remaps, len(ys), len(recs_m))
-        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
-        frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
-        n = len(recs)
-        if out is None:
-            out = self._alloc_items(p, n, spec, "convert_mesh needs an even, positive output size")
-        by, bu, bv = _border(border)
-        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if spec is None:
-            N.check(self._lib.tsvpp_convert_mesh(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
-        else:
-            N.check(self._lib.tsvpp_convert_mesh_tensor(self._ctx, len(ys), frames, len(recs_m), recs_m, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv,
-                                                        outs, stream))
-        return out
+        def items(p, ys, uvs):
+            ys, uvs, _ = _normalize_rois(ys, uvs, [])
+            recs_m = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height, self.device)
+            recs = _normalize_remaps(remaps, len(ys), len(recs_m))
+            return ys, uvs, len(recs), (len(recs_m), recs_m, len(recs), recs)
+        return self._convert_coord("convert_mesh", None, (self._lib.tsvpp_convert_mesh, self._lib.tsvpp_convert_mesh_tensor), items, ys, uvs, params, border, out,
+                                   width, height, dtype, mean, std)
 
     def convert_perspective(self, ys, uvs, persps, params, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
         """Homography-warped outputs (tsvpp_convert_perspective): every entry of `persps` samples its frame BILINEAR through its own 3 x 3 output -> source
@@ -463,23 +426,32 @@ class VideoProcessor:
         dtype / mean / std: as convert_warp.  persps: (h0, ..., h8) of frame 0 or (frame, h0, ..., h8), row-major -- X = (h0 u + h1 v + h2) / (h6 u + h7 v + h8),
         Y = (h3 u + h4 v + h5) / (h6 u + h7 v + h8) with (u, v) = (column + 0.5, row + 0.5) the output pixel's centre, in luma pixels of the whole frame
         (perspective_from_quad, perspective_from_opencv make them).  A homography whose horizon crosses the output is refused (-2)."""
+        def items(p, ys, uvs):
+            ys, uvs, recs = _normalize_persps(ys, uvs, persps)
+            return ys, uvs, len(recs), (len(recs), recs)
+        return self._convert_coord("convert_perspective", "homography", (self._lib.tsvpp_convert_perspective, self._lib.tsvpp_convert_perspective_tensor), items, ys,
+                                   uvs, params, border, out, width, height, dtype, mean, std)
+
+    def _convert_coord(self, name, one, entries, items, ys, uvs, params, border, out, width, height, dtype, mean, std):
+        """convert_warp, convert_perspective, convert_remap and convert_mesh, once.  entries: the call's (colour, tensor) entry points; items(p, ys, uvs): the
+        path's own arguments as (luma planes, chroma planes, number of outputs, the arguments that sit between `frames` and `params` in the C call); one: what an
+        empty call lacks ("matrix"), None where items() has said so already."""
         spec = tensor_spec(dtype, mean, std)
         p = params.parameters if isinstance(params, FrameParameters) else params
-        ys, uvs, recs = _normalize_persps(ys, uvs, persps)
+        ys, uvs, n, between = items(p, ys, uvs)
         widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
         frames = (N.NV12 * len(ys))(*[self._frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
-        n = len(recs)
-        if n == 0:
-            raise RuntimeError("-3: convert_perspective needs at least one homography")
+        if n == 0 and one is not None:
+            raise RuntimeError(f"-3: {name} needs at least one {one}")
         if out is None:
-            out = self._alloc_items(p, n, spec, "convert_perspective needs an even, positive output size")
+            out = self._alloc_items(p, n, spec, f"{name} needs an even, positive output size")
         by, bu, bv = _border(border)
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if spec is None:
-            N.check(self._lib.tsvpp_convert_perspective(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), by, bu, bv, outs, stream))
+            N.check(entries[0](self._ctx, len(ys), frames, *between, ctypes.byref(p), by, bu, bv, outs, stream))
         else:
-            N.check(self._lib.tsvpp_convert_perspective_tensor(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), ctypes.byref(spec), by, bu, bv, outs, stream))
+            N.check(entries[1](self._ctx, len(ys), frames, *between, ctypes.byref(p), ctypes.byref(spec), by, bu, bv, outs, stream))
         return out
 
     def make_batch(self, ys, uvs, params, out=None, width=None, height=None):
@@ -750,6 +722,23 @@ def _border(border):
     return y, u, v
 
 
+def _describe_coord(entries, items, params, frames, border, aligned_outputs, dtype, mean, std):
+    """describe_warp, describe_perspective, describe_remap and describe_mesh, once.  entries: the call's (colour, tensor) entry points; items(p, frame records):
+    the arguments that sit between `frames` and the border in the C call."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
+    between = items(p, recs)
+    fr = (N.NV12 * len(recs))(*recs)
+    by, bu, bv = _border(border)
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    if spec is None:
+        N.check(entries[0](ctypes.byref(p), len(recs), fr, *between, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
+    else:
+        N.check(entries[1](ctypes.byref(p), ctypes.byref(spec), len(recs), fr, *between, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
 def _normalize_warps(ys, uvs, warps):
     """The argument forms of convert_warp / describe_warp as (list of luma planes, list of chroma planes, array of tsvpp_warp): one frame may be given as a bare
     pair of planes, a matrix of frame 0 as six numbers.  Pure Python: touches no device."""
@@ -768,19 +757,10 @@ def _normalize_warps(ys, uvs, warps):
 def describe_warp(params, frames, warps, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
     """What a convert_warp of this request would launch, as a dict (tsvpp_describe_warp: describe_rois's keys with warps= for rois=, then border = "replicate" or
     "Y,U,V") -- host logic only, works without a GPU.  frames: as describe_rois; warps and border as for convert_warp."""
-    p = params.parameters if isinstance(params, FrameParameters) else params
-    recs = _geometry_records(frames)
-    _, _, ws = _normalize_warps([None] * len(recs), [None] * len(recs), warps)
-    fr = (N.NV12 * len(recs))(*recs)
-    by, bu, bv = _border(border)
-    buf = ctypes.create_string_buffer(512)
-    spec = tensor_spec(dtype, mean, std)
-    n = len(ws)
-    if spec is None:
-        N.check(N.lib().tsvpp_describe_warp(ctypes.byref(p), len(recs), fr, n, ws or None, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
-    else:
-        N.check(N.lib().tsvpp_describe_warp_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, n, ws or None, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
-    return _parse_selection(buf.value.decode())
+    def items(p, recs):
+        _, _, ws = _normalize_warps([None] * len(recs), [None] * len(recs), warps)
+        return len(ws), ws or None
+    return _describe_coord((N.lib().tsvpp_describe_warp, N.lib().tsvpp_describe_warp_tensor), items, params, frames, border, aligned_outputs, dtype, mean, std)
 
 
 def warp_rotated_box(cx, cy, box_w, box_h, angle_rad, dst_w, dst_h):
@@ -815,20 +795,11 @@ def _normalize_persps(ys, uvs, persps):
 def describe_perspective(params, frames, persps, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
     """What a convert_perspective of this request would launch, as a dict (tsvpp_describe_perspective: describe_warp's keys, mode persp_bilinear) -- host logic
     only, works without a GPU.  frames: as describe_rois; persps and border as for convert_perspective."""
-    p = params.parameters if isinstance(params, FrameParameters) else params
-    recs = _geometry_records(frames)
-    _, _, qs = _normalize_persps([None] * len(recs), [None] * len(recs), persps)
-    fr = (N.NV12 * len(recs))(*recs)
-    by, bu, bv = _border(border)
-    buf = ctypes.create_string_buffer(512)
-    spec = tensor_spec(dtype, mean, std)
-    n = len(qs)
-    if spec is None:
-        N.check(N.lib().tsvpp_describe_perspective(ctypes.byref(p), len(recs), fr, n, qs or None, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
-    else:
-        N.check(N.lib().tsvpp_describe_perspective_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, n, qs or None, by, bu, bv, 1 if aligned_outputs else 0, buf,
-                                                          len(buf)))
-    return _parse_selection(buf.value.decode())
+    def items(p, recs):
+        _, _, qs = _normalize_persps([None] * len(recs), [None] * len(recs), persps)
+        return len(qs), qs or None
+    return _describe_coord((N.lib().tsvpp_describe_perspective, N.lib().tsvpp_describe_perspective_tensor), items, params, frames, border, aligned_outputs, dtype, mean,
+                           std)
 
 
 def perspective_from_quad(quad, dst_w, dst_h):
@@ -909,20 +880,11 @@ def describe_remap(params, frames, maps, remaps=None, border=None, aligned_outpu
     """What a convert_remap of this request would launch, as a dict (tsvpp_describe_remap: describe_warp's keys with remaps= and maps= for warps= and without
     staged=, which the host cannot know; lds is the launch's dynamic LDS) -- host logic only, works without a GPU.  frames: as describe_rois; maps: as for
     convert_remap (tensors on any device: only strides and hints are read) or (pitch, lds_bytes) integers; remaps and border as for convert_remap."""
-    p = params.parameters if isinstance(params, FrameParameters) else params
-    recs = _geometry_records(frames)
-    ms = _normalize_maps(maps, p.dst_width, p.dst_height)
-    rs = _normalize_remaps(remaps, len(recs), len(ms))
-    fr = (N.NV12 * len(recs))(*recs)
-    by, bu, bv = _border(border)
-    buf = ctypes.create_string_buffer(512)
-    spec = tensor_spec(dtype, mean, std)
-    if spec is None:
-        N.check(N.lib().tsvpp_describe_remap(ctypes.byref(p), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
-    else:
-        N.check(N.lib().tsvpp_describe_remap_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv,
-                                                    1 if aligned_outputs else 0, buf, len(buf)))
-    return _parse_selection(buf.value.decode())
+    def items(p, recs):
+        ms = _normalize_maps(maps, p.dst_width, p.dst_height)
+        rs = _normalize_remaps(remaps, len(recs), len(ms))
+        return len(ms), ms, len(rs), rs
+    return _describe_coord((N.lib().tsvpp_describe_remap, N.lib().tsvpp_describe_remap_tensor), items, params, frames, border, aligned_outputs, dtype, mean, std)
 
 
 def remap_from_opencv(map_x, map_y):
@@ -1033,20 +995,11 @@ def describe_mesh(params, frames, meshes, cell=(16, 16), remaps=None, border=Non
     """What a convert_mesh of this request would launch, as a dict (tsvpp_describe_mesh: describe_remap's keys with meshes= and cell= for maps=, mode
     mesh_bilinear) -- host logic only, works without a GPU.  frames: as describe_rois; meshes: as for convert_mesh (tensors on any device: only strides and hints
     are read) or (pitch, lds_bytes) integers; cell, remaps and border as for convert_mesh."""
-    p = params.parameters if isinstance(params, FrameParameters) else params
-    recs = _geometry_records(frames)
-    ms = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height)
-    rs = _normalize_remaps(remaps, len(recs), len(ms))
-    fr = (N.NV12 * len(recs))(*recs)
-    by, bu, bv = _border(border)
-    buf = ctypes.create_string_buffer(512)
-    spec = tensor_spec(dtype, mean, std)
-    if spec is None:
-        N.check(N.lib().tsvpp_describe_mesh(ctypes.byref(p), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv, 1 if aligned_outputs else 0, buf, len(buf)))
-    else:
-        N.check(N.lib().tsvpp_describe_mesh_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, len(ms), ms, len(rs), rs, by, bu, bv,
-                                                   1 if aligned_outputs else 0, buf, len(buf)))
-    return _parse_selection(buf.value.decode())
+    def items(p, recs):
+        ms = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height)
+        rs = _normalize_remaps(remaps, len(recs), len(ms))
+        return len(ms), ms, len(rs), rs
+    return _describe_coord((N.lib().tsvpp_describe_mesh, N.lib().tsvpp_describe_mesh_tensor), items, params, frames, border, aligned_outputs, dtype, mean, std)
 
 
 def _host_pairs(a, what):

@@ -175,209 +175,146 @@ int VideoProcessor::ConvertInto(AVFrame *input, void *deviceOut, FrameParameters
     return VREADER_OK;
 }
 
-static int convertLetterbox(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY,
-                            int padU, int padV, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName);
-
-// ConvertRois, ConvertRoisArea and the tensor overload differ in the entry point of the C ABI they end in (`tensor`: tsvpp_convert_rois_tensor with `spec`)
-static int convertRois(bool area, bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts,
-                       FrameParameters &options, const std::string &consumerName) {
-    if (isClosed || !inputs || nInputs <= 0 || !rois || nRois <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
+// The tile calls -- every public method below -- share this body: the guard, the consumer's stream, the AVFrames as tsvpp_nv12, the flattened options (options.crop
+// must be empty in all of them: the items address the frames), then `call(frames, &p, stream)`, the one C ABI entry point the method names.  `itemsOk`: the
+// caller's own item pointers and counts are acceptable.  `method` is the public method's name, for the diagnostic.
+template <class Call>
+static int convertTiles(tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, bool itemsOk, void *const *deviceOuts, FrameParameters &options,
+                        const std::string &consumerName, const char *method, Call call) {
+    if (isClosed || !inputs || nInputs <= 0 || !itemsOk || !deviceOuts) return report(VREADER_ERROR, method, __LINE__);
     void *stream = nullptr;
-    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
+    if (int sts = tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)) return report(sts, method, __LINE__);
     std::vector<tsvpp_nv12> frames((size_t)nInputs);
     for (int f = 0; f < nInputs; f++) {
         const AVFrame *in = inputs[f];
-        if (!in) CHECK_STATUS(VREADER_ERROR);
+        if (!in) return report(VREADER_ERROR, method, __LINE__);
         frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
     }
-    const tsvpp_params p = flatten(options); // options.crop must be empty: the boxes are the crops
-    if (tensor) CHECK_STATUS(tsvpp_convert_rois_tensor(ctx, nInputs, frames.data(), nRois, rois, &p, spec, deviceOuts, stream));
-    else CHECK_STATUS((area ? tsvpp_convert_rois_area : tsvpp_convert_rois)(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
-    return VREADER_OK;
+    const tsvpp_params p = flatten(options);
+    return report(call(frames.data(), &p, stream), method, __LINE__);
 }
 
 int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                 std::string consumerName) {
-    return convertRois(false, false, nullptr, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRois",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_rois(ctx, nInputs, frames, nRois, rois, p, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertRoisArea(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                     std::string consumerName) {
-    return convertRois(true, false, nullptr, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRoisArea",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_rois_area(ctx, nInputs, frames, nRois, rois, p, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertRois(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                 const tsvpp_tensor_spec *spec, std::string consumerName) {
-    return convertRois(false, true, spec, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRois",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_rois_tensor(ctx, nInputs, frames, nRois, rois, p, spec, deviceOuts, stream);
+                        });
 }
 
-// ConvertRoisSized and its tensor overload (`spec` non-null: tsvpp_convert_rois_sized_tensor)
-static int convertRoisSized(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois,
-                            int nRois, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName) {
-    if (isClosed || !inputs || nInputs <= 0 || !rois || nRois <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
-    void *stream = nullptr;
-    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
-    std::vector<tsvpp_nv12> frames((size_t)nInputs);
-    for (int f = 0; f < nInputs; f++) {
-        const AVFrame *in = inputs[f];
-        if (!in) CHECK_STATUS(VREADER_ERROR);
-        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
-    }
-    const tsvpp_params p = flatten(options); // options.resize.width / height must be 0 (the sizes are the boxes'), options.crop empty
-    if (tensor) CHECK_STATUS(tsvpp_convert_rois_sized_tensor(ctx, nInputs, frames.data(), nRois, rois, &p, spec, deviceOuts, stream));
-    else CHECK_STATUS(tsvpp_convert_rois_sized(ctx, nInputs, frames.data(), nRois, rois, &p, deviceOuts, stream));
-    return VREADER_OK;
-}
-
+// options.resize.width / height must be 0: the sizes are the boxes'
 int VideoProcessor::ConvertRoisSized(AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                      std::string consumerName) {
-    return convertRoisSized(false, nullptr, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRoisSized",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_rois_sized(ctx, nInputs, frames, nRois, rois, p, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertRoisSized(AVFrame *const *inputs, int nInputs, const tsvpp_roi_sized *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                      const tsvpp_tensor_spec *spec, std::string consumerName) {
-    return convertRoisSized(true, spec, ctx, isClosed, inputs, nInputs, rois, nRois, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRoisSized",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_rois_sized_tensor(ctx, nInputs, frames, nRois, rois, p, spec, deviceOuts, stream);
+                        });
 }
 
+// options.resize is the canvas; null `rects` is legal (tsvpp_letterbox_rect's rectangles)
 int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                                      std::string consumerName) {
-    return convertLetterbox(false, nullptr, ctx, isClosed, inputs, n, rects, padY, padU, padV, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, n, true, deviceOuts, options, consumerName, "ConvertLetterbox",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_letterbox(ctx, n, frames, p, rects, padY, padU, padV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                                      const tsvpp_tensor_spec *spec, std::string consumerName) {
-    return convertLetterbox(true, spec, ctx, isClosed, inputs, n, rects, padY, padU, padV, deviceOuts, options, consumerName);
-}
-
-static int convertLetterbox(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY,
-                            int padU, int padV, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName) {
-    if (isClosed || !inputs || n <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
-    void *stream = nullptr;
-    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
-    std::vector<tsvpp_nv12> frames((size_t)n);
-    for (int f = 0; f < n; f++) {
-        const AVFrame *in = inputs[f];
-        if (!in) CHECK_STATUS(VREADER_ERROR);
-        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
-    }
-    const tsvpp_params p = flatten(options); // options.resize is the canvas; options.crop must be empty
-    if (tensor) CHECK_STATUS(tsvpp_convert_letterbox_tensor(ctx, n, frames.data(), &p, spec, rects, padY, padU, padV, deviceOuts, stream));
-    else CHECK_STATUS(tsvpp_convert_letterbox(ctx, n, frames.data(), &p, rects, padY, padU, padV, deviceOuts, stream));
-    return VREADER_OK;
-}
-
-// ConvertWarp and its tensor overload differ in the entry point of the C ABI they end in (`tensor`: tsvpp_convert_warp_tensor with `spec`)
-static int convertWarp(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps,
-                       int borderY, int borderU, int borderV, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName) {
-    if (isClosed || !inputs || nInputs <= 0 || !warps || nWarps <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
-    void *stream = nullptr;
-    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
-    std::vector<tsvpp_nv12> frames((size_t)nInputs);
-    for (int f = 0; f < nInputs; f++) {
-        const AVFrame *in = inputs[f];
-        if (!in) CHECK_STATUS(VREADER_ERROR);
-        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
-    }
-    const tsvpp_params p = flatten(options); // options.crop must be empty: the matrices address the whole frame
-    if (tensor) CHECK_STATUS(tsvpp_convert_warp_tensor(ctx, nInputs, frames.data(), nWarps, warps, &p, spec, borderY, borderU, borderV, deviceOuts, stream));
-    else CHECK_STATUS(tsvpp_convert_warp(ctx, nInputs, frames.data(), nWarps, warps, &p, borderY, borderU, borderV, deviceOuts, stream));
-    return VREADER_OK;
+    return convertTiles(ctx, isClosed, inputs, n, true, deviceOuts, options, consumerName, "ConvertLetterbox",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_letterbox_tensor(ctx, n, frames, p, spec, rects, padY, padU, padV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
                                 FrameParameters &options, std::string consumerName) {
-    return convertWarp(false, nullptr, ctx, isClosed, inputs, nInputs, warps, nWarps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, warps && nWarps > 0, deviceOuts, options, consumerName, "ConvertWarp",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_warp(ctx, nInputs, frames, nWarps, warps, p, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
                                 FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
-    return convertWarp(true, spec, ctx, isClosed, inputs, nInputs, warps, nWarps, borderY, borderU, borderV, deviceOuts, options, consumerName);
-}
-
-// ConvertPerspective and its tensor overload, as convertWarp (`tensor`: tsvpp_convert_perspective_tensor with `spec`)
-static int convertPerspective(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps,
-                              int nPersps, int borderY, int borderU, int borderV, void *const *deviceOuts, FrameParameters &options, const std::string &consumerName) {
-    if (isClosed || !inputs || nInputs <= 0 || !persps || nPersps <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
-    void *stream = nullptr;
-    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
-    std::vector<tsvpp_nv12> frames((size_t)nInputs);
-    for (int f = 0; f < nInputs; f++) {
-        const AVFrame *in = inputs[f];
-        if (!in) CHECK_STATUS(VREADER_ERROR);
-        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
-    }
-    const tsvpp_params p = flatten(options); // options.crop must be empty: the homographies address the whole frame
-    if (tensor) CHECK_STATUS(tsvpp_convert_perspective_tensor(ctx, nInputs, frames.data(), nPersps, persps, &p, spec, borderY, borderU, borderV, deviceOuts, stream));
-    else CHECK_STATUS(tsvpp_convert_perspective(ctx, nInputs, frames.data(), nPersps, persps, &p, borderY, borderU, borderV, deviceOuts, stream));
-    return VREADER_OK;
+    return convertTiles(ctx, isClosed, inputs, nInputs, warps && nWarps > 0, deviceOuts, options, consumerName, "ConvertWarp",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_warp_tensor(ctx, nInputs, frames, nWarps, warps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertPerspective(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV,
                                        void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
-    return convertPerspective(false, nullptr, ctx, isClosed, inputs, nInputs, persps, nPersps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, persps && nPersps > 0, deviceOuts, options, consumerName, "ConvertPerspective",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_perspective(ctx, nInputs, frames, nPersps, persps, p, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertPerspective(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV,
                                        void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
-    return convertPerspective(true, spec, ctx, isClosed, inputs, nInputs, persps, nPersps, borderY, borderU, borderV, deviceOuts, options, consumerName);
-}
-
-// ConvertRemap and its tensor overload, as convertWarp (`tensor`: tsvpp_convert_remap_tensor with `spec`)
-static int convertRemap(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps,
-                        const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV, void *const *deviceOuts, FrameParameters &options,
-                        const std::string &consumerName) {
-    if (isClosed || !inputs || nInputs <= 0 || !maps || nMaps <= 0 || !remaps || nRemaps <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
-    void *stream = nullptr;
-    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
-    std::vector<tsvpp_nv12> frames((size_t)nInputs);
-    for (int f = 0; f < nInputs; f++) {
-        const AVFrame *in = inputs[f];
-        if (!in) CHECK_STATUS(VREADER_ERROR);
-        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
-    }
-    const tsvpp_params p = flatten(options); // options.crop must be empty: the maps address the whole frame
-    if (tensor) CHECK_STATUS(tsvpp_convert_remap_tensor(ctx, nInputs, frames.data(), nMaps, maps, nRemaps, remaps, &p, spec, borderY, borderU, borderV, deviceOuts, stream));
-    else CHECK_STATUS(tsvpp_convert_remap(ctx, nInputs, frames.data(), nMaps, maps, nRemaps, remaps, &p, borderY, borderU, borderV, deviceOuts, stream));
-    return VREADER_OK;
+    return convertTiles(ctx, isClosed, inputs, nInputs, persps && nPersps > 0, deviceOuts, options, consumerName, "ConvertPerspective",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_perspective_tensor(ctx, nInputs, frames, nPersps, persps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
                                  int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
-    return convertRemap(false, nullptr, ctx, isClosed, inputs, nInputs, maps, nMaps, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, maps && nMaps > 0 && remaps && nRemaps > 0, deviceOuts, options, consumerName, "ConvertRemap",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_remap(ctx, nInputs, frames, nMaps, maps, nRemaps, remaps, p, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
                                  int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
-    return convertRemap(true, spec, ctx, isClosed, inputs, nInputs, maps, nMaps, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
-}
-
-// ConvertMesh and its tensor overload, as convertRemap (`tensor`: tsvpp_convert_mesh_tensor with `spec`)
-static int convertMesh(bool tensor, const tsvpp_tensor_spec *spec, tsvpp_ctx *ctx, bool isClosed, AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes,
-                       const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV, void *const *deviceOuts, FrameParameters &options,
-                       const std::string &consumerName) {
-    if (isClosed || !inputs || nInputs <= 0 || !meshes || nMeshes <= 0 || !remaps || nRemaps <= 0 || !deviceOuts) CHECK_STATUS(VREADER_ERROR);
-    void *stream = nullptr;
-    CHECK_STATUS(tsvpp_consumer_stream(ctx, consumerName.c_str(), &stream)); // always the consumer's FIRST stream: an ordinary in-order launch (include/tsvpp.h)
-    std::vector<tsvpp_nv12> frames((size_t)nInputs);
-    for (int f = 0; f < nInputs; f++) {
-        const AVFrame *in = inputs[f];
-        if (!in) CHECK_STATUS(VREADER_ERROR);
-        frames[(size_t)f] = tsvpp_nv12{ in->data[0], in->data[1], in->linesize[0], in->linesize[1], in->width, in->height };
-    }
-    const tsvpp_params p = flatten(options); // options.crop must be empty: the meshes address the whole frame
-    if (tensor) CHECK_STATUS(tsvpp_convert_mesh_tensor(ctx, nInputs, frames.data(), nMeshes, meshes, nRemaps, remaps, &p, spec, borderY, borderU, borderV, deviceOuts, stream));
-    else CHECK_STATUS(tsvpp_convert_mesh(ctx, nInputs, frames.data(), nMeshes, meshes, nRemaps, remaps, &p, borderY, borderU, borderV, deviceOuts, stream));
-    return VREADER_OK;
+    return convertTiles(ctx, isClosed, inputs, nInputs, maps && nMaps > 0 && remaps && nRemaps > 0, deviceOuts, options, consumerName, "ConvertRemap",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_remap_tensor(ctx, nInputs, frames, nMaps, maps, nRemaps, remaps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
                                 int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
-    return convertMesh(false, nullptr, ctx, isClosed, inputs, nInputs, meshes, nMeshes, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, meshes && nMeshes > 0 && remaps && nRemaps > 0, deviceOuts, options, consumerName, "ConvertMesh",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_mesh(ctx, nInputs, frames, nMeshes, meshes, nRemaps, remaps, p, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
                                 int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
-    return convertMesh(true, spec, ctx, isClosed, inputs, nInputs, meshes, nMeshes, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, consumerName);
+    return convertTiles(ctx, isClosed, inputs, nInputs, meshes && nMeshes > 0 && remaps && nRemaps > 0, deviceOuts, options, consumerName, "ConvertMesh",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_mesh_tensor(ctx, nInputs, frames, nMeshes, meshes, nRemaps, remaps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
 }
 
 int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &options, std::string consumerName) {

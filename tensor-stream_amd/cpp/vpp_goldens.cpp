@@ -4,39 +4,16 @@
 // tests/test_cpp_goldens_gpu.py with the reference's 38 literals (tests/golden/reference_crcs.py) on frame 0 of its own clip.
 //   vpp_goldens frame.nv12 W H table.txt      table line: fourcc planes dstW dstH resize cropL cropT cropR cropB crc [crc2]
 // Prints "<line> ok|FAIL <crc of opaque> <crc of the dump>" per case; exit code = number of failures.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "VideoProcessor.h"
-
-// av_crc(av_crc_get_table(AV_CRC_32_IEEE), -1, buf, n) as the reference's tests call it: libavutil's table is the MSB-first
-// polynomial 0x04C11DB7 run on a byte-swapped state, no final xor (validated by the decoder test's plane CRCs, which this
-// program checks first: tests/src/DecoderTests.cpp:63-65).
-static uint32_t crc32_av(const uint8_t *buf, size_t n) {
-    uint32_t c = __builtin_bswap32(0xFFFFFFFFu);
-    for (size_t i = 0; i < n; i++) {
-        c ^= (uint32_t)buf[i] << 24;
-        for (int k = 0; k < 8; k++) c = (c & 0x80000000u) ? (c << 1) ^ 0x04C11DB7u : (c << 1);
-    }
-    return __builtin_bswap32(c);
-}
+#include "check_common.h"
 
 int main(int argc, char **argv) {
     if (argc < 5) { fprintf(stderr, "usage: vpp_goldens frame.nv12 W H table.txt\n"); return 200; }
     const int W = atoi(argv[2]), H = atoi(argv[3]);
-    std::vector<uint8_t> host((size_t)W * H * 3 / 2);
-    FILE *f = fopen(argv[1], "rb");
-    if (!f || fread(host.data(), 1, host.size(), f) != host.size()) { fprintf(stderr, "cannot read %s\n", argv[1]); return 201; }
-    fclose(f);
+    std::vector<uint8_t> host; // the decoder test copies the planes tight: the pitch is W
+    if (int sts = read_nv12(argv[1], H, W, host)) return sts;
     printf("input Y %u UV %u\n", crc32_av(host.data(), (size_t)W * H), crc32_av(host.data() + (size_t)W * H, (size_t)W * H / 2));
     uint8_t *dY = nullptr, *dUV = nullptr;
-    if (hipMalloc(&dY, (size_t)W * H) != hipSuccess || hipMalloc(&dUV, (size_t)W * H / 2) != hipSuccess) return 202;
-    (void)hipMemcpy(dY, host.data(), (size_t)W * H, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dUV, host.data() + (size_t)W * H, (size_t)W * H / 2, hipMemcpyHostToDevice);
+    if (int sts = upload_nv12(host, H, W, dY, dUV)) return sts;
 
     FILE *tab = fopen(argv[4], "r");
     if (!tab) return 203;
@@ -50,12 +27,7 @@ int main(int argc, char **argv) {
         if (got < 11) c2 = c1;
         VideoProcessor vpp;
         if (vpp.Init(std::make_shared<Logger>()) != 0) return 204;
-        AVFrame *input = av_frame_alloc(), *converted = av_frame_alloc();
-        input->data[0] = dY;
-        input->data[1] = dUV;
-        input->linesize[0] = input->linesize[1] = W; // the decoder test copies the planes tight
-        input->width = W;
-        input->height = H;
+        AVFrame *input = nv12_frame(dY, dUV, W, H, W), *converted = av_frame_alloc();
         ColorOptions color((FourCC)fcc);
         color.planesPos = (Planes)planes;
         ResizeOptions resize(dw, dh);

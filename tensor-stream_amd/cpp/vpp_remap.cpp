@@ -4,25 +4,7 @@
 // --dtype / --mean / --scale: through the ConvertRemap overload that takes a tsvpp_tensor_spec.  BY BU BV: the border sample, or -1 -1 -1 to replicate the edge.
 // A map file is raw fp32: DH rows of DW (x, y) pairs, tight.  The frame file holds H rows of PITCH bytes of luma, then H / 2 rows of PITCH bytes of chroma.
 // Output k samples the frame through map k.  Prints "<index> <crc> <bytes>" per output; exit code 0 = converted.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "VideoProcessor.h"
-#include "tensor_flags.h"
-
-static uint32_t crc32_zlib(const uint8_t *buf, size_t n) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; i++) {
-        c ^= buf[i];
-        for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : (c >> 1);
-    }
-    return c ^ 0xFFFFFFFFu;
-}
+#include "check_common.h"
 
 int main(int argc, char **argv) {
     tsvpp_tensor_spec spec;
@@ -37,14 +19,8 @@ int main(int argc, char **argv) {
     const int W = atoi(argv[10]), H = atoi(argv[11]), P = atoi(argv[12]);
     const int n = argc - 13;
     if (DW <= 0 || DH <= 0 || W <= 0 || H <= 0 || P < W) return 200;
-    std::vector<uint8_t> host((size_t)P * H * 3 / 2);
-    FILE *f = fopen(path, "rb");
-    if (!f || fread(host.data(), 1, host.size(), f) != host.size()) { fprintf(stderr, "cannot read %s\n", path); return 201; }
-    fclose(f);
     uint8_t *dY = nullptr, *dUV = nullptr;
-    if (hipMalloc(&dY, (size_t)P * H) != hipSuccess || hipMalloc(&dUV, (size_t)P * H / 2) != hipSuccess) return 202;
-    (void)hipMemcpy(dY, host.data(), (size_t)P * H, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dUV, host.data() + (size_t)P * H, (size_t)P * H / 2, hipMemcpyHostToDevice);
+    if (int sts = load_nv12(path, H, P, dY, dUV)) return sts;
     // the maps: one device allocation, map k at k * map_bytes (a multiple of 8)
     const size_t map_bytes = (size_t)DW * DH * 2 * sizeof(float);
     std::vector<uint8_t> map_host(map_bytes);
@@ -53,57 +29,33 @@ int main(int argc, char **argv) {
     std::vector<tsvpp_map> maps((size_t)n);
     std::vector<tsvpp_remap> remaps((size_t)n);
     for (int k = 0; k < n; k++) {
-        FILE *m = fopen(argv[13 + k], "rb");
-        if (!m || fread(map_host.data(), 1, map_bytes, m) != map_bytes) { fprintf(stderr, "cannot read %s\n", argv[13 + k]); return 201; }
-        fclose(m);
+        if (!read_file(argv[13 + k], map_host.data(), map_bytes)) return 201;
         (void)hipMemcpy(dMaps + (size_t)k * map_bytes, map_host.data(), map_bytes, hipMemcpyHostToDevice);
         maps[(size_t)k] = tsvpp_map{ (const float *)(dMaps + (size_t)k * map_bytes), 0, 0 };
         remaps[(size_t)k] = tsvpp_remap{ 0, k };
     }
-    AVFrame *input = av_frame_alloc();
-    input->data[0] = dY;
-    input->data[1] = dUV;
-    input->linesize[0] = input->linesize[1] = P;
-    input->width = W;
-    input->height = H;
+    AVFrame *input = nv12_frame(dY, dUV, W, H, P);
     AVFrame *inputs[1] = { input };
 
     VideoProcessor vpp;
     if (vpp.Init(std::make_shared<Logger>()) != 0) return 203;
-    ColorOptions color((FourCC)fcc);
-    color.planesPos = (Planes)planes;
-    color.normalization = norm != 0;
-    ResizeOptions resize(DW, DH);
-    resize.type = (ResizeType)TSVPP_BILINEAR;
-    FrameParameters options(resize, color);
-    size_t bytes = (size_t)(channelsByFourCC((FourCC)fcc) * (float)DW) * (size_t)DH * (norm ? sizeof(float) : 1);
-    if (tensor) {
-        const tsvpp_params flat{ 0, 0, 0, 0, DW, DH, TSVPP_BILINEAR, fcc, planes, norm };
-        bytes = tsvpp_tensor_bytes(&flat, &spec);
-        if (bytes == 0) return 205; // a (parameters, spec) pair the tensor entry points refuse
-    }
-    const size_t stride = (bytes + 255) & ~(size_t)255;
-    uint8_t *dOut = nullptr;
-    if (hipMalloc(&dOut, stride * (size_t)n) != hipSuccess) return 204;
-    std::vector<void *> outs((size_t)n);
-    for (int k = 0; k < n; k++) outs[(size_t)k] = dOut + (size_t)k * stride;
-    const int sts = tensor ? vpp.ConvertRemap(inputs, 1, maps.data(), n, remaps.data(), n, bY, bU, bV, outs.data(), options, &spec, "remap")
-                           : vpp.ConvertRemap(inputs, 1, maps.data(), n, remaps.data(), n, bY, bU, bV, outs.data(), options, "remap");
+    FrameParameters options = frame_parameters(DW, DH, TSVPP_BILINEAR, fcc, planes, norm);
+    size_t bytes = 0;
+    if (int sts = output_bytes(DW, DH, TSVPP_BILINEAR, fcc, planes, norm, tensor ? &spec : nullptr, bytes)) return sts;
+    OutputArena arena;
+    if (int sts = arena.carve((size_t)n, bytes)) return sts;
+    const int sts = tensor ? vpp.ConvertRemap(inputs, 1, maps.data(), n, remaps.data(), n, bY, bU, bV, arena.outs.data(), options, &spec, "remap")
+                           : vpp.ConvertRemap(inputs, 1, maps.data(), n, remaps.data(), n, bY, bU, bV, arena.outs.data(), options, "remap");
     if (sts != 0) return 210;
-    if (tsvpp_consumer_synchronize(vpp.context(), "remap") != 0) return 211; // the conversion is asynchronous, on the consumer's stream
-    std::vector<uint8_t> result(bytes);
-    for (int k = 0; k < n; k++) {
-        if (hipMemcpy(result.data(), outs[(size_t)k], bytes, hipMemcpyDeviceToHost) != hipSuccess) return 212;
-        printf("%d %u %zu\n", k, crc32_zlib(result.data(), bytes), bytes);
-    }
+    if (int failed = print_outputs(vpp, "remap", arena, crc32_zlib)) return failed;
     // a map index that was not given is refused with the reference's status convention, and nothing is launched
     const tsvpp_remap bad = { 0, n };
-    const int refused = tensor ? vpp.ConvertRemap(inputs, 1, maps.data(), n, &bad, 1, bY, bU, bV, outs.data(), options, &spec, "remap")
-                               : vpp.ConvertRemap(inputs, 1, maps.data(), n, &bad, 1, bY, bU, bV, outs.data(), options, "remap");
+    const int refused = tensor ? vpp.ConvertRemap(inputs, 1, maps.data(), n, &bad, 1, bY, bU, bV, arena.outs.data(), options, &spec, "remap")
+                               : vpp.ConvertRemap(inputs, 1, maps.data(), n, &bad, 1, bY, bU, bV, arena.outs.data(), options, "remap");
     if (refused != VREADER_ERROR) return 214;
     av_frame_free(&input);
     vpp.Close();
-    (void)hipFree(dOut);
+    arena.release();
     (void)hipFree(dMaps);
     (void)hipFree(dY);
     (void)hipFree(dUV);

@@ -4,15 +4,7 @@
 // full conversions.
 //   vpp_stages frame.nv12 W H PITCH  L T R B  DW DH TYPE  FOURCC PLANES NORM  prefix
 // L..B = 0 0 0 0 skips the crop stage, DW DH = 0 0 skips the resize stage (both as Convert does).  Exit code 0 = all stages ran.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
-
-#include "VideoProcessor.h"
+#include "check_common.h"
 
 static bool dump(const std::string &name, const void *dev, size_t bytes) {
     std::vector<uint8_t> host(bytes);
@@ -31,23 +23,12 @@ int main(int argc, char **argv) {
     const int DW = atoi(argv[9]), DH = atoi(argv[10]), type = atoi(argv[11]);
     const int fcc = atoi(argv[12]), planes = atoi(argv[13]), norm = atoi(argv[14]);
     const std::string prefix = argv[15];
-    std::vector<uint8_t> host((size_t)P * H * 3 / 2); // the file holds H rows of P bytes of luma, then H / 2 rows of P bytes of chroma
-    FILE *f = fopen(argv[1], "rb");
-    if (!f || fread(host.data(), 1, host.size(), f) != host.size()) { fprintf(stderr, "cannot read %s\n", argv[1]); return 201; }
-    fclose(f);
     uint8_t *dY = nullptr, *dUV = nullptr;
-    if (hipMalloc(&dY, (size_t)P * H) != hipSuccess || hipMalloc(&dUV, (size_t)P * H / 2) != hipSuccess) return 202;
-    (void)hipMemcpy(dY, host.data(), (size_t)P * H, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dUV, host.data() + (size_t)P * H, (size_t)P * H / 2, hipMemcpyHostToDevice);
+    if (int sts = load_nv12(argv[1], H, P, dY, dUV)) return sts; // the file holds H rows of P bytes of luma, then H / 2 rows of P bytes of chroma
     hipStream_t stream;
     if (hipStreamCreate(&stream) != hipSuccess) return 203;
 
-    AVFrame *input = av_frame_alloc(), *output = av_frame_alloc();
-    input->data[0] = dY;
-    input->data[1] = dUV;
-    input->linesize[0] = input->linesize[1] = P;
-    input->width = W;
-    input->height = H;
+    AVFrame *input = nv12_frame(dY, dUV, W, H, P), *output = av_frame_alloc();
     output->width = W;
     output->height = H;
     AVFrame *cur = input;

@@ -1,11 +1,11 @@
 """GPU: VideoProcessor::ConvertLetterbox of the C++ class (tensor-stream_amd/cpp/VideoProcessor.h) through its check program vpp_letterbox: the CRC-32 it prints
 per canvas (zlib's, over the device result) equals zlib.crc32 of the expected canvas (tests/letterbox_util.py: the contract of tsvpp_convert_letterbox)."""
 import os
-import subprocess
 import zlib
 
 import pytest
 
+from cpp_check import run_check, write_nv12
 from letterbox_util import default_rect, expected_canvas
 from util import synth_nv12
 
@@ -27,14 +27,11 @@ def test_crc_per_canvas(oracle, tmp_path, canvas, rtype, fourcc, planes, norm, p
     for k, (w, h, pitch) in enumerate(GEO):
         y, uv = synth_nv12(w, h, seed=900 + k + canvas[0], pitch=pitch)
         src = tmp_path / f"in{k}.nv12"
-        with open(src, "wb") as f:
-            f.write(y.tobytes())
-            f.write(uv.tobytes())
+        write_nv12(src, y, uv)
         frames.append((y, uv))
         args += [src, w, h, pitch]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=300)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(GEO), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(GEO), (rc, *tails)
     for (idx, crc, nbytes, *rect), (w, h, _), (y, uv) in zip(lines, GEO, frames):
         want = default_rect(w, h, *canvas)
         assert tuple(int(v) for v in rect) == want, (idx, rect, want)
@@ -42,4 +39,4 @@ def test_crc_per_canvas(oracle, tmp_path, canvas, rtype, fourcc, planes, norm, p
         assert int(nbytes) == ref.size
         assert int(crc) == zlib.crc32(ref.tobytes()), f"canvas {idx} {(w, h)} -> {canvas}"
     # (after the canvases the program asks for a rectangle outside the canvas: refused with VREADER_ERROR; exit code 0 = all of it held)
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)

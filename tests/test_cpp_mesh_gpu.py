@@ -2,7 +2,6 @@
 (zlib's, over the device result) equals zlib.crc32 of the expected output (tests/mesh_util.py's E(mesh) through tests/remap_util.py: the contract of
 tsvpp_convert_mesh)."""
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 import mesh_util as M
 import remap_util as R
 import tensor_util as T
+from cpp_check import run_check, write_nv12
 from util import synth_nv12
 
 pytestmark = pytest.mark.gpu
@@ -31,9 +31,7 @@ def test_crc_per_output(oracle, tmp_path, dst, cell, fourcc, planes, norm, borde
     w, h, pitch = GEO
     y, uv = synth_nv12(w, h, seed=1800 + dst[0], pitch=pitch)
     src = tmp_path / "in.nv12"
-    with open(src, "wb") as f:
-        f.write(y.tobytes())
-        f.write(uv.tobytes())
+    write_nv12(src, y, uv)
     ms = M.mesh_set(w, h, *dst, cell)
     files = []
     for name in NAMES:
@@ -44,9 +42,8 @@ def test_crc_per_output(oracle, tmp_path, dst, cell, fourcc, planes, norm, borde
         sc = T.scales(T.IMAGENET[1])
         args += ["--dtype", dtype, "--mean", ",".join(float(np.float32(v)).hex() for v in T.IMAGENET[0]), "--scale", ",".join(float(v).hex() for v in sc)]
     args += [*dst, fourcc, planes, int(norm), *border, src, w, h, pitch, M.log2(cell[0]), M.log2(cell[1]), *files]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=300)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(NAMES), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(NAMES), (rc, *tails)
     for (idx, crc, nbytes), name in zip(lines, NAMES):
         ref = R.expected(oracle, y, uv, w, h, M.expand(ms[name], *dst, cell), fourcc, planes, norm, None if border[0] < 0 else border)
         if dtype is not None:
@@ -54,4 +51,4 @@ def test_crc_per_output(oracle, tmp_path, dst, cell, fourcc, planes, norm, borde
         assert int(nbytes) == ref.size
         assert int(crc) == zlib.crc32(ref.tobytes()), f"output {idx} mesh {name} cell {cell} -> {dst}"
     # (after the outputs the program asks for a mesh index it did not give: refused with VREADER_ERROR; exit code 0 = all of it held)
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)

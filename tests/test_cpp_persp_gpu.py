@@ -1,7 +1,6 @@
 """GPU: VideoProcessor::ConvertPerspective of the C++ class (tensor-stream_amd/cpp/VideoProcessor.h) through its check program vpp_persp: the CRC-32 it prints per
 output (zlib's, over the device result) equals zlib.crc32 of the expected output (tests/persp_util.py: the contract of tsvpp_convert_perspective)."""
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 import persp_util as P
 import tensor_util as T
 import warp_util as W
+from cpp_check import run_check, write_nv12
 from util import synth_nv12
 
 pytestmark = pytest.mark.gpu
@@ -38,9 +38,7 @@ def test_crc_per_output(oracle, tmp_path, kind, dst, fourcc, planes, norm, borde
     w, h, pitch = GEO
     y, uv = synth_nv12(w, h, seed=1600 + dst[0], pitch=pitch)
     src = tmp_path / "in.nv12"
-    with open(src, "wb") as f:
-        f.write(y.tobytes())
-        f.write(uv.tobytes())
+    write_nv12(src, y, uv)
     hs = [P.affine(W.scale_only(w, h, *dst))] if kind == "scale_only" else quads(dst)
     args = [EXE]
     if dtype is not None:
@@ -49,9 +47,8 @@ def test_crc_per_output(oracle, tmp_path, kind, dst, fourcc, planes, norm, borde
     args += [*dst, fourcc, planes, int(norm), *border, src, w, h, pitch]
     for hm in hs:
         args += [float(np.float32(v)).hex() for v in hm]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=300)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(hs), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(hs), (rc, *tails)
     for (idx, crc, nbytes), hm in zip(lines, hs):
         ref = P.expected(oracle, y, uv, w, h, hm, dst, fourcc, planes, norm, None if border[0] < 0 else border)
         if dtype is not None:
@@ -59,4 +56,4 @@ def test_crc_per_output(oracle, tmp_path, kind, dst, fourcc, planes, norm, borde
         assert int(nbytes) == ref.size
         assert int(crc) == zlib.crc32(ref.tobytes()), f"output {idx} h={hm} -> {dst}"
     # (after the outputs the program asks for a homography of a frame it did not give: refused with VREADER_ERROR; exit code 0 = all of it held)
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)

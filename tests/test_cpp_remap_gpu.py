@@ -1,7 +1,6 @@
 """GPU: VideoProcessor::ConvertRemap of the C++ class (tensor-stream_amd/cpp/VideoProcessor.h) through its check program vpp_remap: the CRC-32 it prints per output
 (zlib's, over the device result) equals zlib.crc32 of the expected output (tests/remap_util.py: the contract of tsvpp_convert_remap)."""
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -9,6 +8,7 @@ import pytest
 
 import remap_util as R
 import tensor_util as T
+from cpp_check import run_check, write_nv12
 from util import synth_nv12
 
 pytestmark = pytest.mark.gpu
@@ -29,9 +29,7 @@ def test_crc_per_output(oracle, tmp_path, dst, fourcc, planes, norm, border, dty
     w, h, pitch = GEO
     y, uv = synth_nv12(w, h, seed=1600 + dst[0], pitch=pitch)
     src = tmp_path / "in.nv12"
-    with open(src, "wb") as f:
-        f.write(y.tobytes())
-        f.write(uv.tobytes())
+    write_nv12(src, y, uv)
     ms = R.map_set(w, h, *dst)
     files = []
     for name in NAMES:
@@ -42,9 +40,8 @@ def test_crc_per_output(oracle, tmp_path, dst, fourcc, planes, norm, border, dty
         sc = T.scales(T.IMAGENET[1])
         args += ["--dtype", dtype, "--mean", ",".join(float(np.float32(v)).hex() for v in T.IMAGENET[0]), "--scale", ",".join(float(v).hex() for v in sc)]
     args += [*dst, fourcc, planes, int(norm), *border, src, w, h, pitch, *files]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=300)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(NAMES), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(NAMES), (rc, *tails)
     for (idx, crc, nbytes), name in zip(lines, NAMES):
         ref = R.expected(oracle, y, uv, w, h, ms[name], fourcc, planes, norm, None if border[0] < 0 else border)
         if dtype is not None:
@@ -52,4 +49,4 @@ def test_crc_per_output(oracle, tmp_path, dst, fourcc, planes, norm, border, dty
         assert int(nbytes) == ref.size
         assert int(crc) == zlib.crc32(ref.tobytes()), f"output {idx} map {name} -> {dst}"
     # (after the outputs the program asks for a map index it did not give: refused with VREADER_ERROR; exit code 0 = all of it held)
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)

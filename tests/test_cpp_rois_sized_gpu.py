@@ -2,11 +2,11 @@
 per box (libavutil's AV_CRC_32_IEEE over the device result) equals the oracle's over its own bytes for the box's sliced planes at the box's own size (the contract
 of tsvpp_convert_rois_sized); then the program asks for a request with the parameters' own size set and checks that it is refused."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cpp_check import run_check, write_nv12
 from util import synth_nv12
 
 pytestmark = pytest.mark.gpu
@@ -27,13 +27,10 @@ def test_crc_per_box(oracle, tmp_path, pitch, rtype, fourcc, planes, norm):
     w, h = 1280, 720
     y, uv = synth_nv12(w, h, seed=pitch + rtype + fourcc, pitch=pitch)
     src = tmp_path / "in.nv12"
-    with open(src, "wb") as f:
-        f.write(y.tobytes())
-        f.write(uv.tobytes())
+    write_nv12(src, y, uv)
     args = [EXE, str(src), w, h, pitch, rtype, fourcc, planes, int(norm)] + [v for b in BOXES for v in b]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=300)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(BOXES), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(BOXES), (rc, *tails)
     for (idx, crc, nbytes), (l, t, rr, b, dw, dh) in zip(lines, BOXES):
         ys = y[t:b, l:rr]
         uvs = uv[t // 2:t // 2 + (b - t) // 2, l:rr]
@@ -41,4 +38,4 @@ def test_crc_per_box(oracle, tmp_path, pitch, rtype, fourcc, planes, norm):
         assert int(nbytes) == ref.view(np.uint8).size
         assert int(crc) == oracle.av_crc32_ieee(ref), f"box {idx} {(l, t, rr, b)} -> {(dw, dh)}"
     # (after the boxes the program sets the parameters' own size: refused with VREADER_ERROR, reported as CHECK_STATUS does; exit code 0 = all of it held)
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)

@@ -2,12 +2,12 @@
 `vpp_rois --dtype f16 ...` and `vpp_letterbox --dtype bf16 ...` print per output equals the CRC of the expected bytes (tensor_util: the existing oracle's fp32
 result, the float32 affine step, a round-to-nearest-even conversion)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import tensor_util as T
+from cpp_check import run_check, write_nv12
 from letterbox_util import default_rect, expected_canvas
 from util import synth_nv12
 
@@ -18,12 +18,6 @@ BILINEAR, BICUBIC = 1, 2
 RGB24, BGR24 = 1, 2
 PLANAR = 0
 MEAN, STD = T.IMAGENET
-
-
-def write_frame(path, y, uv):
-    with open(path, "wb") as f:
-        f.write(y.tobytes())
-        f.write(uv.tobytes())
 
 
 def flags(dtype):
@@ -38,18 +32,17 @@ def test_vpp_rois_fp16_crc_per_box(oracle, tmp_path):
     assert os.path.exists(exe), "vpp_rois not built (python -c 'import __graft_entry__ as g; g.build()')"
     w, h, pitch, dst = 322, 182, 384, (64, 64)
     y, uv = synth_nv12(w, h, seed=41, pitch=pitch)
-    write_frame(tmp_path / "in.nv12", y, uv)
+    write_nv12(tmp_path / "in.nv12", y, uv)
     boxes = [(40, 30, 140, 100), (101, 20, 201, 90), (100, 60, 164, 124), (262, 132, 322, 182)]
     args = [exe] + flags("f16") + [str(tmp_path / "in.nv12"), w, h, pitch, *dst, BILINEAR, BGR24, PLANAR, 1] + [v for b in boxes for v in b]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=120)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(boxes), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(boxes), (rc, *tails)
     for (idx, crc, nbytes), (l, t, rr, b) in zip(lines, boxes):
         q = oracle.convert(y[t:b, l:rr], uv[t // 2:t // 2 + (b - t) // 2, l:rr], dst=dst, resize_type=BILINEAR, fourcc=BGR24, planes=PLANAR, normalization=True)[0]
         want = T.expected(q, 3, T.IMAGENET, T.F16)
         assert int(nbytes) == want.size == 3 * 64 * 64 * 2
         assert int(crc) == oracle.av_crc32_ieee(want), f"box {idx} {(l, t, rr, b)}"
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)
 
 
 def test_vpp_letterbox_bf16_crc_per_canvas(oracle, tmp_path):
@@ -62,11 +55,10 @@ def test_vpp_letterbox_bf16_crc_per_canvas(oracle, tmp_path):
     for k, (w, h, p) in enumerate(geo):
         y, uv = synth_nv12(w, h, seed=51 + k, pitch=p)
         host.append((y, uv))
-        write_frame(tmp_path / f"f{k}.nv12", y, uv)
+        write_nv12(tmp_path / f"f{k}.nv12", y, uv)
         args += [str(tmp_path / f"f{k}.nv12"), w, h, p]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=120)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(geo), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(geo), (rc, *tails)
     for k, ln in enumerate(lines):
         w, h, _ = geo[k]
         rect = default_rect(w, h, *canvas)
@@ -75,4 +67,4 @@ def test_vpp_letterbox_bf16_crc_per_canvas(oracle, tmp_path):
         want = T.expected(q, 3, T.IMAGENET, T.BF16)
         assert int(ln[2]) == want.size == 3 * 70 * 66 * 2
         assert int(ln[1]) == T.crc32_zlib(want), f"canvas {k}"
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)

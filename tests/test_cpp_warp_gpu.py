@@ -2,7 +2,6 @@
 (zlib's, over the device result) equals zlib.crc32 of the expected output (tests/warp_util.py: the contract of tsvpp_convert_warp)."""
 import math
 import os
-import subprocess
 import zlib
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 
 import tensor_util as T
 import warp_util as W
+from cpp_check import run_check, write_nv12
 from util import synth_nv12
 
 pytestmark = pytest.mark.gpu
@@ -37,9 +37,7 @@ def test_crc_per_output(oracle, tmp_path, kind, dst, fourcc, planes, norm, borde
     w, h, pitch = GEO
     y, uv = synth_nv12(w, h, seed=1400 + dst[0], pitch=pitch)
     src = tmp_path / "in.nv12"
-    with open(src, "wb") as f:
-        f.write(y.tobytes())
-        f.write(uv.tobytes())
+    write_nv12(src, y, uv)
     ms = [W.scale_only(w, h, *dst)] if kind == "scale_only" else rotated(dst)
     args = [EXE]
     if dtype is not None:
@@ -48,9 +46,8 @@ def test_crc_per_output(oracle, tmp_path, kind, dst, fourcc, planes, norm, borde
     args += [*dst, fourcc, planes, int(norm), *border, src, w, h, pitch]
     for m in ms:
         args += [float(np.float32(v)).hex() for v in m]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=300)
-    lines = [ln.split() for ln in r.stdout.splitlines() if ln and ln[0].isdigit()]
-    assert len(lines) == len(ms), (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    rc, lines, tails = run_check(args)
+    assert len(lines) == len(ms), (rc, *tails)
     for (idx, crc, nbytes), m in zip(lines, ms):
         ref = W.expected(oracle, y, uv, w, h, m, dst, fourcc, planes, norm, None if border[0] < 0 else border)
         if dtype is not None:
@@ -58,4 +55,4 @@ def test_crc_per_output(oracle, tmp_path, kind, dst, fourcc, planes, norm, borde
         assert int(nbytes) == ref.size
         assert int(crc) == zlib.crc32(ref.tobytes()), f"output {idx} m={m} -> {dst}"
     # (after the outputs the program asks for a matrix of a frame it did not give: refused with VREADER_ERROR; exit code 0 = all of it held)
-    assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
+    assert rc == 0, (rc, *tails)

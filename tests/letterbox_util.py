@@ -8,6 +8,12 @@ PLANAR, MERGED = 0, 1
 
 FLAVOURS = [(fcc, planes, norm) for fcc in (RGB24, BGR24) for planes in (PLANAR, MERGED) for norm in (False, True)] + [(Y800, MERGED, False), (Y800, MERGED, True)]
 
+# the frames of the letterbox GPU tests, (width, height, pitch): pad above and below; pad left and right (in 64 x 64: 36 x 64 at left 14, the rectangle's edge
+# splits 4-column thread tiles); no pad in 64 x 64 (the plain colour conversion); an up-scale; a frame a tile's footprint of which is several times the tile
+GEO = [(128, 72, 192), (72, 128, 96), (64, 64, 80), (32, 18, 48), (322, 182, 384)]
+# ... and their canvases.  70 x 66: 4 k + 2 columns (the shifted tile column); 30 x 34: narrower than a tile (element-wise stores)
+CANVASES = [(64, 64), (96, 64), (70, 66), (30, 34)]
+
 
 def default_rect(in_w, in_h, dst_w, dst_h):
     """(left, top, width, height): the rule of include/tsvpp.h, in Python's unbounded integers"""

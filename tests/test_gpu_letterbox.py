@@ -9,18 +9,14 @@ import numpy as np
 import pytest
 import torch
 
-from letterbox_util import BGR24, BICUBIC, BILINEAR, FLAVOURS, MERGED, NEAREST, PLANAR, RGB24, Y800, AREA, bits, default_rect, expected_canvas
+from guard_util import arena
+from letterbox_util import BGR24, BICUBIC, BILINEAR, CANVASES, FLAVOURS, GEO, MERGED, NEAREST, PLANAR, RGB24, Y800, AREA, bits, default_rect, expected_canvas
 from util import frame_k, knob_run, synth_nv12
 
 pytestmark = pytest.mark.gpu
 
 LIMIT = 32  # TSVPP_MAX_LETTERBOX
 GRAY = (114, 128, 128)
-# (width, height, pitch): pad above and below; pad left and right (in 64 x 64: 36 x 64 at left 14, the rectangle's edge splits 4-column thread tiles); no pad in
-# 64 x 64 (the plain colour conversion); an up-scale; a frame a tile's footprint of which is several times the tile
-GEO = [(128, 72, 192), (72, 128, 96), (64, 64, 80), (32, 18, 48), (322, 182, 384)]
-# 70 x 66: 4 k + 2 columns (the shifted tile column); 30 x 34: narrower than a tile (element-wise stores)
-CANVASES = [(64, 64), (96, 64), (70, 66), (30, 34)]
 
 
 def params(ts, canvas, rt, fcc, planes, norm):
@@ -90,9 +86,6 @@ def test_mixed_batch_and_splitting_over_launches(vpp, oracle, frames, n):
     check(vpp, oracle, h, d, geo, (70, 66), BICUBIC, RGB24, MERGED, False, only=only, what=f"n={n}")
 
 
-GUARD = 256
-
-
 @pytest.mark.parametrize("canvas", [(64, 64), (70, 66), (30, 34)])
 @pytest.mark.parametrize("rt,fcc,planes,norm,off", [(BILINEAR, BGR24, PLANAR, True, 0), (BILINEAR, BGR24, PLANAR, True, 4), (BICUBIC, RGB24, MERGED, True, 4),
                                                     (BICUBIC, RGB24, MERGED, False, 0), (BICUBIC, RGB24, MERGED, False, 1), (NEAREST, BGR24, PLANAR, False, 1),
@@ -103,27 +96,10 @@ def test_unaligned_outputs_and_guard_bytes(vpp, oracle, frames, rt, fcc, planes,
     host, dev = frames
     n = len(GEO)
     nbytes = (1 if fcc == Y800 else 3) * canvas[0] * canvas[1] * (4 if norm else 1)
-    stride = ((GUARD + off + nbytes + 15) // 16 * 16 + GUARD + 255) // 256 * 256
-    total = n * stride + GUARD
-    tile = (torch.arange(4096, device="cuda", dtype=torch.int32) * 131 + 17).remainder(251).to(torch.uint8)
-    pat = tile.repeat((total + 4095) // 4096)[:total]
-    buf = pat.clone()
-    assert buf.data_ptr() % 16 == 0
-    starts = [k * stride + GUARD + off for k in range(n)]
-    slots = []
-    for s in starts:
-        buf[s:s + nbytes] = 0xA5
-        slots.append(buf[s:s + nbytes])
-        assert slots[-1].data_ptr() % 16 == off
+    _, slots, verify = arena([nbytes] * n, off, what="canvas", where=f"canvas {canvas}")
     out = [s.view(torch.float32) if norm else s for s in slots]
     check(vpp, oracle, host, dev, GEO, canvas, rt, fcc, planes, norm, out=out, what=f"offset {off}")
-    want = buf.clone()
-    for s in starts:
-        want[s:s + nbytes] = pat[s:s + nbytes]
-    if not torch.equal(want, pat):
-        bad = torch.nonzero(want != pat).flatten()[0].item()
-        k = min(bad // stride, n - 1)
-        raise AssertionError(f"guard byte damaged at {bad - starts[k]} relative to canvas {k} of {nbytes} bytes (offset {off}, canvas {canvas})")
+    verify()
     if not knob_run():
         d = ts.describe_letterbox(params(ts, canvas, rt, fcc, planes, norm), GEO, aligned_outputs=(off == 0))
         # element-wise stores: canvases off the 16-byte alignment, and widths 4 k + 2 narrower than a tile (no tile column to shift)

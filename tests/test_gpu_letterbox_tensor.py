@@ -9,8 +9,7 @@ import pytest
 import torch
 
 import tensor_util as T
-from letterbox_util import BGR24, BICUBIC, BILINEAR, MERGED, NEAREST, PLANAR, RGB24, Y800, default_rect, expected_canvas
-from test_gpu_letterbox import CANVASES, GEO
+from letterbox_util import BGR24, BICUBIC, BILINEAR, CANVASES, GEO, MERGED, NEAREST, PLANAR, RGB24, Y800, default_rect, expected_canvas
 from util import frame_k, knob_run, synth_nv12
 
 pytestmark = pytest.mark.gpu

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from guard_util import arena
 from util import knob_run, synth_nv12
 
 pytestmark = pytest.mark.gpu
@@ -163,9 +164,6 @@ def test_frames_of_different_size_and_pitch(vpp, oracle, n_frames):
         check_rois(vpp, oracle, host, dev, boxes, (224, 224), rt, fcc, planes, norm, widths=widths, what=f"{n_frames} frames")
 
 
-GUARD = 256
-
-
 @pytest.mark.parametrize("dst", [(224, 224), (250, 250), (30, 30)])
 @pytest.mark.parametrize("rt,fcc,planes,norm,off", [(BILINEAR, BGR24, PLANAR, True, 0), (BILINEAR, BGR24, PLANAR, True, 4), (BICUBIC, RGB24, MERGED, True, 4),
                                                     (BICUBIC, RGB24, MERGED, False, 0), (BICUBIC, RGB24, MERGED, False, 1), (BILINEAR, RGB24, MERGED, False, 4),
@@ -179,27 +177,10 @@ def test_unaligned_outputs_and_guard_bytes(vpp, oracle, frame, rt, fcc, planes, 
     boxes = [b if len(b) == 4 else b[1:] for b in boxes]
     n = len(boxes)
     nbytes = (1 if fcc == Y800 else 3) * dst[0] * dst[1] * (4 if norm else 1)
-    stride = ((GUARD + off + nbytes + 15) // 16 * 16 + GUARD + 255) // 256 * 256
-    total = n * stride + GUARD
-    tile = (torch.arange(4096, device="cuda", dtype=torch.int32) * 131 + 17).remainder(251).to(torch.uint8)
-    pat = tile.repeat((total + 4095) // 4096)[:total]
-    buf = pat.clone()
-    assert buf.data_ptr() % 16 == 0
-    starts = [k * stride + GUARD + off for k in range(n)]
-    slots = []
-    for s in starts:
-        buf[s:s + nbytes] = 0xA5
-        slots.append(buf[s:s + nbytes])
-        assert slots[-1].data_ptr() % 16 == off
+    _, slots, verify = arena([nbytes] * n, off, what="output", where=f"dst {dst}")
     out = [s.view(torch.float32) if norm else s for s in slots]
     check_rois(vpp, oracle, [host], [dev], boxes, dst, rt, fcc, planes, norm, widths=W, out=out, what=f"offset {off}")
-    want = buf.clone()
-    for s in starts:
-        want[s:s + nbytes] = pat[s:s + nbytes]
-    if not torch.equal(want, pat):
-        bad = torch.nonzero(want != pat).flatten()[0].item()
-        k = min(bad // stride, n - 1)
-        raise AssertionError(f"guard byte damaged at {bad - starts[k]} relative to output {k} of {nbytes} bytes (offset {off}, dst {dst})")
+    verify()
     if not knob_run():
         d = ts.describe_rois(params(ts, dst, rt, fcc, planes, norm), (W, H, PITCH), boxes, aligned_outputs=(off == 0))
         # element-wise stores: outputs off the 16-byte alignment, and widths 4 k + 2 narrower than a tile (no tile column to shift)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from guard_util import arena
 from util import knob_run, synth_nv12
 
 pytestmark = pytest.mark.gpu
@@ -195,9 +196,6 @@ def test_frames_of_different_size_and_pitch(vpp, oracle, n_frames):
         check_rois(vpp, oracle, host, dev, boxes, dst, fcc, planes, norm, widths=widths, what=f"{n_frames} frames")
 
 
-GUARD = 256
-
-
 @pytest.mark.parametrize("dst", [(250, 250), (30, 30)])
 @pytest.mark.parametrize("fcc,planes,norm", [(BGR24, PLANAR, True), (RGB24, MERGED, True), (RGB24, MERGED, False), (BGR24, PLANAR, False), (Y800, MERGED, False)])
 @pytest.mark.parametrize("off", [0, 4])
@@ -208,27 +206,10 @@ def test_unaligned_outputs_and_guard_bytes(vpp, oracle, frame, fcc, planes, norm
     boxes = within_the_cap(box_set(*dst), dst)[:8] + within_the_cap(box_set(*dst), dst)[16:20] + [b[1:] for b in seeded_boxes(3, seed=dst[0] + off, frames=[(W, H)])]
     n = len(boxes)
     nbytes = (1 if fcc == Y800 else 3) * dst[0] * dst[1] * (4 if norm else 1)
-    stride = ((GUARD + off + nbytes + 15) // 16 * 16 + GUARD + 255) // 256 * 256
-    total = n * stride + GUARD
-    tile = (torch.arange(4096, device="cuda", dtype=torch.int32) * 131 + 17).remainder(251).to(torch.uint8)
-    pat = tile.repeat((total + 4095) // 4096)[:total]
-    buf = pat.clone()
-    assert buf.data_ptr() % 16 == 0
-    starts = [k * stride + GUARD + off for k in range(n)]
-    slots = []
-    for s in starts:
-        buf[s:s + nbytes] = 0xA5
-        slots.append(buf[s:s + nbytes])
-        assert slots[-1].data_ptr() % 16 == off
+    _, slots, verify = arena([nbytes] * n, off, what="output", where=f"dst {dst}")
     out = [s.view(torch.float32) if norm else s for s in slots]
     check_rois(vpp, oracle, [host], [dev], boxes, dst, fcc, planes, norm, widths=W, out=out, what=f"offset {off}")
-    want = buf.clone()
-    for s in starts:
-        want[s:s + nbytes] = pat[s:s + nbytes]
-    if not torch.equal(want, pat):
-        bad = torch.nonzero(want != pat).flatten()[0].item()
-        k = min(bad // stride, n - 1)
-        raise AssertionError(f"guard byte damaged at {bad - starts[k]} relative to output {k} of {nbytes} bytes (offset {off}, dst {dst})")
+    verify()
     if not knob_run():
         d = ts.describe_rois_area(params(ts, dst, fcc, planes, norm), (W, H, PITCH), boxes, aligned_outputs=(off == 0))
         assert d["kernel"].split(",")[1] == ("vec" if off == 0 and not (dst[0] % 4 != 0 and dst[0] < 32) else "elem")

@@ -9,7 +9,7 @@ import rois_sized_fuzz as Z
 import rois_sized_util as U
 import tensor_util as T
 import tile_fuzz as F
-from test_gpu_tile_fuzz import device_frames, host_frames
+from tile_fuzz import device_frames, host_frames
 
 pytestmark = pytest.mark.gpu
 

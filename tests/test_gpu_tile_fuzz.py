@@ -18,6 +18,7 @@ import tensor_util as T
 import tile_fuzz as F
 import warp_util as W
 from letterbox_util import PLANAR, Y800, default_rect, expected_canvas
+from tile_fuzz import device_frames, host_frames
 from util import knob_run
 
 pytestmark = pytest.mark.gpu
@@ -28,24 +29,6 @@ POISON = 0xA5
 
 def pattern(total):
     return np.tile(_TILE, (total + 4095) // 4096)[:total]
-
-
-def host_frames(call):
-    return [F.planes(fr) for fr in call["frames"]]
-
-
-def device_frames(host, call):
-    """every plane as a slice of a larger flat uint8 tensor: it starts off_y / off_uv bytes past a 16-byte boundary"""
-    dev = []
-    for (flat_y, flat_uv, _, _), fr in zip(host, call["frames"]):
-        pair = []
-        for flat, rows, pitch, off in ((flat_y, fr["h"], fr["pitch_y"], fr["off_y"]), (flat_uv, fr["h"] // 2, fr["pitch_uv"], fr["off_uv"])):
-            t = torch.from_numpy(flat).cuda()
-            assert t.data_ptr() % 16 == 0
-            pair.append(t[off:off + rows * pitch].view(rows, pitch))
-            assert pair[-1].data_ptr() % 16 == off
-        dev.append(tuple(pair))
-    return dev
 
 
 def _tensor_form(call, ref):

@@ -174,7 +174,7 @@ def _warp(rng, frames, dst, stats, k):
 
 def _persp(rng, frames, dst, stats, k):
     """the homography of the frame's corners, each moved by up to 0.3 of the frame size; every fourth quad is shifted half a frame outside, every eighth entry is
-    the affine embedding of a drawn warp matrix; float32 values, as test_gpu_persp.f32 rounds them"""
+    the affine embedding of a drawn warp matrix; float32 values, as coord_paths.f32 rounds them"""
     while True:
         f = int(rng.integers(0, len(frames)))
         w, h = frames[f]["w"], frames[f]["h"]
@@ -268,6 +268,25 @@ def planes(fr):
         flat = rng.integers(0, 256, off + rows * pitch + 16, dtype=np.uint8)
         out.append((flat, flat[off:off + rows * pitch].reshape(rows, pitch)))
     return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def host_frames(call):
+    return [planes(fr) for fr in call["frames"]]
+
+
+def device_frames(host, call):
+    """every plane as a slice of a larger flat uint8 tensor: it starts off_y / off_uv bytes past a 16-byte boundary"""
+    import torch
+    dev = []
+    for (flat_y, flat_uv, _, _), fr in zip(host, call["frames"]):
+        pair = []
+        for flat, rows, pitch, off in ((flat_y, fr["h"], fr["pitch_y"], fr["off_y"]), (flat_uv, fr["h"] // 2, fr["pitch_uv"], fr["off_uv"])):
+            t = torch.from_numpy(flat).cuda()
+            assert t.data_ptr() % 16 == 0
+            pair.append(t[off:off + rows * pitch].view(rows, pitch))
+            assert pair[-1].data_ptr() % 16 == off
+        dev.append(tuple(pair))
+    return dev
 
 
 def geometry(call):

@@ -271,8 +271,8 @@ int tsvpp_roi_area_rows(float scale, int first, int n, float *out, int max_float
  *                     resize returns for a frame of that constant.  The pad is given in YUV because it then runs through the one colour back end the library has,
  *                     in every flavour (uint8 and fp32, planar and merged, swapped channels, Y800 -- which keeps pad_y alone --, the TSVPP_OPT_COLOR_G_TERM
  *                     variants), and needs no store code of its own.
- * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  Not: AREA (its down-scale needs weight rows), NV12 / UYVY / YUV444 /
- * HSV outputs, crops, frames out of a tsvpp_table, an RGB pad colour.
+ * Supported: NEAREST, BILINEAR, BICUBIC; RGB24 / BGR24 planar and merged, Y800; uint8 and fp32.  Not: AREA (its down-scale needs weight rows: a call of its own,
+ * tsvpp_convert_letterbox_area below, generates them), NV12 / UYVY / YUV444 / HSV outputs, crops, frames out of a tsvpp_table, an RGB pad colour.
  * `in`, `rects`, `outs` are HOST arrays and may be freed on return: the per-frame records (planes, pitches, size, ratios, rectangle, canvas pointer: 64 bytes)
  * travel BY VALUE in the kernarg segment of their launch -- no allocation, no copy, no host synchronisation, nothing cached in the context, no replay cache --
  * which is what bounds a launch to TSVPP_MAX_LETTERBOX frames.  The call is therefore legal while `stream` is being captured into a hipGraph.  Always an ordinary
@@ -344,6 +344,47 @@ int tsvpp_convert_letterbox_tensor(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, 
                                    int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
 int tsvpp_describe_letterbox_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
                                     int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- letterbox with AREA (not in the reference) ------------------------------------------------------------------------------------------------------------------
+ * The letterbox call with the one filter a down-scale to a detector input should use.  1920 x 1080 into a 640 x 640 canvas is the exact ratio 3: every BILINEAR
+ * weight is zero there and tsvpp_convert_letterbox point-samples one source pixel in nine (4K -> 640 is ratio 6, 720p -> 640 x 360 ratio 2).  Without this call
+ * the answer is tsvpp_convert(AREA) into a temporary, a fill and a strided copy -- and the first tsvpp_convert of a scale allocates and synchronously copies a
+ * device weight table, so that call cannot be captured.
+ * One pair of entry points for both output families:
+ *   spec == NULL  outputs and rules of tsvpp_convert_letterbox: uint8 / fp32, RGB24 / BGR24 planar and merged, Y800;
+ *   spec != NULL  outputs and rules of tsvpp_convert_letterbox_tensor, word for word: planar and Y800 only, fp16 / bf16 / fp32 elements, outputs aligned to the
+ *                 element, the pad through the same expression as every sample.
+ * The differences to those calls:
+ *   resize type   p->resize_type must be TSVPP_AREA; anything else is TSVPP_UNSUPPORTED (and the two existing pairs keep answering TSVPP_UNSUPPORTED for AREA).
+ *   contract      the inner rectangle of canvas k is, bit for bit and in every flavour, what tsvpp_convert returns for frame k with dst = the rectangle's size and
+ *                 TSVPP_AREA.  Per frame as Convert decides per request (reference src/Resize.cu:435): xr > 1 AND yr > 1 runs the weighted box of the down-scale,
+ *                 any other frame the AREA up-scale rule (the 2 x 2 blend).  One launch may mix both.  The pad is tsvpp_convert_letterbox's.
+ *   no tables     the kernel generates the weight rows a tile reads inside the tile, as tsvpp_convert_rois_area's does: no allocation, no copy, no host
+ *                 synchronisation, nothing cached in the context, records by value in the kernarg segment -- legal under stream capture, the first call of a
+ *                 scale included.  TSVPP_MAX_LETTERBOX frames per launch.
+ *   limits        tsvpp_convert_rois_area's, with the rectangle as the output: TSVPP_UNSUPPORTED for a down-scale frame that needs more than 40 taps on an axis
+ *                 (taps = ceil(ratio)) and for a rectangle side above 65536.  Deviation as there: a ratio whose weight pattern never closes is answered with the
+ *                 generator's rows, where tsvpp_convert refuses it.
+ *   cost          tsvpp_convert_rois_area's tile waits for one lane to run the generator over every output index in front of it.  The generator returns to its
+ *                 initial state wherever its closing test passes -- periodically, every P indices -- so this kernel starts each chain at the last multiple of P in
+ *                 front of its tile and runs first % P steps instead of `first`; a wave finds P by testing 64 candidates per round (csrc/vpp_letterbox_area.h).
+ *                 1920 -> 640, 1080 -> 360, 3840 -> 640, 1280 -> 640: P = 1, no steps in front of any tile.  1920 -> 608: P = 57.  1366 -> 640: P = 320, up to
+ *                 304 steps (the chroma chain in front of column 608, which starts at 0).  A pattern that does not close in front of a tile costs that tile what it costs in tsvpp_convert_rois_area; the rows are the same
+ *                 either way.  The host neither searches periods nor plans tiles when converting.
+ * Status, decided before any device is touched (the describe call returns the same one): tsvpp_convert_letterbox's, in its order; then the limits above; then,
+ * with a spec, rules 2 and 3 of the tensor entry points.
+ * tsvpp_describe_letterbox_area prints tsvpp_describe_letterbox's keys (mode=area, kernel=vpp_letterbox_area<...> / vpp_letterbox_area_tensor<...>; lds= includes
+ * the weight rows) and then "inner=WxH+left+top down=<frames on the down-scale path> taps=<largest taps_x>x<largest taps_y> chain=<steps>": the most generator
+ * steps any chain of any tile of the FIRST launch runs in front of its tile's first row (0 for 1920 x 1080 into 640 x 640).  chain= is worked out on the host, in
+ * this call only. */
+int tsvpp_convert_letterbox_area(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */,
+                                 const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
+int tsvpp_describe_letterbox_area(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
+                                  int aligned_outputs, char *buf, size_t buf_len);
+/* DEBUG ONLY (tests), host only: tsvpp_roi_area_rows as tsvpp_convert_letterbox_area's kernel produces the rows -- the generator begun at the jump start of
+ * (scale, first), the largest multiple of the pattern's period that is <= first (0 where the pattern does not close in 1 .. first), which *start receives.
+ * Arguments, result and statuses as tsvpp_roi_area_rows. */
+int tsvpp_letterbox_area_rows(float scale, int first, int n, float *out, int max_floats, int *taps, int *start);
 
 /* ---- regions of interest, each to its own output size (not in the reference) -----------------------------------------------------------------------------------
  * tsvpp_convert_rois with the output size taken PER BOX: text lines that go to one height and a width of their own, the levels of a pyramid or preview ladder,

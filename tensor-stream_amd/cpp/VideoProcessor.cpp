@@ -253,6 +253,20 @@ int VideoProcessor::ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_
                         });
 }
 
+// options.resize.type must be AREA; `spec` may be null (the library's flavours)
+int VideoProcessor::ConvertLetterboxArea(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
+                                         FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, n, true, deviceOuts, options, consumerName, "ConvertLetterboxArea",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_letterbox_area(ctx, n, frames, p, spec, rects, padY, padU, padV, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertLetterboxArea(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
+                                         FrameParameters &options, std::string consumerName) {
+    return ConvertLetterboxArea(inputs, n, rects, padY, padU, padV, deviceOuts, options, nullptr, consumerName);
+}
+
 int VideoProcessor::ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
                                 FrameParameters &options, std::string consumerName) {
     return convertTiles(ctx, isClosed, inputs, nInputs, warps && nWarps > 0, deviceOuts, options, consumerName, "ConvertWarp",

@@ -136,6 +136,14 @@ public:
                     const tsvpp_tensor_spec *spec, std::string consumerName);
     int ConvertLetterbox(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                          const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertLetterbox for options.resize.type == AREA (tsvpp_convert_letterbox_area, include/tsvpp.h): every frame with both ratios above 1 is averaged with the AREA
+    // down-scale, any other takes AREA's up-scale rule; the rectangle holds what ConvertInto returns for the rectangle's size with AREA, bit for bit; no weight
+    // table is built or cached, so the first call of a scale is as capturable as any other.  ConvertLetterbox refuses AREA and this refuses everything else.
+    // Plain, and with a tensor spec (null: the plain call).
+    int ConvertLetterboxArea(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                             std::string consumerName);
+    int ConvertLetterboxArea(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                             const tsvpp_tensor_spec *spec, std::string consumerName);
     // Boxes that each go to their OWN output size (tsvpp_convert_rois_sized, include/tsvpp.h; not in the reference): text lines of one height and their own widths,
     // the levels of a pyramid, the inputs of several heads behind one detector pass.  rois[i] carries the box and its dst_width x dst_height; deviceOuts[i] holds
     // tsvpp_rois_sized_bytes bytes.  options.resize.width and height must be 0 (the sizes are the boxes') and options.crop empty; options.resize.type is NEAREST,

@@ -8,6 +8,7 @@
 //   tsvpp_rois.cpp   regions of interest (both entry points: NEAREST / BILINEAR / BICUBIC and AREA)
 //   tsvpp_rois_sized.cpp regions of interest, each to its own output size (a skeleton of its own: the boxes of a call are split by store class)
 //   tsvpp_letterbox.cpp  aspect-preserving resize into a padded canvas
+//   tsvpp_letterbox_area.cpp  the same with AREA: weight rows generated per tile, from a jump start
 //   tsvpp_warp.cpp   affine warps        } the coordinate paths: one path with a different source coordinate.  Each file holds its record's geometry, its
 //   tsvpp_persp.cpp  homographies        } footprint function or LDS hint, its labels, its entry points and its host-only helpers; the request skeleton they
 //   tsvpp_remap.cpp  coordinate maps     } share is coord_plan (tsvpp_plan.cpp)
@@ -276,6 +277,8 @@ int rois_sized_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frame
 // (tsvpp_convert_letterbox / tsvpp_describe_letterbox; RoiPlan: the canvas is its dst_w x dst_h).  letterbox_rect_of: frame k's rectangle, the caller's or the default
 int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);
 tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int k, int dst_w, int dst_h);
+// (tsvpp_convert_letterbox_area / tsvpp_describe_letterbox_area; RoiPlan: mode is M_AREA_DOWN -- every frame chooses its rule --, down / taps_x / taps_y as rois_plan's)
+int letterbox_area_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);
 // (tsvpp_convert_warp / tsvpp_describe_warp; RoiPlan: mode is M_BILINEAR).  The border is (-1, -1, -1), replicate, or three components 0..255
 int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl);
 // (tsvpp_convert_perspective / tsvpp_describe_perspective) warp_plan's rules in warp_plan's order, then the horizon rule (include/tsvpp.h)

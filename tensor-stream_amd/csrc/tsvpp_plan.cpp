@@ -339,7 +339,9 @@ tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int 
     return r;
 }
 
-int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl) {
+// The request rules of both letterbox calls, in the one order that decides which status a request with two faults gets; `area`: which of them is asked (each
+// answers TSVPP_UNSUPPORTED to the other's resize types)
+static int letterbox_request(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, bool area, RoiPlan &pl) {
     // TSVPP_ERROR: arguments that describe no request at all
     if (!p || !in || n <= 0) return TSVPP_ERROR;
     if (tile_request_error(p, n, in) != TSVPP_OK) return TSVPP_ERROR;
@@ -354,9 +356,32 @@ int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsv
     for (int f = 0; rects && f < n; f++) // (the default rectangle of an even canvas is even)
         if ((rects[f].left | rects[f].top | rects[f].width | rects[f].height) & 1) return TSVPP_UNSUPPORTED;
     if (tile_frame_spans(n, in) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    // AREA: its down-scale needs weight rows (vpp_rois_area.hip generates them per tile); not in this kernel yet.  The rectangle travels in 32-bit fields: a canvas
-    // side has no limit of its own, the grid has
-    return tile_output_plan(p, false, TSVPP_MAX_LETTERBOX, pl);
+    // AREA: its down-scale needs weight rows, which a kernel of its own generates per tile (vpp_letterbox_area.hip, tsvpp_convert_letterbox_area).  The rectangle
+    // travels in 32-bit fields: a canvas side has no limit of its own, the grid has
+    return tile_output_plan(p, area, TSVPP_MAX_LETTERBOX, pl);
+}
+
+int letterbox_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl) {
+    return letterbox_request(p, n, in, rects, pad_y, pad_u, pad_v, false, pl);
+}
+
+// tsvpp_convert_letterbox_area: the letterbox call's rules, then tsvpp_convert_rois_area's limits with the rectangle as the output -- the generator never runs
+// further than a rectangle is wide / high, and a down-scale frame's weight rows must fit the tile's LDS
+int letterbox_area_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl) {
+    const int sts = letterbox_request(p, n, in, rects, pad_y, pad_u, pad_v, true, pl);
+    if (sts != TSVPP_OK) return sts;
+    for (int f = 0; f < n; f++) {
+        const tsvpp_rect rc = letterbox_rect_of(in, rects, f, pl.dst_w, pl.dst_h);
+        if (rc.width > ROI_AREA_MAX_DST || rc.height > ROI_AREA_MAX_DST) return TSVPP_UNSUPPORTED;
+        const float xr = (float)in[f].width / (float)rc.width, yr = (float)in[f].height / (float)rc.height;
+        if (roi_area_mode(xr, yr) != M_AREA_DOWN) continue;
+        const int tx = roi_area_taps(xr), ty = roi_area_taps(yr);
+        if (tx > ROI_AREA_MAX_TAPS || ty > ROI_AREA_MAX_TAPS) return TSVPP_UNSUPPORTED;
+        pl.down++;
+        pl.taps_x = tx > pl.taps_x ? tx : pl.taps_x;
+        pl.taps_y = ty > pl.taps_y ? ty : pl.taps_y;
+    }
+    return TSVPP_OK;
 }
 
 // The border of the coordinate paths: (-1, -1, -1) replicates the frame's edge, anything else is a sample, each value 0..255

@@ -100,6 +100,7 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_debug_last_launch", "tsvpp_convert_rois", "tsvpp_describe_rois", "tsvpp_convert_rois_area", "tsvpp_describe_rois_area", "tsvpp_roi_area_rows", "tsvpp_debug_area_tables",
            "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox",
            "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor",
+           "tsvpp_convert_letterbox_area", "tsvpp_describe_letterbox_area", "tsvpp_letterbox_area_rows",
            "tsvpp_rois_sized_bytes", "tsvpp_convert_rois_sized", "tsvpp_describe_rois_sized", "tsvpp_convert_rois_sized_tensor", "tsvpp_describe_rois_sized_tensor",
            "tsvpp_rois_sized_tile",
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
@@ -187,6 +188,12 @@ def lib():
     L.tsvpp_convert_letterbox_tensor.restype = i32
     L.tsvpp_describe_letterbox_tensor.argtypes = [pp, ps, i32, pn, pc, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_describe_letterbox_tensor.restype = i32
+    L.tsvpp_convert_letterbox_area.argtypes = [vp, i32, pn, pp, ps, pc, i32, i32, i32, ctypes.POINTER(vp), vp]  # (spec may be None)
+    L.tsvpp_convert_letterbox_area.restype = i32
+    L.tsvpp_describe_letterbox_area.argtypes = [pp, ps, i32, pn, pc, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_letterbox_area.restype = i32
+    L.tsvpp_letterbox_area_rows.argtypes = [ctypes.c_float, i32, i32, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.tsvpp_letterbox_area_rows.restype = i32
     pz = ctypes.POINTER(RoiSized)
     L.tsvpp_rois_sized_bytes.argtypes = [pp, ps, i32, i32]
     L.tsvpp_rois_sized_bytes.restype = ctypes.c_size_t

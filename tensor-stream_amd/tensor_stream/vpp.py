@@ -350,7 +350,17 @@ class VideoProcessor:
         on torch's current stream; `rects` is the list of (left, top, width, height) that was used, to map detections back.
         dtype / mean / std (see tensor_spec): with any of them given the canvases come out as what a network takes (tsvpp_convert_letterbox_tensor), the pad
         included: it goes through (x / 255 - mean[c]) * (1 / std[c]) like every sample."""
-        spec = tensor_spec(dtype, mean, std)
+        return self._convert_letterbox(False, ys, uvs, params, pad, rects, out, width, height, tensor_spec(dtype, mean, std))
+
+    def convert_letterbox_area(self, ys, uvs, params, pad=(114, 128, 128), rects=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_letterbox for ResizeType.AREA (tsvpp_convert_letterbox_area), same arguments and result (out, rects): every frame with both ratios above 1 is
+        averaged with the AREA down-scale -- the filter a 1080p or 4K frame into a 640 x 640 canvas should get, where BILINEAR point-samples --, any other frame
+        takes AREA's up-scale rule.  The inner rectangle equals Convert(AREA) to the rectangle's size bit for bit; the weight rows are generated inside the kernel,
+        so the call allocates and caches nothing and can be captured into a graph the first time it sees a scale.  Any other resize type is refused.
+        dtype / mean / std: as convert_letterbox (the same entry point with a tensor spec)."""
+        return self._convert_letterbox(True, ys, uvs, params, pad, rects, out, width, height, tensor_spec(dtype, mean, std))
+
+    def _convert_letterbox(self, area, ys, uvs, params, pad, rects, out, width, height, spec):
         p = params.parameters if isinstance(params, FrameParameters) else params
         n = len(ys)
         if n == 0:
@@ -362,7 +372,10 @@ class VideoProcessor:
         recs = None if rects is None else _rects(rects, n)
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if spec is None:
+        if area:
+            N.check(self._lib.tsvpp_convert_letterbox_area(self._ctx, n, frames, ctypes.byref(p), None if spec is None else ctypes.byref(spec), recs, int(pad[0]),
+                                                           int(pad[1]), int(pad[2]), outs, stream))
+        elif spec is None:
             N.check(self._lib.tsvpp_convert_letterbox(self._ctx, n, frames, ctypes.byref(p), recs, int(pad[0]), int(pad[1]), int(pad[2]), outs, stream))
         else:
             N.check(self._lib.tsvpp_convert_letterbox_tensor(self._ctx, n, frames, ctypes.byref(p), ctypes.byref(spec), recs, int(pad[0]), int(pad[1]), int(pad[2]),
@@ -711,6 +724,21 @@ def describe_letterbox(params, frames, rects=None, aligned_outputs=True, dtype=N
         N.check(N.lib().tsvpp_describe_letterbox(ctypes.byref(p), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
     else:
         N.check(N.lib().tsvpp_describe_letterbox_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def describe_letterbox_area(params, frames, rects=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_letterbox_area of this request would launch, as a dict (tsvpp_describe_letterbox_area: describe_letterbox's keys, then down = frames on the
+    down-scale path, taps = "XxY" and chain = the most generator steps a chain of the first launch runs in front of its tile) -- host logic only, works without
+    a GPU.  Arguments as describe_letterbox."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = _geometry_records(frames)
+    fr = (N.NV12 * max(len(recs), 1))(*recs)
+    rc = None if rects is None else _rects(rects, len(recs))
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    N.check(N.lib().tsvpp_describe_letterbox_area(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf,
+                                                  len(buf)))
     return _parse_selection(buf.value.decode())
 
 

@@ -67,6 +67,15 @@ def cases():
     return generate()
 
 
+def host_frames(case):
+    """[(y, uv)] of the case: seeded random planes at the frame's pitch -- or, where a test has set case["content"], that class of tests/edge_content.py"""
+    if case.get("content"):
+        import edge_content
+        return [edge_content.frame(case["content"], w, h, p, p) for w, h, p in case["frames"]]
+    from util import synth_nv12
+    return [synth_nv12(w, h, seed=case["seed"] + 100 * case["index"] + k, pitch=p) for k, (w, h, p) in enumerate(case["frames"])]
+
+
 def rects_of(case):
     return case["rects"] if case["rects"] is not None else [default_rect(f[0], f[1], *case["canvas"]) for f in case["frames"]]
 

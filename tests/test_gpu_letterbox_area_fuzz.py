@@ -7,7 +7,6 @@ import pytest
 import letterbox_area_fuzz as Z
 import tensor_util as T
 from letterbox_util import AREA, PLANAR, Y800, bits, expected_canvas
-from util import synth_nv12
 
 CASES = Z.cases()
 
@@ -44,14 +43,13 @@ def test_describe_accepts_every_case(index):
     assert d["kernel"].startswith("vpp_letterbox_area_tensor<" if case["tensor"] else "vpp_letterbox_area<")
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("index", range(Z.CASES))
-def test_case_against_the_oracle(vpp, oracle, index):
+def run_case(vpp, oracle, case):
+    """one case (tests/test_gpu_edge_content.py: the same case with its frames' content replaced) against the oracle, the bytes between the canvases included"""
     import torch
     import tensor_stream as ts
-    case = CASES[index]
+    index = case["index"]
     canvas, (fcc, planes, norm) = case["canvas"], case["flavour"]
-    host = [synth_nv12(w, h, seed=case["seed"] + 100 * index + k, pitch=p) for k, (w, h, p) in enumerate(case["frames"])]
+    host = Z.host_frames(case)
     dev = [(torch.from_numpy(y).cuda(), torch.from_numpy(uv).cuda()) for y, uv in host]
     n, c = len(host), (1 if fcc == Y800 else 3)
     esz = T.ESIZE[case["tensor"][0]] if case["tensor"] else (4 if norm else 1)
@@ -76,9 +74,16 @@ def test_case_against_the_oracle(vpp, oracle, index):
             ref = expected_canvas(oracle, y, uv, w, h, rects[k], canvas, AREA, fcc, planes, norm, case["pad"])
             g = bits(got[k])
         bad = np.flatnonzero(g != ref) if g.size == ref.size else np.array([-1])
-        assert bad.size == 0, f"case {index} frame {k} {case['frames'][k]} rect {rects[k]} canvas {canvas} {case['flavour']} {case['tensor']}: {bad.size} bytes differ, first at {bad[:4]}"
+        assert bad.size == 0, f"case {index} content {case.get('content')} frame {k} {case['frames'][k]} rect {rects[k]} canvas {canvas} {case['flavour']} {case['tensor']}: {bad.size} bytes differ, first at {bad[:4]}"
     # the bytes between the canvases stay as they were
     keep = torch.ones_like(buf, dtype=torch.bool)
     for k in range(n):
         keep[k * stride + off:k * stride + off + nbytes] = False
     assert bool((buf[keep] == 0xA5).all()), f"case {index}: bytes outside the canvases were written"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("index", range(Z.CASES))
+def test_case_against_the_oracle(vpp, oracle, index):
+    assert CASES[index]["index"] == index
+    run_case(vpp, oracle, CASES[index])

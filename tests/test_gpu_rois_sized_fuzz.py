@@ -16,27 +16,32 @@ pytestmark = pytest.mark.gpu
 _ran = []
 
 
+def run_call(vpp, oracle, call):
+    """one drawn call (tests/test_gpu_edge_content.py: the same call with its frames' content replaced) against the oracle, guards included"""
+    import tensor_stream as ts
+    host = host_frames(call)
+    dev = device_frames(host, call)
+    planes_host = [(h[2], h[3]) for h in host]
+    fcc, planes, norm = call["flavour"]
+    what = f"seed {call['seed']} call {call['index']}: request {call}"
+    refs = []
+    for b, s in zip(call["items"], call["sizes"]):
+        ref = U.expect(oracle, planes_host, b, s, call["rt"], fcc, planes, norm)
+        if call["tensor"] is not None:
+            ref = T.expected(ref.view(np.float32), U.channels(fcc), T.SPECS[call["tensor"][1]], call["tensor"][0])
+        refs.append(ref)
+    kw = F.tensor_kwargs(call)
+    dtype = kw.get("dtype")
+    outs = U.run(vpp, dev, call["items"], call["sizes"], U.frame_parameters(ts, call["rt"], fcc, planes, norm), fcc, Z.element_bytes(call), aligned=call["aligned"],
+                 frames=[(fr["w"], fr["h"]) for fr in call["frames"]], dtype=dtype, what=what, **({k: v for k, v in kw.items() if k != "dtype"}))
+    U.compare(outs, refs, call["items"], call["sizes"], what)
+
+
 @pytest.mark.parametrize("chunk", range(Z.CHUNKS))
 def test_calls_match_the_oracle(vpp, oracle, chunk):
-    import tensor_stream as ts
     calls = Z.cases(chunk)
     for call in calls:
-        host = host_frames(call)
-        dev = device_frames(host, call)
-        planes_host = [(h[2], h[3]) for h in host]
-        fcc, planes, norm = call["flavour"]
-        what = f"seed {call['seed']} call {call['index']}: request {call}"
-        refs = []
-        for b, s in zip(call["items"], call["sizes"]):
-            ref = U.expect(oracle, planes_host, b, s, call["rt"], fcc, planes, norm)
-            if call["tensor"] is not None:
-                ref = T.expected(ref.view(np.float32), U.channels(fcc), T.SPECS[call["tensor"][1]], call["tensor"][0])
-            refs.append(ref)
-        kw = F.tensor_kwargs(call)
-        dtype = kw.get("dtype")
-        outs = U.run(vpp, dev, call["items"], call["sizes"], U.frame_parameters(ts, call["rt"], fcc, planes, norm), fcc, Z.element_bytes(call), aligned=call["aligned"],
-                     frames=[(fr["w"], fr["h"]) for fr in call["frames"]], dtype=dtype, what=what, **({k: v for k, v in kw.items() if k != "dtype"}))
-        U.compare(outs, refs, call["items"], call["sizes"], what)
+        run_call(vpp, oracle, call)
         _ran.append((chunk, call["index"]))
     assert len(calls) == Z.CALLS and sum(1 for c, _ in _ran if c == chunk) == Z.CALLS  # every drawn call ran
 

@@ -45,7 +45,7 @@ _expected = {}
 
 def expected(oracle, call, host):
     """the expected bytes of every output of the call, computed once per module"""
-    key = (call["family"], call["seed"], call["index"])
+    key = (call["family"], call["seed"], call["index"], call.get("content"))  # (content: tests/edge_content.py's class, where a test has replaced the frames)
     if key in _expected:
         return _expected[key]
     fcc, planes, norm = call["flavour"]

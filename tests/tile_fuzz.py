@@ -261,7 +261,10 @@ def cases(family, chunk):
 
 def planes(fr):
     """the content of a frame: (flat_y, flat_uv, y, uv) -- two flat uint8 buffers (to be placed on a 16-byte boundary) and the planes (rows x pitch) as views of
-    them that start off_y / off_uv bytes in"""
+    them that start off_y / off_uv bytes in.  fr["content"], where a test has set it: a class of tests/edge_content.py in place of the seeded random bytes"""
+    if fr.get("content"):
+        import edge_content
+        return edge_content.planes(fr["content"], fr)
     rng = np.random.default_rng(fr["seed"])
     out = []
     for rows, pitch, off in ((fr["h"], fr["pitch_y"], fr["off_y"]), (fr["h"] // 2, fr["pitch_uv"], fr["off_uv"])):

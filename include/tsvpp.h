@@ -475,8 +475,8 @@ int tsvpp_rois_sized_tile(const tsvpp_params *p, int n_frames, const tsvpp_nv12 
  *                      a null plane or output.
  *   TSVPP_UNSUPPORTED  odd dst_*, an odd frame size, a resize type other than BILINEAR, an output format outside the list, |m[k]| > 2^24 (with that bound every
  *                      coordinate is finite), an output of 4 GiB or more.
- * Out of scope, follow-ups: NEAREST / BICUBIC / AREA warps, a device-resident matrix list, per-warp output sizes, merged half-precision tensors.  Perspective
- * (3 x 3) maps are tsvpp_convert_perspective's (below). */
+ * Out of scope, follow-ups: NEAREST / AREA warps, a device-resident matrix list, per-warp output sizes, merged half-precision tensors.  BICUBIC answers
+ * TSVPP_UNSUPPORTED here: it has an entry point of its own, tsvpp_convert_warp_bicubic (below).  Perspective (3 x 3) maps are tsvpp_convert_perspective's (below). */
 #define TSVPP_MAX_WARPS 32 /* outputs per launch; more are split */
 typedef struct tsvpp_warp {
     int32_t frame; /* index into `frames` */
@@ -505,6 +505,43 @@ int tsvpp_warp_rotated_box(double cx, double cy, double box_w, double box_h, dou
  * even first, odd last) of `warp` on a frame of frame_w x frame_h: out8 = { xlo, xhi, ylo, yhi } in luma pixels, then { cxlo, cxhi, cylo, cyhi } in chroma pairs.
  * TSVPP_ERROR for null arguments, a frame size <= 0, an empty or negative range. */
 int tsvpp_warp_footprint(const tsvpp_warp *warp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
+
+/* ---- BICUBIC affine warps (not in the reference) ---------------------------------------------------------------------------------------------------------------
+ * tsvpp_convert_warp with the library's BICUBIC in place of its BILINEAR: recognition heads are trained on bicubic-aligned crops, and an up-sampled plate or text
+ * line is visibly soft under BILINEAR.  An entry point of its own because tsvpp_convert_warp's answer to BICUBIC (TSVPP_UNSUPPORTED) is part of its contract.  One
+ * pair serves both output families: `spec` == NULL -- outputs and rules are tsvpp_convert_warp's (uint8 and fp32, RGB24 / BGR24 planar and merged, Y800); with a
+ * `spec` they are tsvpp_convert_warp_tensor's, word for word.  tsvpp_warp, TSVPP_MAX_WARPS, the records by value in the kernarg segment, no allocation, no copy,
+ * no host synchronisation, legality under stream capture, TSVPP_OPT_COLOR_G_TERM and the coefficient block: all as tsvpp_convert_warp.
+ *   Coordinate   tsvpp_convert_warp's fx, fy, bit for bit (the two fused multiply-adds; chroma with ctx / cty on the pair grid, never derived from luma).  f is
+ *                clamped into [-1, limit] before it becomes an integer, which changes no result.
+ *   Axis         p = floor(f), w = f - p (exact in fp32); p < 0 -> p = 0, w = 0; p > limit - 1 -> p = limit - 1, w = 0: the library's BICUBIC axis on the warp's
+ *                coordinate.  limit = the frame's width / height; chroma: half of each.
+ *   Taps         the reference's edge rule: p - lo, p, p + hi, p + 2 hi with hi = 0 where p + 1 or p + 2 would leave the plane (BOTH upper taps collapse onto the
+ *                centre), lo = 0 at the low edge, else 1; the same on rows.  Chroma: the rule on pairs with limits w / 2, h / 2, U from byte column 2 x, V from
+ *                2 x + 1 (for an even width this is the resize's rule on byte columns with step 2).
+ *   Sum          the library's BICUBIC: Keys' cubic with a = -0.75, coefficients from (double)w with the exact square and the correctly rounded cube,
+ *                    c0 = (a w - 2a w2) + a w3    c1 = (1 - (a + 3) w2) + (a + 2) w3    c2 = ((-a) w + (2a + 3) w2) - (a + 2) w3    c3 = a w2 - a w3
+ *                four horizontal sums ((c0 p0 + c1 p1) + c2 p2) + c3 p3 in fp64, each rounded half away from zero and clamped to 0..255, then the vertical sum
+ *                of those four integers with the row weights, formed, rounded and clamped the same way.  (The kernel evaluates in fp32 and recomputes in fp64
+ *                within 5e-4 of a tie: the result is the fp64 one.)  The virtual NV12 frame then goes through the one colour back end.
+ *   Border       tsvpp_convert_warp's rule and test: -1, -1, -1 replicates -- the edge rule above is the whole rule; otherwise a sample whose position lies outside
+ *                the frame takes the border component whole, never mixed into the cubic.
+ *   Identities   m = ((float)w / dst_w, 0, 0, 0, (float)h / dst_h, 0) gives tsvpp_convert(BICUBIC, dst) of the whole frame bit for bit (the coordinate reduces to
+ *                fmaf(j + 0.5f, ratio, -0.5f)); a translation by even integers inside the frame is the plain colour conversion of that crop (w = 0: coefficients
+ *                0, 1, 0, 0).
+ * Status: tsvpp_convert_warp's, in its order, with "a resize type other than BICUBIC" (BILINEAR, NEAREST, AREA, unknown: TSVPP_UNSUPPORTED); with a spec, rules 2
+ * and 3 of the tensor block follow.  Out of scope: BICUBIC for tsvpp_convert_remap / tsvpp_convert_mesh, NEAREST / AREA warps, per-output sizes. */
+int tsvpp_convert_warp_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, const tsvpp_params *p,
+                               const tsvpp_tensor_spec *spec /* may be NULL */, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+/* What tsvpp_convert_warp_bicubic WOULD launch: tsvpp_describe_warp's (with a spec: tsvpp_describe_warp_tensor's) line with mode=warp_bicubic and
+ * kernel=vpp_warp_bicubic<...> (vpp_warp_bicubic_tensor<...>); every other key is that call's.  staged = the warps whose every tile stages its box in LDS: the
+ * BILINEAR box with the 4-tap halo.  Host only: needs no context and no GPU. */
+int tsvpp_describe_warp_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_nv12 *frames, int n_warps,
+                                const tsvpp_warp *warps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* DEBUG ONLY (tests), host only: tsvpp_warp_footprint for the BICUBIC call -- [p(min) - 1, p(max) + 2] per axis, clamped into the frame, p() the centre tap (the
+ * floor clamped into 0 .. limit - 1) of the least and the greatest of the tile's corner coordinates: every tap lies in [p - 1, p + 2] and p is monotone in f.
+ * Arguments and statuses as tsvpp_warp_footprint. */
+int tsvpp_warp_bicubic_footprint(const tsvpp_warp *warp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
 
 /* ---- perspective warps (not in the reference) ---------------------------------------------------------------------------------------------------------------
  * What no 2 x 3 matrix rectifies: a licence plate, a document page, a shelf label, a court seen from a broadcast camera, a road surface for a bird's-eye view --
@@ -539,8 +576,8 @@ int tsvpp_warp_footprint(const tsvpp_warp *warp, int frame_w, int frame_h, int j
  * Status, decided before any device is touched (tsvpp_describe_perspective returns the same one), in tsvpp_convert_warp's order:
  *   TSVPP_ERROR        everything tsvpp_convert_warp answers with it, an entry of h that is not finite among them; when converting: a null plane or output.
  *   TSVPP_UNSUPPORTED  everything tsvpp_convert_warp answers with it (|h[k]| > 2^24 for its matrix bound), then the horizon rule above.
- * Out of scope, TSVPP_UNSUPPORTED or follow-ups: NEAREST / BICUBIC / AREA sampling, a device-resident matrix list, per-output sizes, merged half-precision
- * tensors, maps whose horizon crosses the output. */
+ * Out of scope, TSVPP_UNSUPPORTED or follow-ups: NEAREST / AREA sampling, a device-resident matrix list, per-output sizes, merged half-precision tensors, maps
+ * whose horizon crosses the output.  BICUBIC answers TSVPP_UNSUPPORTED here: it has an entry point of its own, tsvpp_convert_perspective_bicubic (below). */
 #define TSVPP_MAX_PERSP 32 /* outputs per launch; more are split */
 typedef struct tsvpp_persp {
     int32_t frame; /* index into `frames` */
@@ -570,6 +607,23 @@ int tsvpp_persp_from_quad(const double quad[8], int dst_w, int dst_h, tsvpp_pers
 /* DEBUG ONLY (tests), host only: tsvpp_warp_footprint for `persp` -- the interval box the kernel and the host compute for a tile.  TSVPP_ERROR as there;
  * TSVPP_UNSUPPORTED where the denominator falls below 2^-64 on either grid of the range (the request rules refuse such an output). */
 int tsvpp_persp_footprint(const tsvpp_persp *persp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
+
+/* ---- BICUBIC perspective warps (not in the reference) ------------------------------------------------------------------------------------------------------------
+ * tsvpp_convert_perspective with the library's BICUBIC: the coordinate is tsvpp_convert_perspective's, bit for bit (two numerators, one denominator, one
+ * reciprocal, two products; chroma with the primed terms on the pair grid); from fx, fy on everything is tsvpp_convert_warp_bicubic's, word for word -- axis,
+ * taps, sum, border.  Hence: h = (m0, m1, m2, m3, m4, m5, 0, 0, 1) gives the bits of tsvpp_convert_warp_bicubic with m, and h and 4 h give the same bits.  `spec`
+ * == NULL: outputs and rules of tsvpp_convert_perspective; with a spec, of tsvpp_convert_perspective_tensor.  tsvpp_persp, TSVPP_MAX_PERSP and everything about
+ * the call are tsvpp_convert_perspective's.  Status: tsvpp_convert_perspective's, in its order (the horizon rule included), with "a resize type other than
+ * BICUBIC"; with a spec, rules 2 and 3 of the tensor block follow. */
+int tsvpp_convert_perspective_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, const tsvpp_params *p,
+                                      const tsvpp_tensor_spec *spec /* may be NULL */, int border_y, int border_u, int border_v, void *const *outs, void *stream);
+/* What tsvpp_convert_perspective_bicubic WOULD launch: tsvpp_describe_perspective's (with a spec: its tensor form's) line with mode=persp_bicubic and
+ * kernel=vpp_persp_bicubic<...> (vpp_persp_bicubic_tensor<...>).  Host only: needs no context and no GPU. */
+int tsvpp_describe_perspective_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_nv12 *frames, int n,
+                                       const tsvpp_persp *persps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len);
+/* DEBUG ONLY (tests), host only: tsvpp_persp_footprint for the BICUBIC call -- the interval box with the 4-tap halo, [p(min) - 1, p(max) + 2] per axis, clamped
+ * into the frame.  Arguments and statuses as tsvpp_persp_footprint. */
+int tsvpp_persp_bicubic_footprint(const tsvpp_persp *persp, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last, int32_t *out8);
 
 /* ---- per-pixel coordinate maps (not in the reference) ----------------------------------------------------------------------------------------------------------
  * What no matrix describes: the lens.  Undistortion of wide-angle, fisheye and action cameras, stereo rectification, undistort and resize in one pass, cylindrical

@@ -299,6 +299,33 @@ int VideoProcessor::ConvertPerspective(AVFrame *const *inputs, int nInputs, cons
                         });
 }
 
+// options.resize.type must be BICUBIC; `spec` may be null (the library's flavours)
+int VideoProcessor::ConvertWarpBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV,
+                                       void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, nInputs, warps && nWarps > 0, deviceOuts, options, consumerName, "ConvertWarpBicubic",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_warp_bicubic(ctx, nInputs, frames, nWarps, warps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertWarpBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV,
+                                       void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
+    return ConvertWarpBicubic(inputs, nInputs, warps, nWarps, borderY, borderU, borderV, deviceOuts, options, nullptr, consumerName);
+}
+
+int VideoProcessor::ConvertPerspectiveBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV,
+                                              void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, nInputs, persps && nPersps > 0, deviceOuts, options, consumerName, "ConvertPerspectiveBicubic",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_perspective_bicubic(ctx, nInputs, frames, nPersps, persps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertPerspectiveBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV,
+                                              void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
+    return ConvertPerspectiveBicubic(inputs, nInputs, persps, nPersps, borderY, borderU, borderV, deviceOuts, options, nullptr, consumerName);
+}
+
 int VideoProcessor::ConvertRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
                                  int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
     return convertTiles(ctx, isClosed, inputs, nInputs, maps && nMaps > 0 && remaps && nRemaps > 0, deviceOuts, options, consumerName, "ConvertRemap",

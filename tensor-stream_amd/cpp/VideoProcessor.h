@@ -168,6 +168,18 @@ public:
                            FrameParameters &options, std::string consumerName);
     int ConvertPerspective(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV, void *const *deviceOuts,
                            FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertWarp and ConvertPerspective sampled with the library's BICUBIC (tsvpp_convert_warp_bicubic, tsvpp_convert_perspective_bicubic, include/tsvpp.h; not in
+    // the reference): the coordinate is the BILINEAR method's bit for bit, the 4 x 4 taps follow the reference's edge rule, the sums are Convert(BICUBIC)'s.
+    // options.resize.type must be BICUBIC (ConvertWarp / ConvertPerspective refuse it, and these refuse everything else); every other argument and the status
+    // convention are the BILINEAR method's.  Plain, and with a tensor spec (null: the plain call).
+    int ConvertWarpBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                           FrameParameters &options, std::string consumerName);
+    int ConvertWarpBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
+                           FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
+    int ConvertPerspectiveBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV,
+                                  void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    int ConvertPerspectiveBicubic(AVFrame *const *inputs, int nInputs, const tsvpp_persp *persps, int nPersps, int borderY, int borderU, int borderV,
+                                  void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
     // Per-pixel coordinate maps -- lens undistortion, rectification, unwraps (tsvpp_convert_remap, include/tsvpp.h; not in the reference): output k samples frame
     // remaps[k].frame BILINEAR where the device-resident map remaps[k].map says, into options' width x height, colour-converted and stored to deviceOuts[k];
     // on the consumer's stream, status convention as ConvertWarp.  options.crop must be empty.  With a tensor spec: tsvpp_convert_remap_tensor.

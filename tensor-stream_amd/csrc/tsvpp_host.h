@@ -280,9 +280,11 @@ tsvpp_rect letterbox_rect_of(const tsvpp_nv12 *in, const tsvpp_rect *rects, int 
 // (tsvpp_convert_letterbox_area / tsvpp_describe_letterbox_area; RoiPlan: mode is M_AREA_DOWN -- every frame chooses its rule --, down / taps_x / taps_y as rois_plan's)
 int letterbox_area_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, RoiPlan &pl);
 // (tsvpp_convert_warp / tsvpp_describe_warp; RoiPlan: mode is M_BILINEAR).  The border is (-1, -1, -1), replicate, or three components 0..255
-int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl);
+int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl,
+              Mode filter = M_BILINEAR); // (filter: the one resize type the entry point samples with -- M_BICUBIC for tsvpp_convert_warp_bicubic)
 // (tsvpp_convert_perspective / tsvpp_describe_perspective) warp_plan's rules in warp_plan's order, then the horizon rule (include/tsvpp.h)
-int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, int border_y, int border_u, int border_v, RoiPlan &pl);
+int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, int border_y, int border_u, int border_v, RoiPlan &pl,
+               Mode filter = M_BILINEAR);
 // (tsvpp_convert_remap / tsvpp_describe_remap) warp_plan's rules in warp_plan's order without the matrix rules, with the maps' (include/tsvpp.h); `xy` is not read
 int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y,
                int border_u, int border_v, RoiPlan &pl);

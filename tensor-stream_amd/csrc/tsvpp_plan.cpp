@@ -393,10 +393,10 @@ static bool coord_border_ok(int border_y, int border_u, int border_v) {
 // The request skeleton of the four coordinate paths (warp_plan, persp_plan, remap_plan, mesh_plan), once: the rules they share, in the one order that decides
 // which status a request with two faults gets.  A path passes what it alone knows: `given` -- its own arrays are there and not empty; index_ok(i) -- item i names
 // a frame (and a map, a mesh) of the request; path_error() / path_unsupported() -- whether one of its own TSVPP_ERROR / TSVPP_UNSUPPORTED rules is broken.
-// `limit` = outputs per launch
+// `limit` = outputs per launch; `filter` = the one resize type the entry point samples with (M_BILINEAR, or M_BICUBIC for the *_bicubic calls)
 template <class INDEX, class ERR, class UNS>
-int coord_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, bool given, int n, int border_y, int border_u, int border_v, int limit, RoiPlan &pl,
-               INDEX index_ok, ERR path_error, UNS path_unsupported) {
+int coord_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, bool given, int n, int border_y, int border_u, int border_v, int limit, Mode filter,
+               RoiPlan &pl, INDEX index_ok, ERR path_error, UNS path_unsupported) {
     // TSVPP_ERROR: arguments that describe no request at all
     if (!p || !frames || n_frames <= 0 || !given || n <= 0) return TSVPP_ERROR;
     if (tile_request_error(p, n_frames, frames) != TSVPP_OK) return TSVPP_ERROR;
@@ -407,15 +407,15 @@ int coord_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, bo
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    // NEAREST, BICUBIC and AREA through a coordinate: follow-ups
-    if (tile_output_plan(p, false, limit, pl) != TSVPP_OK || pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED;
+    // every other resize type belongs to another entry point (BICUBIC warps: tsvpp_convert_warp_bicubic) or is a follow-up (NEAREST, AREA)
+    if (tile_output_plan(p, false, limit, pl) != TSVPP_OK || pl.mode != filter) return TSVPP_UNSUPPORTED;
     return path_unsupported() ? TSVPP_UNSUPPORTED : TSVPP_OK;
 }
 
 // ... of the matrix paths: REC is tsvpp_warp (K = 6 entries) or tsvpp_persp (K = 9).  `any` = some entry of some matrix satisfies the predicate
 template <class REC, int K>
 int matrix_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const REC *recs, float (REC::*entries)[K], int border_y, int border_u,
-                int border_v, int limit, RoiPlan &pl) {
+                int border_v, int limit, Mode filter, RoiPlan &pl) {
     const auto any = [&](auto pred) {
         for (int i = 0; i < n; i++)
             for (int k = 0; k < K; k++)
@@ -423,18 +423,20 @@ int matrix_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, i
         return false;
     };
     return coord_plan(
-        p, n_frames, frames, recs != nullptr, n, border_y, border_u, border_v, limit, pl, [&](int i) { return recs[i].frame >= 0 && recs[i].frame < n_frames; },
+        p, n_frames, frames, recs != nullptr, n, border_y, border_u, border_v, limit, filter, pl, [&](int i) { return recs[i].frame >= 0 && recs[i].frame < n_frames; },
         [&] { return any([](float v) { return !std::isfinite(v); }); },
         // with every entry inside 2^24 and indices below 2^31 no numerator or denominator overflows: every one is finite
         [&] { return any([](float v) { return std::fabs(v) > 16777216.0f; }); });
 }
 
-int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl) {
-    return matrix_plan(p, n_frames, frames, n_warps, warps, &tsvpp_warp::m, border_y, border_u, border_v, TSVPP_MAX_WARPS, pl);
+int warp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, int border_y, int border_u, int border_v, RoiPlan &pl,
+              Mode filter) {
+    return matrix_plan(p, n_frames, frames, n_warps, warps, &tsvpp_warp::m, border_y, border_u, border_v, TSVPP_MAX_WARPS, filter, pl);
 }
 
-int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, int border_y, int border_u, int border_v, RoiPlan &pl) {
-    const int sts = matrix_plan(p, n_frames, frames, n, persps, &tsvpp_persp::h, border_y, border_u, border_v, TSVPP_MAX_PERSP, pl);
+int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n, const tsvpp_persp *persps, int border_y, int border_u, int border_v, RoiPlan &pl,
+               Mode filter) {
+    const int sts = matrix_plan(p, n_frames, frames, n, persps, &tsvpp_persp::h, border_y, border_u, border_v, TSVPP_MAX_PERSP, filter, pl);
     if (sts != TSVPP_OK) return sts;
     // the horizon: the denominator, as the kernel evaluates it, is monotone in each index, so its least value over the output is that of a corner pixel (luma
     // grid) or corner pair (chroma grid).  Below 2^-64 a reciprocal could overflow or change sign: no answer
@@ -453,7 +455,7 @@ static bool remap_index_ok(const tsvpp_remap &r, int n_frames, int n_grids) { re
 int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y,
                int border_u, int border_v, RoiPlan &pl) {
     return coord_plan(
-        p, n_frames, frames, maps && remaps && n_maps > 0, n, border_y, border_u, border_v, TSVPP_MAX_REMAPS, pl,
+        p, n_frames, frames, maps && remaps && n_maps > 0, n, border_y, border_u, border_v, TSVPP_MAX_REMAPS, M_BILINEAR, pl,
         [&](int i) { return remap_index_ok(remaps[i], n_frames, n_maps); },
         [&] {
             for (int m = 0; m < n_maps; m++) {
@@ -470,7 +472,7 @@ int mesh_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int
               int border_u, int border_v, RoiPlan &pl) {
     const auto cell_ok = [](int l) { return l >= MESH_LOG2_MIN && l <= MESH_LOG2_MAX; };
     return coord_plan(
-        p, n_frames, frames, meshes && remaps && n_meshes > 0, n, border_y, border_u, border_v, TSVPP_MAX_MESHES, pl,
+        p, n_frames, frames, meshes && remaps && n_meshes > 0, n, border_y, border_u, border_v, TSVPP_MAX_MESHES, M_BILINEAR, pl,
         [&](int i) { return remap_index_ok(remaps[i], n_frames, n_meshes); },
         [&] {
             for (int m = 0; m < n_meshes; m++) {

@@ -104,8 +104,9 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_rois_sized_bytes", "tsvpp_convert_rois_sized", "tsvpp_describe_rois_sized", "tsvpp_convert_rois_sized_tensor", "tsvpp_describe_rois_sized_tensor",
            "tsvpp_rois_sized_tile",
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
+           "tsvpp_convert_warp_bicubic", "tsvpp_describe_warp_bicubic", "tsvpp_warp_bicubic_footprint",
            "tsvpp_convert_perspective", "tsvpp_describe_perspective", "tsvpp_convert_perspective_tensor", "tsvpp_describe_perspective_tensor", "tsvpp_persp_from_quad",
-           "tsvpp_persp_footprint",
+           "tsvpp_persp_footprint", "tsvpp_convert_perspective_bicubic", "tsvpp_describe_perspective_bicubic", "tsvpp_persp_bicubic_footprint",
            "tsvpp_convert_remap", "tsvpp_describe_remap", "tsvpp_convert_remap_tensor", "tsvpp_describe_remap_tensor", "tsvpp_remap_footprint", "tsvpp_remap_lds_need",
            "tsvpp_convert_mesh", "tsvpp_describe_mesh", "tsvpp_convert_mesh_tensor", "tsvpp_describe_mesh_tensor", "tsvpp_mesh_dims", "tsvpp_mesh_expand",
            "tsvpp_mesh_from_map", "tsvpp_mesh_error", "tsvpp_mesh_lds_need"]
@@ -220,6 +221,13 @@ def lib():
     L.tsvpp_warp_rotated_box.restype = i32
     L.tsvpp_warp_footprint.argtypes = [pw, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
     L.tsvpp_warp_footprint.restype = i32
+    # (BICUBIC: one pair per call, spec may be None)
+    L.tsvpp_convert_warp_bicubic.argtypes = L.tsvpp_convert_warp_tensor.argtypes
+    L.tsvpp_convert_warp_bicubic.restype = i32
+    L.tsvpp_describe_warp_bicubic.argtypes = L.tsvpp_describe_warp_tensor.argtypes
+    L.tsvpp_describe_warp_bicubic.restype = i32
+    L.tsvpp_warp_bicubic_footprint.argtypes = L.tsvpp_warp_footprint.argtypes
+    L.tsvpp_warp_bicubic_footprint.restype = i32
     pq = ctypes.POINTER(Persp)
     L.tsvpp_convert_perspective.argtypes = [vp, i32, pn, i32, pq, pp, i32, i32, i32, ctypes.POINTER(vp), vp]
     L.tsvpp_convert_perspective.restype = i32
@@ -233,6 +241,12 @@ def lib():
     L.tsvpp_persp_from_quad.restype = i32
     L.tsvpp_persp_footprint.argtypes = [pq, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32)]
     L.tsvpp_persp_footprint.restype = i32
+    L.tsvpp_convert_perspective_bicubic.argtypes = L.tsvpp_convert_perspective_tensor.argtypes
+    L.tsvpp_convert_perspective_bicubic.restype = i32
+    L.tsvpp_describe_perspective_bicubic.argtypes = L.tsvpp_describe_perspective_tensor.argtypes
+    L.tsvpp_describe_perspective_bicubic.restype = i32
+    L.tsvpp_persp_bicubic_footprint.argtypes = L.tsvpp_persp_footprint.argtypes
+    L.tsvpp_persp_bicubic_footprint.restype = i32
     pm, pr, pf = ctypes.POINTER(Map), ctypes.POINTER(Remap), ctypes.POINTER(ctypes.c_float)
     L.tsvpp_convert_remap.argtypes = [vp, i32, pn, i32, pm, i32, pr, pp, i32, i32, i32, ctypes.POINTER(vp), vp]
     L.tsvpp_convert_remap.restype = i32

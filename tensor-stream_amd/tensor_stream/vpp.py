@@ -445,6 +445,26 @@ class VideoProcessor:
         return self._convert_coord("convert_perspective", "homography", (self._lib.tsvpp_convert_perspective, self._lib.tsvpp_convert_perspective_tensor), items, ys,
                                    uvs, params, border, out, width, height, dtype, mean, std)
 
+    def convert_warp_bicubic(self, ys, uvs, warps, params, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_warp sampled with the library's BICUBIC (tsvpp_convert_warp_bicubic): the coordinate is convert_warp's bit for bit, the 4 x 4 taps follow the
+        reference's edge rule and the sums are Convert(BICUBIC)'s -- the scale-only matrix gives Convert(BICUBIC) of the whole frame bit for bit.  params'
+        resize_type must be BICUBIC; every argument and the result: as convert_warp (dtype / mean / std: the same entry point with a spec)."""
+        def items(p, ys, uvs):
+            ys, uvs, recs = _normalize_warps(ys, uvs, warps)
+            return ys, uvs, len(recs), (len(recs), recs)
+        return self._convert_coord("convert_warp_bicubic", "matrix", _convert_pair(self._lib.tsvpp_convert_warp_bicubic), items, ys, uvs, params, border, out, width,
+                                   height, dtype, mean, std)
+
+    def convert_perspective_bicubic(self, ys, uvs, persps, params, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_perspective sampled with the library's BICUBIC (tsvpp_convert_perspective_bicubic): the coordinate is convert_perspective's bit for bit, the
+        sample convert_warp_bicubic's -- a homography with last row (0, 0, 1) gives that call's bits.  params' resize_type must be BICUBIC; every argument and the
+        result: as convert_perspective."""
+        def items(p, ys, uvs):
+            ys, uvs, recs = _normalize_persps(ys, uvs, persps)
+            return ys, uvs, len(recs), (len(recs), recs)
+        return self._convert_coord("convert_perspective_bicubic", "homography", _convert_pair(self._lib.tsvpp_convert_perspective_bicubic), items, ys, uvs, params,
+                                   border, out, width, height, dtype, mean, std)
+
     def _convert_coord(self, name, one, entries, items, ys, uvs, params, border, out, width, height, dtype, mean, std):
         """convert_warp, convert_perspective, convert_remap and convert_mesh, once.  entries: the call's (colour, tensor) entry points; items(p, ys, uvs): the
         path's own arguments as (luma planes, chroma planes, number of outputs, the arguments that sit between `frames` and `params` in the C call); one: what an
@@ -750,6 +770,17 @@ def _border(border):
     return y, u, v
 
 
+def _convert_pair(entry):
+    """An entry point whose `spec` may be null (tsvpp_convert_warp_bicubic) as _convert_coord's (colour, tensor) pair: the colour form passes no spec.  The spec
+    sits behind `params`, in front of the last five arguments."""
+    return (lambda *a: entry(*a[:-5], None, *a[-5:])), entry
+
+
+def _describe_pair(entry):
+    """... and a describe call of that kind as _describe_coord's pair: the spec sits behind `params`, the first argument"""
+    return (lambda p, *a: entry(p, None, *a)), entry
+
+
 def _describe_coord(entries, items, params, frames, border, aligned_outputs, dtype, mean, std):
     """describe_warp, describe_perspective, describe_remap and describe_mesh, once.  entries: the call's (colour, tensor) entry points; items(p, frame records):
     the arguments that sit between `frames` and the border in the C call."""
@@ -791,6 +822,15 @@ def describe_warp(params, frames, warps, border=None, aligned_outputs=True, dtyp
     return _describe_coord((N.lib().tsvpp_describe_warp, N.lib().tsvpp_describe_warp_tensor), items, params, frames, border, aligned_outputs, dtype, mean, std)
 
 
+def describe_warp_bicubic(params, frames, warps, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_warp_bicubic of this request would launch, as a dict (tsvpp_describe_warp_bicubic: describe_warp's keys, mode warp_bicubic) -- host logic
+    only, works without a GPU.  Arguments as describe_warp."""
+    def items(p, recs):
+        _, _, ws = _normalize_warps([None] * len(recs), [None] * len(recs), warps)
+        return len(ws), ws or None
+    return _describe_coord(_describe_pair(N.lib().tsvpp_describe_warp_bicubic), items, params, frames, border, aligned_outputs, dtype, mean, std)
+
+
 def warp_rotated_box(cx, cy, box_w, box_h, angle_rad, dst_w, dst_h):
     """The matrix (m0, ..., m5), as float32 values, that maps a dst_w x dst_h output onto the box of box_w x box_h luma pixels centred at (cx, cy) and rotated
     by angle_rad, clockwise on screen (tsvpp_warp_rotated_box: evaluated in double, each entry rounded once)."""
@@ -828,6 +868,15 @@ def describe_perspective(params, frames, persps, border=None, aligned_outputs=Tr
         return len(qs), qs or None
     return _describe_coord((N.lib().tsvpp_describe_perspective, N.lib().tsvpp_describe_perspective_tensor), items, params, frames, border, aligned_outputs, dtype, mean,
                            std)
+
+
+def describe_perspective_bicubic(params, frames, persps, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_perspective_bicubic of this request would launch, as a dict (tsvpp_describe_perspective_bicubic: describe_perspective's keys, mode
+    persp_bicubic) -- host logic only, works without a GPU.  Arguments as describe_perspective."""
+    def items(p, recs):
+        _, _, qs = _normalize_persps([None] * len(recs), [None] * len(recs), persps)
+        return len(qs), qs or None
+    return _describe_coord(_describe_pair(N.lib().tsvpp_describe_perspective_bicubic), items, params, frames, border, aligned_outputs, dtype, mean, std)
 
 
 def perspective_from_quad(quad, dst_w, dst_h):

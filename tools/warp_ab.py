@@ -3,6 +3,7 @@
 with HIP events.
 
     python tools/warp_ab.py [--out profiles/warp_ab.txt] [--repeats 20] [--iters 50] [--ns 1,4,16,32]
+    python tools/warp_ab.py --bicubic        tsvpp_convert_warp_bicubic: the protocol below with the legs of tools/coord_bicubic_ab.py, into profiles/warp_bicubic_ab.txt
 
 Protocol (tools/rois_ab.py's): per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the
 figure is the MEDIAN block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next frame of a pool of 96 distinct 1080p
@@ -100,12 +101,17 @@ def must_move(L, mats, elem):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "warp_ab.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/warp_ab.txt; with --bicubic: profiles/warp_bicubic_ab.txt")
+    ap.add_argument("--bicubic", action="store_true", help="the BICUBIC call against Convert + grid_sample(bicubic) and against the BILINEAR call (tools/coord_bicubic_ab.py)")
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--ns", default="1,4,16,32")
     ap.add_argument("--frames", type=int, default=96)
     a = ap.parse_args()
+    if a.bicubic:
+        import coord_bicubic_ab
+        return coord_bicubic_ab.run("warp", a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "warp_ab.txt")
     assert torch.cuda.is_available(), "tools/warp_ab.py measures on the GPU: there is nothing to report without one"
     O.build()
     L = N.lib()

@@ -530,7 +530,7 @@ int tsvpp_warp_footprint(const tsvpp_warp *warp, int frame_w, int frame_h, int j
  *                fmaf(j + 0.5f, ratio, -0.5f)); a translation by even integers inside the frame is the plain colour conversion of that crop (w = 0: coefficients
  *                0, 1, 0, 0).
  * Status: tsvpp_convert_warp's, in its order, with "a resize type other than BICUBIC" (BILINEAR, NEAREST, AREA, unknown: TSVPP_UNSUPPORTED); with a spec, rules 2
- * and 3 of the tensor block follow.  Out of scope: BICUBIC for tsvpp_convert_remap / tsvpp_convert_mesh, NEAREST / AREA warps, per-output sizes. */
+ * and 3 of the tensor block follow.  BICUBIC maps and meshes: tsvpp_convert_remap_bicubic / tsvpp_convert_mesh_bicubic (below).  Out of scope: NEAREST / AREA warps, per-output sizes. */
 int tsvpp_convert_warp_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_warps, const tsvpp_warp *warps, const tsvpp_params *p,
                                const tsvpp_tensor_spec *spec /* may be NULL */, int border_y, int border_u, int border_v, void *const *outs, void *stream);
 /* What tsvpp_convert_warp_bicubic WOULD launch: tsvpp_describe_warp's (with a spec: tsvpp_describe_warp_tensor's) line with mode=warp_bicubic and
@@ -759,6 +759,56 @@ int tsvpp_mesh_from_map(const float *host_xy, int pitch, int dst_w, int dst_h, i
 int tsvpp_mesh_error(const float *host_xy, int pitch, int dst_w, int dst_h, const float *host_mesh, int mesh_pitch, int log2_cw, int log2_ch, float *max_abs);
 /* tsvpp_remap_lds_need of E(mesh): what a caller puts into tsvpp_mesh::lds_bytes. */
 int tsvpp_mesh_lds_need(const float *host_mesh, int pitch, int dst_w, int dst_h, int log2_cw, int log2_ch, int frame_w, int frame_h, int luma_only);
+
+/* ---- BICUBIC coordinate maps and warp meshes (not in the reference) ----------------------------------------------------------------------------------------------
+ * tsvpp_convert_remap / tsvpp_convert_mesh with the library's BICUBIC in place of their BILINEAR -- OpenCV's remap(..., INTER_CUBIC): a lens correction resamples
+ * every pixel of every frame at a non-integer position, so a soft filter softens the whole stream.  Entry points of their own because the BILINEAR calls' answer
+ * to BICUBIC (TSVPP_UNSUPPORTED) is part of their contract.  One pair per call serves both output families, as tsvpp_convert_warp_bicubic's: `spec` == NULL --
+ * outputs and rules are tsvpp_convert_remap's / tsvpp_convert_mesh's (uint8 and fp32, RGB24 / BGR24 planar and merged, Y800); with a `spec` they are the tensor
+ * forms', word for word.
+ *   Coordinate   Dense call: tsvpp_convert_remap's, bit for bit -- the luma coordinate is the map entry, the chroma coordinate is
+ *                fmaf((x00 + x01) + (x10 + x11), 0.125f, -0.25f) of the UNCLAMPED entries, then the clamp c = fminf(fmaxf(f, -1.0f), (float)limit), fmaxf first so a
+ *                NaN counts as -1.  Mesh call: tsvpp_convert_mesh's coordinate (the three fused multiply-adds), then the same.  Every bit pattern stays legal.
+ *   From c on    everything is tsvpp_convert_warp_bicubic's, word for word: the axis (p = floor(c), w = c - p, both ends folded; its own clamp is a no-op here), the
+ *                reference's edge rule for the taps, Keys' cubic with a = -0.75 -- fp64 row sums rounded half away from zero and clamped, then the column sum of
+ *                those integers; evaluated in fp32 and recomputed in fp64 near a tie --, U and V from byte columns 2 p and 2 p + 1, the border test on c (luma and
+ *                chroma decide independently; -1, -1, -1 replicates), and the one colour back end.
+ *   Identities   The identity map with dst equal to the frame is tsvpp_convert without a resize (w = 0: coefficients 0, 1, 0, 0).  A map that holds the coordinates
+ *                of an exact power-of-two ratio is tsvpp_convert(BICUBIC) at that ratio, down (x = 2 j + 0.5) and up (x = 0.5 j - 0.25): the chroma expression is
+ *                exact there.  A translation by even integers is the crop.  A map that holds the fp32 luma coordinates of an affine matrix gives, as Y800, the bits
+ *                of tsvpp_convert_warp_bicubic's Y800; colour does not match, the chroma coordinate is this call's own.  tsvpp_convert_mesh_bicubic is, bit for
+ *                bit, tsvpp_convert_remap_bicubic of tsvpp_mesh_expand(mesh).
+ *   Footprint    Per axis [P(min) - 1, P(max) + 2], clamped into the plane: P is the centre tap (the floor clamped into 0 .. limit - 1), min and max the extremes
+ *                of the tile's own clamped coordinates -- the reduction the BILINEAR kernel does, with the halo rule of tsvpp_warp_bicubic_footprint.  One
+ *                function for host and kernel; tsvpp_remap_bicubic_footprint evaluates it on a host copy.
+ *   LDS hint     tsvpp_map::lds_bytes / tsvpp_mesh::lds_bytes as in the BILINEAR calls; tsvpp_remap_bicubic_lds_need computes it with this footprint.  A hint
+ *                computed for the BILINEAR call is never wrong here, only slower: the tiles it is too small for gather.
+ * Carried over unchanged: tsvpp_map, tsvpp_mesh, tsvpp_remap, the records by value in the kernarg segment (TSVPP_MAX_REMAPS / TSVPP_MAX_MESHES outputs per
+ * launch), no allocation, no copy, no host synchronisation, legality under stream capture with map and mesh updates visible to a replayed graph, no byte of pitch
+ * padding read, TSVPP_OPT_COLOR_G_TERM and the coefficient block.
+ * Status: the BILINEAR call's, in its order, with "a resize type other than BICUBIC" (BILINEAR, NEAREST, AREA, unknown: TSVPP_UNSUPPORTED); with a spec, rules 2
+ * and 3 of the tensor block follow.  Out of scope: NEAREST / AREA maps, fixed-point maps, per-output sizes. */
+int tsvpp_convert_remap_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps,
+                                const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int border_y, int border_u, int border_v, void *const *outs,
+                                void *stream);
+/* What tsvpp_convert_remap_bicubic WOULD launch: tsvpp_describe_remap's (with a spec: tsvpp_describe_remap_tensor's) line with mode=remap_bicubic and
+ * kernel=vpp_remap_bicubic<...> (vpp_remap_bicubic_tensor<...>); every other key is that call's.  Host only: needs no context and no GPU. */
+int tsvpp_describe_remap_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_nv12 *frames, int n_maps,
+                                 const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf,
+                                 size_t buf_len);
+int tsvpp_convert_mesh_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
+                               const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int border_y, int border_u, int border_v, void *const *outs,
+                               void *stream);
+/* ... with mode=mesh_bicubic and kernel=vpp_mesh_bicubic<...> (vpp_mesh_bicubic_tensor<...>). */
+int tsvpp_describe_mesh_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_nv12 *frames, int n_meshes,
+                                const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf,
+                                size_t buf_len);
+/* DEBUG ONLY (tests), host only: tsvpp_remap_footprint for the BICUBIC calls ("Footprint" above).  Arguments and statuses as tsvpp_remap_footprint. */
+int tsvpp_remap_bicubic_footprint(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int j_first, int j_last, int i_first, int i_last,
+                                  int32_t *out8);
+/* Host only: tsvpp_remap_lds_need with that footprint -- what a caller of the BICUBIC calls puts into tsvpp_map::lds_bytes (for a mesh: of tsvpp_mesh_expand's
+ * map, into tsvpp_mesh::lds_bytes). */
+int tsvpp_remap_bicubic_lds_need(const float *host_xy, int pitch, int dst_w, int dst_h, int frame_w, int frame_h, int luma_only);
 
 /* Pre-build everything a (params, input size) pair needs so that later tsvpp_convert* calls for it touch no
  * allocator -- e.g. before hipGraph capture: the AREA weight tables (the reference mallocs, copies and leaks them

@@ -358,6 +358,32 @@ int VideoProcessor::ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp
                         });
 }
 
+int VideoProcessor::ConvertBicubicRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY,
+                                        int borderU, int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, nInputs, maps && nMaps > 0 && remaps && nRemaps > 0, deviceOuts, options, consumerName, "ConvertBicubicRemap",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_remap_bicubic(ctx, nInputs, frames, nMaps, maps, nRemaps, remaps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertBicubicRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY,
+                                        int borderU, int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
+    return ConvertBicubicRemap(inputs, nInputs, maps, nMaps, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, nullptr, consumerName);
+}
+
+int VideoProcessor::ConvertBicubicMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY,
+                                       int borderU, int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, nInputs, meshes && nMeshes > 0 && remaps && nRemaps > 0, deviceOuts, options, consumerName, "ConvertBicubicMesh",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_mesh_bicubic(ctx, nInputs, frames, nMeshes, meshes, nRemaps, remaps, p, spec, borderY, borderU, borderV, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertBicubicMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY,
+                                       int borderU, int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName) {
+    return ConvertBicubicMesh(inputs, nInputs, meshes, nMeshes, remaps, nRemaps, borderY, borderU, borderV, deviceOuts, options, nullptr, consumerName);
+}
+
 int VideoProcessor::Convert(AVFrame *input, AVFrame *output, FrameParameters &options, std::string consumerName) {
     if (isClosed || !input || !output) CHECK_STATUS(VREADER_ERROR);
     const tsvpp_params p = flatten(options);

@@ -194,6 +194,19 @@ public:
                     void *const *deviceOuts, FrameParameters &options, std::string consumerName);
     int ConvertMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU, int borderV,
                     void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertRemap and ConvertMesh sampled with the library's BICUBIC -- OpenCV's remap(..., INTER_CUBIC) (tsvpp_convert_remap_bicubic, tsvpp_convert_mesh_bicubic,
+    // include/tsvpp.h; not in the reference): the coordinate is the BILINEAR method's bit for bit, the sample ConvertWarpBicubic's.  options.resize must be
+    // BICUBIC.  `spec` may be null (the plain flavours) or not (the tensor forms); every other argument as the BILINEAR method's.  (The word order differs from
+    // ConvertWarpBicubic's on purpose: the exported symbols that contain "ConvertRemap" are exactly the BILINEAR method's two, which tests/test_remap_cpu.py
+    // counts; the mesh method follows the map method.)
+    int ConvertBicubicRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                            int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    int ConvertBicubicRemap(AVFrame *const *inputs, int nInputs, const tsvpp_map *maps, int nMaps, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                            int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
+    int ConvertBicubicMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                           int borderV, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    int ConvertBicubicMesh(AVFrame *const *inputs, int nInputs, const tsvpp_mesh *meshes, int nMeshes, const tsvpp_remap *remaps, int nRemaps, int borderY, int borderU,
+                           int borderV, void *const *deviceOuts, FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
     // Hands a result of Convert (output->opaque) BACK to the processor instead of hipFree()ing it (round 6).  hipFree stays legal -- it is the reference's
     // contract (c_examples/src/Sample.cpp:27,36) -- but it costs a device-wide synchronisation and the next Convert a hipMalloc: 120-180 us a frame with millisecond
     // outliers, where the conversion itself takes ~6.  A released buffer is reused by the next Convert that needs the same number of bytes: no allocator call in

@@ -1,16 +1,22 @@
 // vpp_mesh -- samples one NV12 frame through a handful of warp meshes with the C++ class (VideoProcessor::ConvertMesh) and prints a CRC-32 per output (the
 // zlib / IEEE 802.3 one: reflected 0xEDB88320, as Python's zlib.crc32); tests/test_cpp_mesh_gpu.py compares each with the CRC of the expected output.
-//   vpp_mesh [--dtype f16|bf16|f32] [--mean a,b,c] [--scale a,b,c] DW DH FOURCC PLANES NORM BY BU BV frame.nv12 W H PITCH LOG2_CW LOG2_CH  mesh.f32 [mesh.f32 ...]
+//   vpp_mesh [--bicubic] [--dtype f16|bf16|f32] [--mean a,b,c] [--scale a,b,c] DW DH FOURCC PLANES NORM BY BU BV frame.nv12 W H PITCH LOG2_CW LOG2_CH  mesh.f32 [mesh.f32 ...]
+// --bicubic: through VideoProcessor::ConvertBicubicMesh (BICUBIC in place of BILINEAR; tests/test_cpp_remap_bicubic_gpu.py).
 // --dtype / --mean / --scale: through the ConvertMesh overload that takes a tsvpp_tensor_spec.  BY BU BV: the border sample, or -1 -1 -1 to replicate the edge.
 // A mesh file is raw fp32: tsvpp_mesh_dims' rows of cols (x, y) control points, tight.  The frame file holds H rows of PITCH bytes of luma, then H / 2 rows of
 // PITCH bytes of chroma.  Output k samples the frame through mesh k.  Prints "<index> <crc> <bytes>" per output; exit code 0 = converted.
 #include "check_common.h"
 
 int main(int argc, char **argv) {
+    const bool cubic = argc > 1 && strcmp(argv[1], "--bicubic") == 0;
+    if (cubic) {
+        argv++;
+        argc--;
+    }
     tsvpp_tensor_spec spec;
     const bool tensor = tensor_flags(argc, argv, spec);
     if (argc < 16) {
-        fprintf(stderr, "usage: vpp_mesh " TENSOR_FLAGS_USAGE " DW DH FOURCC PLANES NORM BY BU BV frame.nv12 W H PITCH LOG2_CW LOG2_CH mesh.f32 [mesh.f32 ...]\n");
+        fprintf(stderr, "usage: vpp_mesh [--bicubic] " TENSOR_FLAGS_USAGE " DW DH FOURCC PLANES NORM BY BU BV frame.nv12 W H PITCH LOG2_CW LOG2_CH mesh.f32 [mesh.f32 ...]\n");
         return 200;
     }
     const int DW = atoi(argv[1]), DH = atoi(argv[2]), fcc = atoi(argv[3]), planes = atoi(argv[4]), norm = atoi(argv[5]);
@@ -41,19 +47,24 @@ int main(int argc, char **argv) {
 
     VideoProcessor vpp;
     if (vpp.Init(std::make_shared<Logger>()) != 0) return 203;
-    FrameParameters options = frame_parameters(DW, DH, TSVPP_BILINEAR, fcc, planes, norm);
+    const int type = cubic ? TSVPP_BICUBIC : TSVPP_BILINEAR;
+    FrameParameters options = frame_parameters(DW, DH, type, fcc, planes, norm);
     size_t bytes = 0;
-    if (int sts = output_bytes(DW, DH, TSVPP_BILINEAR, fcc, planes, norm, tensor ? &spec : nullptr, bytes)) return sts;
+    if (int sts = output_bytes(DW, DH, type, fcc, planes, norm, tensor ? &spec : nullptr, bytes)) return sts;
     OutputArena arena;
     if (int sts = arena.carve((size_t)n, bytes)) return sts;
-    const int sts = tensor ? vpp.ConvertMesh(inputs, 1, maps.data(), n, remaps.data(), n, bY, bU, bV, arena.outs.data(), options, &spec, "mesh")
-                           : vpp.ConvertMesh(inputs, 1, maps.data(), n, remaps.data(), n, bY, bU, bV, arena.outs.data(), options, "mesh");
+    // the four forms: BILINEAR or --bicubic, plain or with the tensor spec (the BICUBIC method's spec may be null)
+    const auto convert = [&](const tsvpp_remap *items, int cnt) {
+        if (cubic) return vpp.ConvertBicubicMesh(inputs, 1, maps.data(), n, items, cnt, bY, bU, bV, arena.outs.data(), options, tensor ? &spec : nullptr, "mesh");
+        return tensor ? vpp.ConvertMesh(inputs, 1, maps.data(), n, items, cnt, bY, bU, bV, arena.outs.data(), options, &spec, "mesh")
+                      : vpp.ConvertMesh(inputs, 1, maps.data(), n, items, cnt, bY, bU, bV, arena.outs.data(), options, "mesh");
+    };
+    const int sts = convert(remaps.data(), n);
     if (sts != 0) return 210;
     if (int failed = print_outputs(vpp, "mesh", arena, crc32_zlib)) return failed;
     // a mesh index that was not given is refused with the reference's status convention, and nothing is launched
     const tsvpp_remap bad = { 0, n };
-    const int refused = tensor ? vpp.ConvertMesh(inputs, 1, maps.data(), n, &bad, 1, bY, bU, bV, arena.outs.data(), options, &spec, "mesh")
-                               : vpp.ConvertMesh(inputs, 1, maps.data(), n, &bad, 1, bY, bU, bV, arena.outs.data(), options, "mesh");
+    const int refused = convert(&bad, 1);
     if (refused != VREADER_ERROR) return 214;
     av_frame_free(&input);
     vpp.Close();

@@ -1,5 +1,6 @@
 // tsvpp_mesh.cpp -- sparse control-grid warps (include/tsvpp.h): tsvpp_convert_mesh / tsvpp_describe_mesh, their tensor forms (`spec`, null for the first pair;
-// kernel vpp_mesh_tensor.hip) and the host-only functions on HOST copies of a mesh and a map: tsvpp_mesh_dims, tsvpp_mesh_expand, tsvpp_mesh_from_map,
+// kernel vpp_mesh_tensor.hip), tsvpp_convert_mesh_bicubic / tsvpp_describe_mesh_bicubic (BICUBIC: `spec` null or not; kernels vpp_mesh_bicubic.hip /
+// vpp_mesh_bicubic_tensor.hip) and the host-only functions on HOST copies of a mesh and a map: tsvpp_mesh_dims, tsvpp_mesh_expand, tsvpp_mesh_from_map,
 // tsvpp_mesh_error, tsvpp_mesh_lds_need; TSVPP_MAX_MESHES outputs per launch, kernel vpp_mesh.hip.  The body is tsvpp_tiles.h's, and so is what the four
 // coordinate paths share (CoordRequest): MeshPath says what differs -- the request rules (mesh_plan, tsvpp_plan.cpp) and the record.  The launch's LDS is the
 // budget or the caller's hint (coord_hint_budget), as the dense call's: the meshes live in device memory and the host plans nothing per tile.
@@ -8,14 +9,14 @@
 #include <vector>
 
 #include "tsvpp_tiles.h"
-#include "vpp_mesh.h"
+#include "vpp_map_bicubic.h"
 
 using namespace tsvpp;
 
 namespace {
 
-// The request of one call, as tsvpp_tiles.h asks for it
-struct MeshPath : CoordRequest {
+// The request of one call, as tsvpp_tiles.h asks for it.  CUBIC: the *_bicubic entry points, as RemapPathT's (tsvpp_remap.cpp)
+template <bool CUBIC> struct MeshPathT : CoordRequest {
     using Launch = MeshLaunch;
     static constexpr bool kCountsStaged = false;
     int n_meshes;
@@ -23,7 +24,7 @@ struct MeshPath : CoordRequest {
     int n;
     const tsvpp_remap *remaps;
 
-    int plan(RoiPlan &pl) const { return mesh_plan(p, n_frames, frames, n_meshes, meshes, n, remaps, border_y, border_u, border_v, pl); }
+    int plan(RoiPlan &pl) const { return mesh_plan(p, n_frames, frames, n_meshes, meshes, n, remaps, border_y, border_u, border_v, pl, CUBIC ? M_BICUBIC : M_BILINEAR); }
     int items() const { return n; }
     int limit(const RoiPlan &) const { return (int)TSVPP_MAX_MESHES; }
     int grids() const { return n_meshes; }
@@ -47,16 +48,18 @@ struct MeshPath : CoordRequest {
     }
     int stage_budget(const RoiPlan &, MeshLaunch &L, int budget, bool) const { return coord_hint_budget(L, budget, REMAP_REDUCE_LDS); }
     hipError_t launch(const RoiPlan &pl, bool vec, bool, const MeshLaunch &L, hipStream_t stream, char *name, size_t name_len, bool dry_run) const {
-        return launch_with(launch_mesh, launch_mesh_tensor, pl, vec, L, stream, name, name_len, dry_run);
+        return launch_with(CUBIC ? launch_mesh_bicubic : launch_mesh, CUBIC ? launch_mesh_bicubic_tensor : launch_mesh_tensor, pl, vec, L, stream, name, name_len, dry_run);
     }
-    const char *mode_name(const RoiPlan &) const { return "mesh_bilinear"; }
+    const char *mode_name(const RoiPlan &) const { return CUBIC ? "mesh_bicubic" : "mesh_bilinear"; }
     void counts(char *buf, size_t len) const {
         std::snprintf(buf, len, "remaps=%d meshes=%d cell=%dx%d frames=%d", n, n_meshes, 1 << meshes[0].log2_cw, 1 << meshes[0].log2_ch, n_frames);
     }
     void label(char *buf, size_t len, const RoiPlan &pl, void *stream) const {
-        std::snprintf(buf, len, "tsvpp_convert_mesh%s n=%d meshes=%d frames=%d ->%dx%d fourcc=%d stream=%p", tensor ? "_tensor" : "", n, n_meshes, n_frames, pl.dst_w, pl.dst_h, p->fourcc, stream);
+        std::snprintf(buf, len, "tsvpp_convert_mesh%s%s n=%d meshes=%d frames=%d ->%dx%d fourcc=%d stream=%p", CUBIC ? "_bicubic" : "", tensor ? "_tensor" : "", n, n_meshes, n_frames, pl.dst_w, pl.dst_h, p->fourcc, stream);
     }
 };
+using MeshPath = MeshPathT<false>;
+using MeshBicubicPath = MeshPathT<true>;
 
 // ---- HOST copies ----
 // A grid of (x, y) fp32 pairs, rows `pitch` bytes apart: a control grid or a dense map
@@ -126,6 +129,16 @@ int tsvpp_convert_mesh_tensor(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *fr
 int tsvpp_describe_mesh_tensor(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes,
                                int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
     return tile_describe(MeshPath{ { true, p, spec, n_frames, frames, border_y, border_u, border_v }, n_meshes, meshes, n, remaps }, aligned_outputs, buf, buf_len);
+}
+
+int tsvpp_convert_mesh_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps,
+                               const tsvpp_params *p, const tsvpp_tensor_spec *spec, int border_y, int border_u, int border_v, void *const *outs, void *stream) {
+    return coord_grid_convert(MeshBicubicPath{ { spec != nullptr, p, spec, n_frames, frames, border_y, border_u, border_v }, n_meshes, meshes, n, remaps }, ctx, outs, stream);
+}
+
+int tsvpp_describe_mesh_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes,
+                                int n, const tsvpp_remap *remaps, int border_y, int border_u, int border_v, int aligned_outputs, char *buf, size_t buf_len) {
+    return tile_describe(MeshBicubicPath{ { spec != nullptr, p, spec, n_frames, frames, border_y, border_u, border_v }, n_meshes, meshes, n, remaps }, aligned_outputs, buf, buf_len);
 }
 
 int tsvpp_mesh_dims(int dst_w, int dst_h, int log2_cw, int log2_ch, int *cols, int *rows) {

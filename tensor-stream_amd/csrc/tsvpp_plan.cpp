@@ -407,7 +407,7 @@ int coord_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, bo
     // TSVPP_UNSUPPORTED: requests the library (or NV12 itself) has no answer for
     if (tile_request_odd(p, n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
     if (tile_frame_spans(n_frames, frames) != TSVPP_OK) return TSVPP_UNSUPPORTED;
-    // every other resize type belongs to another entry point (BICUBIC warps: tsvpp_convert_warp_bicubic) or is a follow-up (NEAREST, AREA)
+    // every other resize type belongs to another entry point (BICUBIC: tsvpp_convert_warp_bicubic and its kin) or is a follow-up (NEAREST, AREA)
     if (tile_output_plan(p, false, limit, pl) != TSVPP_OK || pl.mode != filter) return TSVPP_UNSUPPORTED;
     return path_unsupported() ? TSVPP_UNSUPPORTED : TSVPP_OK;
 }
@@ -453,9 +453,9 @@ int persp_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, in
 static bool remap_index_ok(const tsvpp_remap &r, int n_frames, int n_grids) { return r.frame >= 0 && r.frame < n_frames && r.map >= 0 && r.map < n_grids; }
 
 int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_maps, const tsvpp_map *maps, int n, const tsvpp_remap *remaps, int border_y,
-               int border_u, int border_v, RoiPlan &pl) {
+               int border_u, int border_v, RoiPlan &pl, Mode filter) {
     return coord_plan(
-        p, n_frames, frames, maps && remaps && n_maps > 0, n, border_y, border_u, border_v, TSVPP_MAX_REMAPS, M_BILINEAR, pl,
+        p, n_frames, frames, maps && remaps && n_maps > 0, n, border_y, border_u, border_v, TSVPP_MAX_REMAPS, filter, pl,
         [&](int i) { return remap_index_ok(remaps[i], n_frames, n_maps); },
         [&] {
             for (int m = 0; m < n_maps; m++) {
@@ -469,10 +469,10 @@ int remap_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, in
 }
 
 int mesh_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *frames, int n_meshes, const tsvpp_mesh *meshes, int n, const tsvpp_remap *remaps, int border_y,
-              int border_u, int border_v, RoiPlan &pl) {
+              int border_u, int border_v, RoiPlan &pl, Mode filter) {
     const auto cell_ok = [](int l) { return l >= MESH_LOG2_MIN && l <= MESH_LOG2_MAX; };
     return coord_plan(
-        p, n_frames, frames, meshes && remaps && n_meshes > 0, n, border_y, border_u, border_v, TSVPP_MAX_MESHES, M_BILINEAR, pl,
+        p, n_frames, frames, meshes && remaps && n_meshes > 0, n, border_y, border_u, border_v, TSVPP_MAX_MESHES, filter, pl,
         [&](int i) { return remap_index_ok(remaps[i], n_frames, n_meshes); },
         [&] {
             for (int m = 0; m < n_meshes; m++) {

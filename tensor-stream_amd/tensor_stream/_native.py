@@ -109,7 +109,9 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_persp_footprint", "tsvpp_convert_perspective_bicubic", "tsvpp_describe_perspective_bicubic", "tsvpp_persp_bicubic_footprint",
            "tsvpp_convert_remap", "tsvpp_describe_remap", "tsvpp_convert_remap_tensor", "tsvpp_describe_remap_tensor", "tsvpp_remap_footprint", "tsvpp_remap_lds_need",
            "tsvpp_convert_mesh", "tsvpp_describe_mesh", "tsvpp_convert_mesh_tensor", "tsvpp_describe_mesh_tensor", "tsvpp_mesh_dims", "tsvpp_mesh_expand",
-           "tsvpp_mesh_from_map", "tsvpp_mesh_error", "tsvpp_mesh_lds_need"]
+           "tsvpp_mesh_from_map", "tsvpp_mesh_error", "tsvpp_mesh_lds_need",
+           "tsvpp_convert_remap_bicubic", "tsvpp_describe_remap_bicubic", "tsvpp_convert_mesh_bicubic", "tsvpp_describe_mesh_bicubic",
+           "tsvpp_remap_bicubic_footprint", "tsvpp_remap_bicubic_lds_need"]
 
 _lib = None
 
@@ -279,6 +281,12 @@ def lib():
     L.tsvpp_mesh_error.restype = i32
     L.tsvpp_mesh_lds_need.argtypes = [pf, i32, i32, i32, i32, i32, i32, i32, i32]
     L.tsvpp_mesh_lds_need.restype = i32
+    # the BICUBIC map calls: one pair of entry points each, the tensor forms' signatures with a spec that may be null
+    for name, like in (("tsvpp_convert_remap_bicubic", L.tsvpp_convert_remap_tensor), ("tsvpp_describe_remap_bicubic", L.tsvpp_describe_remap_tensor),
+                       ("tsvpp_convert_mesh_bicubic", L.tsvpp_convert_mesh_tensor), ("tsvpp_describe_mesh_bicubic", L.tsvpp_describe_mesh_tensor),
+                       ("tsvpp_remap_bicubic_footprint", L.tsvpp_remap_footprint), ("tsvpp_remap_bicubic_lds_need", L.tsvpp_remap_lds_need)):
+        getattr(L, name).argtypes = like.argtypes
+        getattr(L, name).restype = i32
     L.tsvpp_debug_area_tables.argtypes = [vp]
     L.tsvpp_debug_area_tables.restype = i32
     L.tsvpp_debug_last_launch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

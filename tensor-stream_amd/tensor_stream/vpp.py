@@ -465,6 +465,30 @@ class VideoProcessor:
         return self._convert_coord("convert_perspective_bicubic", "homography", _convert_pair(self._lib.tsvpp_convert_perspective_bicubic), items, ys, uvs, params,
                                    border, out, width, height, dtype, mean, std)
 
+    def convert_remap_bicubic(self, ys, uvs, maps, params, remaps=None, border=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_remap sampled with the library's BICUBIC -- OpenCV's remap(..., INTER_CUBIC) (tsvpp_convert_remap_bicubic): the coordinate is convert_remap's bit
+        for bit, the sample convert_warp_bicubic's.  params' resize_type must be BICUBIC; a hint comes from remap_lds_hint(..., bicubic=True) (convert_remap's is
+        never wrong here, only slower); every other argument and the result: as convert_remap."""
+        def items(p, ys, uvs):
+            ys, uvs, _ = _normalize_rois(ys, uvs, [])
+            recs_m = _normalize_maps(maps, p.dst_width, p.dst_height, self.device)
+            recs = _normalize_remaps(remaps, len(ys), len(recs_m))
+            return ys, uvs, len(recs), (len(recs_m), recs_m, len(recs), recs)
+        return self._convert_coord("convert_remap_bicubic", None, _convert_pair(self._lib.tsvpp_convert_remap_bicubic), items, ys, uvs, params, border, out, width,
+                                   height, dtype, mean, std)
+
+    def convert_mesh_bicubic(self, ys, uvs, meshes, params, cell=(16, 16), remaps=None, border=None, out=None, width=None, height=None, dtype=None, mean=None,
+                             std=None):
+        """convert_mesh sampled with the library's BICUBIC (tsvpp_convert_mesh_bicubic): bit for bit convert_remap_bicubic of mesh_expand(mesh).  params'
+        resize_type must be BICUBIC; a hint comes from mesh_lds_hint(..., bicubic=True); every other argument and the result: as convert_mesh."""
+        def items(p, ys, uvs):
+            ys, uvs, _ = _normalize_rois(ys, uvs, [])
+            recs_m = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height, self.device)
+            recs = _normalize_remaps(remaps, len(ys), len(recs_m))
+            return ys, uvs, len(recs), (len(recs_m), recs_m, len(recs), recs)
+        return self._convert_coord("convert_mesh_bicubic", None, _convert_pair(self._lib.tsvpp_convert_mesh_bicubic), items, ys, uvs, params, border, out, width,
+                                   height, dtype, mean, std)
+
     def _convert_coord(self, name, one, entries, items, ys, uvs, params, border, out, width, height, dtype, mean, std):
         """convert_warp, convert_perspective, convert_remap and convert_mesh, once.  entries: the call's (colour, tensor) entry points; items(p, ys, uvs): the
         path's own arguments as (luma planes, chroma planes, number of outputs, the arguments that sit between `frames` and `params` in the C call); one: what an
@@ -964,6 +988,16 @@ def describe_remap(params, frames, maps, remaps=None, border=None, aligned_outpu
     return _describe_coord((N.lib().tsvpp_describe_remap, N.lib().tsvpp_describe_remap_tensor), items, params, frames, border, aligned_outputs, dtype, mean, std)
 
 
+def describe_remap_bicubic(params, frames, maps, remaps=None, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_remap_bicubic of this request would launch, as a dict (tsvpp_describe_remap_bicubic: describe_remap's keys, mode remap_bicubic) -- host logic
+    only, works without a GPU.  Arguments as describe_remap."""
+    def items(p, recs):
+        ms = _normalize_maps(maps, p.dst_width, p.dst_height)
+        rs = _normalize_remaps(remaps, len(recs), len(ms))
+        return len(ms), ms, len(rs), rs
+    return _describe_coord(_describe_pair(N.lib().tsvpp_describe_remap_bicubic), items, params, frames, border, aligned_outputs, dtype, mean, std)
+
+
 def remap_from_opencv(map_x, map_y):
     """OpenCV's pair of (H, W) maps (what cv2.initUndistortRectifyMap returns as CV_32FC1, what cv2.remap takes) as one (H, W, 2) float32 map of convert_remap:
     [..., 0] = x, [..., 1] = y.  OpenCV's convention is the contract's -- no arithmetic.  numpy arrays give a numpy array, tensors a tensor on their device."""
@@ -993,14 +1027,16 @@ def remap_from_grid(grid, w, h):
     return np.ascontiguousarray(np.stack((((g[..., 0] + one) * np.float32(w) - one) * half, ((g[..., 1] + one) * np.float32(h) - one) * half), axis=-1))
 
 
-def remap_lds_hint(map, frame_w, frame_h, luma_only=False):
+def remap_lds_hint(map, frame_w, frame_h, luma_only=False, bicubic=False):
     """The LDS hint of a map on a frame_w x frame_h frame (tsvpp_remap_lds_need): the largest staging need, in bytes, over all of its 32 x 32 tiles -- what
-    convert_remap takes as (tensor, lds_bytes).  Copies the map to the host once; luma_only: for Y800 outputs.  map: a tensor or array (H, W, 2) float32."""
+    convert_remap takes as (tensor, lds_bytes).  Copies the map to the host once; luma_only: for Y800 outputs.  map: a tensor or array (H, W, 2) float32.
+    bicubic: the hint of convert_remap_bicubic, whose tiles stage the 4-tap halo too (tsvpp_remap_bicubic_lds_need)."""
     host = map.detach().cpu().numpy() if isinstance(map, torch.Tensor) else np.asarray(map)
     if host.dtype != np.float32 or host.ndim != 3 or host.shape[2] != 2:
         raise ValueError(f"a map is float32 (H, W, 2), not {host.dtype} {host.shape}")
     host = np.ascontiguousarray(host)
-    need = N.lib().tsvpp_remap_lds_need(host.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), 0, host.shape[1], host.shape[0], int(frame_w), int(frame_h), 1 if luma_only else 0)
+    fn = N.lib().tsvpp_remap_bicubic_lds_need if bicubic else N.lib().tsvpp_remap_lds_need
+    need = fn(host.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), 0, host.shape[1], host.shape[0], int(frame_w), int(frame_h), 1 if luma_only else 0)
     if need < 0:
         N.check(need)
     return need
@@ -1079,6 +1115,16 @@ def describe_mesh(params, frames, meshes, cell=(16, 16), remaps=None, border=Non
     return _describe_coord((N.lib().tsvpp_describe_mesh, N.lib().tsvpp_describe_mesh_tensor), items, params, frames, border, aligned_outputs, dtype, mean, std)
 
 
+def describe_mesh_bicubic(params, frames, meshes, cell=(16, 16), remaps=None, border=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_mesh_bicubic of this request would launch, as a dict (tsvpp_describe_mesh_bicubic: describe_mesh's keys, mode mesh_bicubic) -- host logic
+    only, works without a GPU.  Arguments as describe_mesh."""
+    def items(p, recs):
+        ms = _normalize_meshes(meshes, cell, p.dst_width, p.dst_height)
+        rs = _normalize_remaps(remaps, len(recs), len(ms))
+        return len(ms), ms, len(rs), rs
+    return _describe_coord(_describe_pair(N.lib().tsvpp_describe_mesh_bicubic), items, params, frames, border, aligned_outputs, dtype, mean, std)
+
+
 def _host_pairs(a, what):
     """a tensor or array (H, W, 2) float32 as a contiguous numpy array, and whether it came as a tensor"""
     host = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
@@ -1133,9 +1179,12 @@ def mesh_error(xy, mesh, cell):
     return worst.value
 
 
-def mesh_lds_hint(mesh, dst_size, cell, frame_w, frame_h, luma_only=False):
+def mesh_lds_hint(mesh, dst_size, cell, frame_w, frame_h, luma_only=False, bicubic=False):
     """The LDS hint of a mesh for a dst_size = (dst_w, dst_h) output on a frame_w x frame_h frame (tsvpp_mesh_lds_need: remap_lds_hint of mesh_expand(mesh)) --
-    what convert_mesh takes as (tensor, lds_bytes).  Copies the mesh to the host once; luma_only: for Y800 outputs."""
+    what convert_mesh takes as (tensor, lds_bytes).  Copies the mesh to the host once; luma_only: for Y800 outputs.  bicubic: the hint of convert_mesh_bicubic
+    (remap_lds_hint(mesh_expand(mesh), bicubic=True))."""
+    if bicubic:
+        return remap_lds_hint(mesh_expand(_host_pairs(mesh, "mesh"), dst_size, cell), frame_w, frame_h, luma_only, bicubic=True)
     lw, lh = _cell_logs(cell)
     w, h = (int(v) for v in dst_size)
     hm = _host_pairs(mesh, "mesh")

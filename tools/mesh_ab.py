@@ -2,7 +2,7 @@
 """A/B: lens undistortion of n 1080p frames (pitch 2048) through a barrel warp given as a control grid -- tsvpp_convert_mesh against tsvpp_convert_remap of the
 expanded mesh, which computes the same bits -- on one stream of one MI355X.
 
-    python tools/mesh_ab.py [--out profiles/mesh_ab.txt] [--repeats 20] [--ns 1,4,8,32]
+    python tools/mesh_ab.py [--bicubic] [--out profiles/mesh_ab.txt] [--repeats 20] [--ns 1,4,8,32]
 
 Protocol (tools/remap_ab.py's): every leg is timed with HIP events around blocks of back-to-back calls on ONE stream, frames and outputs rotating through pools of
 more than 256 MiB each (the MI355X has a 256 MiB last-level cache); the legs' blocks alternate, per leg the median of `repeats` blocks, with the blocks' min .. max.  Before it is timed every
@@ -14,7 +14,11 @@ leg is parity-checked (first and last output of a call) against tests/mesh_util.
   (dn)   (d) with one distinct dense map per output: what that stabiliser sends today (n copies of E(mesh), 16.6 MB each at 1080p)
 "bytes" = what a call must move per output: the mesh (a, a32, an) or the dense map (d), the source bounding boxes of its tiles (tsvpp_remap_footprint of E(mesh):
 luma + chroma bytes) and the output; "roofline" = (a)'s bytes / time as a fraction of 8 TB/s.  Expectation: (a) is not slower than (d) by more than the spread
-(max - min) of (d)'s own blocks, in any row."""
+(max - min) of (d)'s own blocks, in any row.
+With --bicubic (default --out profiles/mesh_bicubic_ab.txt) every leg samples BICUBIC: the mesh legs are tsvpp_convert_mesh_bicubic, the dense legs
+tsvpp_convert_remap_bicubic, hints and footprints are the BICUBIC ones, the model is tests/remap_bicubic_util.py's; the elements are tools/remap_ab.py's (fp32
+planar; fp16 with ImageNet mean / std through the spec), and a leg (b), tsvpp_convert_batch to fp32 planar + grid_sample(mode="bicubic") over E(mesh) with the grid
+built outside the timing, is timed beside them (b / a)."""
 import argparse
 import ctypes
 import os
@@ -23,6 +27,7 @@ import sys
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tensor-stream_amd"), os.path.join(ROOT, "tests")):
@@ -30,6 +35,7 @@ for p in (ROOT, os.path.join(ROOT, "tensor-stream_amd"), os.path.join(ROOT, "tes
         sys.path.insert(0, p)
 
 import mesh_util as MU  # noqa: E402  (the model of the mesh's coordinate contract, and the barrel mesh)
+import remap_bicubic_util as RB  # noqa: E402  (... with --bicubic)
 import remap_util as RU  # noqa: E402  (the model of everything behind the coordinate)
 import tensor_stream as ts  # noqa: E402
 import tensor_util as T  # noqa: E402
@@ -38,9 +44,10 @@ from tensor_stream import _native as N  # noqa: E402
 
 W, H, PITCH = 1920, 1080, 2048
 HBM = 8e12
-BILINEAR, BGR24, PLANAR, MERGED = 1, 2, 0, 1
+BILINEAR, BICUBIC, BGR24, PLANAR, MERGED = 1, 2, 2, 0, 1
 WORKLOADS = [("undistort 1080p -> 1920x1080", (1920, 1080)), ("undistort + resize 1080p -> 640x640", (640, 640))]
 ELEMENTS = [("BGR24 planar fp32", PLANAR, True, 4), ("BGR24 merged uint8", MERGED, False, 1)]
+ELEMENTS_BICUBIC = [ELEMENTS[0], ("BGR24 planar fp16, ImageNet mean / std", PLANAR, True, 2)]  # (elem 2: through the tensor spec)
 
 
 def timed(fns, stream, repeats, iters, warm):
@@ -65,13 +72,13 @@ def timed(fns, stream, repeats, iters, warm):
     return blocks
 
 
-def footprint_bytes(L, xy, dst):
+def footprint_bytes(L, xy, dst, cubic=False):
     """per output: the source bounding boxes of all tiles, both planes"""
     total = 0
     out8 = (ctypes.c_int32 * 8)()
     ptr = xy.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
     for (j0, j1, i0, i1) in RU.tiles(dst[0], dst[1], True):
-        assert L.tsvpp_remap_footprint(ptr, 0, dst[0], dst[1], W, H, j0, j1, i0, i1, out8) == 0
+        assert (L.tsvpp_remap_bicubic_footprint if cubic else L.tsvpp_remap_footprint)(ptr, 0, dst[0], dst[1], W, H, j0, j1, i0, i1, out8) == 0
         f = list(out8)
         total += (f[1] - f[0] + 1) * (f[3] - f[2] + 1) + 2 * (f[5] - f[4] + 1) * (f[7] - f[6] + 1)
     return total
@@ -79,11 +86,14 @@ def footprint_bytes(L, xy, dst):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_ab.txt"))
+    ap.add_argument("--bicubic", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--ns", default="1,4,8,32")
     ap.add_argument("--frames", type=int, default=96)
     a = ap.parse_args()
+    cubic = a.bicubic
+    a.out = a.out or os.path.join(ROOT, "profiles", "mesh_bicubic_ab.txt" if cubic else "mesh_ab.txt")
     assert torch.cuda.is_available(), "tools/mesh_ab.py measures on the GPU: there is nothing to report without one"
     O.build()
     L = N.lib()
@@ -113,28 +123,37 @@ def main():
              "# (a32) = (a) at cell 32 x 32   (an) = (a) with one distinct mesh per output (the stabiliser's call)   (dn) = (d) with one distinct dense map per output",
              "# us per call, [min .. max of the blocks]; MB = bytes a call must move per output (mesh or map + tile footprints + output); roofline = (a)'s bytes / time / 8 TB/s;",
              "# ok = (a) <= (d) + (max - min of (d)'s blocks)"]
+    if cubic:
+        lines.insert(1, "# --bicubic: the mesh legs = tsvpp_convert_mesh_bicubic, the dense legs = tsvpp_convert_remap_bicubic, BICUBIC hints; (b) = tsvpp_convert_batch to fp32 planar + "
+                        "grid_sample(mode=bicubic) over E(mesh) (+ normalise + .half())")
+        p_full = ts.FrameParameters(pixel_format=BGR24, planes_pos=PLANAR, normalization=True).parameters
     all_ok = True
     virtual = {}
     for wname, dst in WORKLOADS:
         mesh = {c: MU.barrel(dst[0], dst[1], (c, c), W, H) for c in (16, 32)}
         dense = {c: MU.expand(mesh[c], dst[0], dst[1], (c, c)) for c in (16, 32)}
-        hint = {c: ts.mesh_lds_hint(mesh[c], dst, (c, c), W, H) for c in (16, 32)}
-        assert hint[16] == ts.remap_lds_hint(dense[16], W, H)
+        hint = {c: ts.mesh_lds_hint(mesh[c], dst, (c, c), W, H, bicubic=cubic) for c in (16, 32)}
+        assert hint[16] == ts.remap_lds_hint(dense[16], W, H, bicubic=cubic)
         d_mesh = {c: torch.from_numpy(mesh[c]).to(dev) for c in (16, 32)}
         d_dense = torch.from_numpy(dense[16]).to(dev)
-        foot = {c: footprint_bytes(L, dense[c], dst) for c in (16, 32)}
+        foot = {c: footprint_bytes(L, dense[c], dst, cubic) for c in (16, 32)}
+        d64 = d_dense.double() if cubic else None  # leg (b)'s normalised grid: the inverse of remap_from_grid
+        grid1 = cubic and torch.stack(((2 * d64[..., 0] + 1) / W - 1, (2 * d64[..., 1] + 1) / H - 1), dim=-1).float()[None]
         err = ts.mesh_error(RU.barrel(dst[0], dst[1], W, H), mesh[16], (16, 16)), ts.mesh_error(RU.barrel(dst[0], dst[1], W, H), mesh[32], (32, 32))
-        for ename, planes, norm, elem in ELEMENTS:
-            p = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=BILINEAR, pixel_format=BGR24, planes_pos=planes, normalization=norm).parameters
+        for ename, planes, norm, elem in (ELEMENTS_BICUBIC if cubic else ELEMENTS):
+            half = elem == 2
+            spec = ts.tensor_spec(dtype=torch.float16, mean=T.IMAGENET[0], std=T.IMAGENET[1]) if half else None
+            sref = None if spec is None else ctypes.byref(spec)
+            p = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=BICUBIC if cubic else BILINEAR, pixel_format=BGR24, planes_pos=planes, normalization=norm).parameters
             out_bytes = 3 * dst[0] * dst[1] * elem
             mb = {"a": mesh[16].nbytes + foot[16] + out_bytes, "d": dense[16].nbytes + foot[16] + out_bytes, "a32": mesh[32].nbytes + foot[32] + out_bytes}
             lines += ["", f"## {wname}, {ename}   (hint {hint[16]} bytes; MB per output: (a) {mb['a'] / 1e6:.2f}, (d) {mb['d'] / 1e6:.2f}, (a32) {mb['a32'] / 1e6:.2f}; "
                           f"the mesh is within {err[0]:.4f} px of the dense barrel map at cell 16, {err[1]:.4f} px at cell 32)",
                       f"{'n':>3} | {'(a) us':>9} {'spread':>19} {'roofline':>8} | {'(d) us':>9} {'spread':>19} | {'(a32) us':>9} {'spread':>19} | {'(an) us':>9} {'spread':>19} | "
-                      f"{'(dn) us':>9} {'spread':>19} | {'a / d':>6} {'a32 / a':>7} {'an / a':>6} {'an / dn':>7} | ok"]
+                      f"{'(dn) us':>9} {'spread':>19} | " + (f"{'(b) us':>9} {'spread':>19} {'b / a':>6} | " if cubic else "") + f"{'a / d':>6} {'a32 / a':>7} {'an / a':>6} {'an / dn':>7} | ok"]
             for n in [int(v) for v in a.ns.split(",")]:
                 sets = max(2, (257 << 20) // (n * out_bytes) + 1)
-                pool = [vpp._alloc(p, dst[0], dst[1], n) for _ in range(sets)]
+                pool = [vpp._alloc(p, dst[0], dst[1], n, torch.float16 if half else None) for _ in range(sets)]
                 out_arrs = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in pool]
                 calls = max(1, a.frames // n)
                 frame_arrs = [(N.NV12 * n)(*[frames[(c * n + i) % a.frames] for i in range(n)]) for c in range(calls)]
@@ -151,13 +170,19 @@ def main():
 
                 def leg_mesh(meshes, n_meshes, remaps):
                     def fn(k):
-                        if L.tsvpp_convert_mesh(vpp._ctx, n, frame_arrs[k % calls], n_meshes, meshes, n, remaps, pref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
+                        if cubic:
+                            if L.tsvpp_convert_mesh_bicubic(vpp._ctx, n, frame_arrs[k % calls], n_meshes, meshes, n, remaps, pref, sref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
+                                raise RuntimeError("tsvpp_convert_mesh_bicubic failed")
+                        elif L.tsvpp_convert_mesh(vpp._ctx, n, frame_arrs[k % calls], n_meshes, meshes, n, remaps, pref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
                             raise RuntimeError("tsvpp_convert_mesh failed")
                     return fn
 
                 def leg_dense(maps, n_maps, remaps):
                     def fn(k):
-                        if L.tsvpp_convert_remap(vpp._ctx, n, frame_arrs[k % calls], n_maps, maps, n, remaps, pref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
+                        if cubic:
+                            if L.tsvpp_convert_remap_bicubic(vpp._ctx, n, frame_arrs[k % calls], n_maps, maps, n, remaps, pref, sref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
+                                raise RuntimeError("tsvpp_convert_remap_bicubic failed")
+                        elif L.tsvpp_convert_remap(vpp._ctx, n, frame_arrs[k % calls], n_maps, maps, n, remaps, pref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
                             raise RuntimeError("tsvpp_convert_remap failed")
                     return fn
 
@@ -166,8 +191,24 @@ def main():
                     key = (c, dst, i)
                     if key not in virtual:
                         y, uv = host_frame(i)
-                        virtual[key] = RU.virtual_frame_from_map(y, uv, W, H, dense[c])
-                    return O.convert(virtual[key][0], virtual[key][1], fourcc=BGR24, planes=planes, normalization=norm)[0].ravel().view(np.uint8)
+                        virtual[key] = (RB if cubic else RU).virtual_frame_from_map(y, uv, W, H, dense[c])
+                    q = O.convert(virtual[key][0], virtual[key][1], fourcc=BGR24, planes=planes, normalization=norm)[0]
+                    return T.expected(q, 3, T.IMAGENET, T.F16) if half else q.ravel().view(np.uint8)
+
+                if cubic:  # leg (b): not this library's arithmetic, so no parity; timed with the others
+                    full_sets = max(2, (257 << 20) // (n * 3 * W * H * 4) + 1)
+                    full = [torch.empty((n, 3, H, W), dtype=torch.float32, device=dev) for _ in range(full_sets)]
+                    full_arrs = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in full]
+                    grid = grid1.expand(n, -1, -1, -1)
+                    if half:
+                        t_mean = torch.tensor(list(spec.mean), dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+                        t_scale = torch.tensor(list(spec.scale), dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+
+                    def leg_b(k):
+                        if L.tsvpp_convert_batch(vpp._ctx, n, frame_arrs[k % calls], ctypes.byref(p_full), full_arrs[k % full_sets], raw) != 0:
+                            raise RuntimeError("tsvpp_convert_batch failed")
+                        x = F.grid_sample(full[k % full_sets], grid, mode="bicubic", padding_mode="border", align_corners=False)
+                        return x.sub(t_mean).mul(t_scale).half() if half else x
 
                 iters = max(2, 40 // n) if dst[0] > 1000 else max(4, 160 // n)
                 with torch.cuda.stream(stream):
@@ -181,18 +222,21 @@ def main():
                         for i in sorted({0, n - 1}):
                             if not np.array_equal(T.bits(pool[0][i]), expected(c, i)):
                                 raise SystemExit(f"PARITY FAILURE: leg ({leg}) {wname} {ename} n={n} output {i}")
-                    res = timed({leg: fn for leg, fn, _ in legs}, stream, a.repeats, iters, warm=max(3, iters // 2))
+                    res = timed({**{leg: fn for leg, fn, _ in legs}, **({"b": leg_b} if cubic else {})}, stream, a.repeats, iters, warm=max(3, iters // 2))
                 m = {k: statistics.median(v) for k, v in res.items()}
                 sp = lambda v: f"{min(v):9.2f}..{max(v):<8.2f}"  # noqa: E731
                 ok = m["a"] <= m["d"] + (max(res["d"]) - min(res["d"]))
                 all_ok = all_ok and ok
+                b_cols = f"{m['b']:9.2f} {sp(res['b'])} {m['b'] / m['a']:6.2f} | " if cubic else ""
                 lines.append(f"{n:>3} | {m['a']:9.2f} {sp(res['a'])} {n * mb['a'] / (m['a'] * 1e-6) / HBM:8.4f} | {m['d']:9.2f} {sp(res['d'])} | {m['a32']:9.2f} {sp(res['a32'])} | "
-                             f"{m['an']:9.2f} {sp(res['an'])} | {m['dn']:9.2f} {sp(res['dn'])} | {m['a'] / m['d']:6.2f} {m['a32'] / m['a']:7.2f} {m['an'] / m['a']:6.2f} {m['an'] / m['dn']:7.2f} | "
+                             f"{m['an']:9.2f} {sp(res['an'])} | {m['dn']:9.2f} {sp(res['dn'])} | {b_cols}{m['a'] / m['d']:6.2f} {m['a32'] / m['a']:7.2f} {m['an'] / m['a']:6.2f} {m['an'] / m['dn']:7.2f} | "
                              f"{'yes' if ok else 'NO'}")
                 print(lines[-1], flush=True)
                 del pool, out_arrs, copies, dense_copies
+                if cubic:
+                    del full, full_arrs
                 torch.cuda.empty_cache()
-    lines += ["", "# parity: every leg bit-exact against tests/mesh_util.py's E(mesh) through tests/remap_util.py's model and the CPU oracle, first and last output of call 0, before timing",
+    lines += ["", f"# parity: every leg{' but (b)' if cubic else ''} bit-exact against tests/mesh_util.py's E(mesh) through tests/{'remap_bicubic_util' if cubic else 'remap_util'}.py's model and the CPU oracle, first and last output of call 0, before timing",
               f"# expectation ((a) not slower than (d) beyond the spread of (d)'s blocks, in every row): {'met' if all_ok else 'NOT MET'}"]
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

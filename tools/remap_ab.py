@@ -2,7 +2,7 @@
 """A/B: lens undistortion of n 1080p frames (pitch 2048) through ONE shared barrel map -- the fused tsvpp_convert_remap against what a user does without it -- on
 one stream, timed with HIP events.
 
-    python tools/remap_ab.py [--out profiles/remap_ab.txt] [--repeats 20] [--ns 1,4,8,32]
+    python tools/remap_ab.py [--bicubic] [--out profiles/remap_ab.txt] [--repeats 20] [--ns 1,4,8,32]
 
 Protocol (tools/warp_ab.py's): per (workload, element, n, leg) a warm-up, then `repeats` timed blocks between two events on the stream; the figure is the MEDIAN
 block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next n frames of a pool of 96 distinct 1080p frames (318 MiB) and
@@ -17,6 +17,10 @@ Workloads: 1080p -> 1920 x 1080 (undistort) and 1080p -> 640 x 640 (undistort + 
          the equivalent normalised grid, built once outside the timing; (x - mean) * scale -> .half() for the fp16 rows.  NOT this library's arithmetic (it
          blends RGB, not NV12): the mean absolute difference to (a) is printed as a check of the geometry
   (w)    one tsvpp_convert_warp[_tensor] call with the scale-only matrix of the same sizes: the cost floor without a map
+With --bicubic (default --out profiles/map_bicubic_ab.txt) every leg samples BICUBIC: (a), (a40), (ag) are tsvpp_convert_remap_bicubic with the hint of
+tsvpp_remap_bicubic_lds_need, (b) is grid_sample(mode="bicubic"), (w) is tsvpp_convert_warp_bicubic, and a leg (c), the BILINEAR map call on the same map with its
+own hint, is timed beside them (a / c); the footprints are tsvpp_remap_bicubic_footprint's.  The condition is then stricter: (b) - (a) exceeds the spread
+(max - min) of (b)'s blocks in every row.
 "bytes" of (a) = what it must move: the map (8 bytes per output pixel, counted once per OUTPUT although the n outputs share one map -- after the first output the
 map is re-read from cache) + the source bounding boxes of its tiles (tsvpp_remap_footprint: luma + chroma bytes) + the outputs; "roofline" = bytes / time as a
 fraction of 8 TB/s.  The one condition: (a) is faster than (b) in every row."""
@@ -35,16 +39,18 @@ for p in (ROOT, os.path.join(ROOT, "tensor-stream_amd"), os.path.join(ROOT, "tes
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import remap_bicubic_util as RB  # noqa: E402  (... of the BICUBIC map call's)
 import remap_util as RU  # noqa: E402  (the model of the remap's contract, and the barrel map)
 import tensor_stream as ts  # noqa: E402
 import tensor_util as T  # noqa: E402  (the expected bits of the tensor entry points)
+import warp_bicubic_util as WB  # noqa: E402
 import warp_util as WU  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from tensor_stream import _native as N  # noqa: E402
 
 W, H, PITCH = 1920, 1080, 2048
 HBM = 8e12
-BILINEAR, BGR24, PLANAR = 1, 2, 0
+BILINEAR, BICUBIC, BGR24, PLANAR = 1, 2, 2, 0
 WORKLOADS = [("undistort 1080p -> 1920x1080", (1920, 1080)), ("undistort + resize 1080p -> 640x640", (640, 640))]
 ELEMENTS = [("BGR24 planar fp32", None, None), ("BGR24 planar fp16, ImageNet mean / std", T.F16, T.IMAGENET)]
 
@@ -67,13 +73,13 @@ def timed(fn, stream, repeats, iters, warm):
     return blocks
 
 
-def must_move(L, xy, dst, elem):
+def must_move(L, xy, dst, elem, cubic=False):
     """bytes leg (a) must move per output: the map, per tile the source bounding box in both planes, the output"""
     total = 8 * dst[0] * dst[1] + 3 * dst[0] * dst[1] * elem
     out8 = (ctypes.c_int32 * 8)()
     ptr = xy.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
     for (j0, j1, i0, i1) in RU.tiles(dst[0], dst[1], True):
-        assert L.tsvpp_remap_footprint(ptr, 0, dst[0], dst[1], W, H, j0, j1, i0, i1, out8) == 0
+        assert (L.tsvpp_remap_bicubic_footprint if cubic else L.tsvpp_remap_footprint)(ptr, 0, dst[0], dst[1], W, H, j0, j1, i0, i1, out8) == 0
         f = list(out8)
         total += (f[1] - f[0] + 1) * (f[3] - f[2] + 1) + 2 * (f[5] - f[4] + 1) * (f[7] - f[6] + 1)
     return total
@@ -81,11 +87,14 @@ def must_move(L, xy, dst, elem):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "remap_ab.txt"))
+    ap.add_argument("--bicubic", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--ns", default="1,4,8,32")
     ap.add_argument("--frames", type=int, default=96)
     a = ap.parse_args()
+    cubic = a.bicubic
+    a.out = a.out or os.path.join(ROOT, "profiles", "map_bicubic_ab.txt" if cubic else "remap_ab.txt")
     assert torch.cuda.is_available(), "tools/remap_ab.py measures on the GPU: there is nothing to report without one"
     O.build()
     L = N.lib()
@@ -126,18 +135,21 @@ def main():
              "# (b) = tsvpp_convert_batch to fp32 planar + torch grid_sample (+ normalise + .half())   (w) = 1 x tsvpp_convert_warp, scale-only matrix: the floor without a map",
              "# us per call, [min .. max of the blocks]; roofline = bytes (a) must move (map once per output -- a shared map is re-read from cache -- + tile footprints + outputs) / time / 8 TB/s;",
              "# |b-a| = mean absolute difference of (b)'s result to (a)'s"]
+    if cubic:
+        lines.insert(1, "# --bicubic: (a) (a40) (ag) = tsvpp_convert_remap_bicubic, (b) = grid_sample(mode=bicubic), (w) = tsvpp_convert_warp_bicubic, (c) = tsvpp_convert_remap (BILINEAR) on the same map")
     faster = True
     virtual = {}
     for wname, dst in WORKLOADS:
         xy = RU.barrel(dst[0], dst[1], W, H)
         d_xy = torch.from_numpy(xy).to(dev)
-        hint = ts.remap_lds_hint(xy, W, H)
-        moved1 = {4: must_move(L, xy, dst, 4), 2: must_move(L, xy, dst, 2)}
+        hint = ts.remap_lds_hint(xy, W, H, bicubic=cubic)
+        moved1 = {4: must_move(L, xy, dst, 4, cubic), 2: must_move(L, xy, dst, 2, cubic)}
         m_scale = WU.scale_only(W, H, *dst)
         # the normalised grid of leg (b): the inverse of remap_from_grid, x = ((gx + 1) w - 1) / 2
         d64 = d_xy.double()
         grid1 = torch.stack(((2 * d64[..., 0] + 1) / W - 1, (2 * d64[..., 1] + 1) / H - 1), dim=-1).float()[None]
-        p = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=BILINEAR, pixel_format=BGR24, planes_pos=PLANAR, normalization=True).parameters
+        p = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=BICUBIC if cubic else BILINEAR, pixel_format=BGR24, planes_pos=PLANAR, normalization=True).parameters
+        p_lin = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=BILINEAR, pixel_format=BGR24, planes_pos=PLANAR, normalization=True).parameters
         for ename, dtype, spec_ms in ELEMENTS:
             tdt = torch.float32 if dtype is None else T.TORCH[dtype]
             elem = 4 if dtype is None else T.ESIZE[dtype]
@@ -147,7 +159,7 @@ def main():
                 t_scale = torch.tensor(list(spec.scale), dtype=torch.float32, device=dev).view(1, 3, 1, 1)
             lines += ["", f"## {wname}, {ename}   (hint {hint} bytes; {moved1[elem] / 1e6:.2f} MB per output)",
                       f"{'n':>3} | {'(a) us':>9} {'spread':>19} {'roofline':>8} | {'(a40) us':>9} {'spread':>19} | {'(ag) us':>9} {'spread':>19} | {'(b) us':>9} {'spread':>19} | "
-                      f"{'(w) us':>9} {'spread':>19} | {'b / a':>6} {'a / w':>6} {'a / ag':>6} {'a / a40':>7} | {'|b-a|':>7}"]
+                      f"{'(w) us':>9} {'spread':>19} | " + (f"{'(c) us':>9} {'spread':>19} {'a / c':>6} | " if cubic else "") + f"{'b / a':>6} {'a / w':>6} {'a / ag':>6} {'a / a40':>7} | {'|b-a|':>7}"]
             for n in [int(v) for v in a.ns.split(",")]:
                 out_bytes = 3 * dst[0] * dst[1] * elem
                 sets = max(2, (257 << 20) // (n * out_bytes) + 1)
@@ -162,12 +174,17 @@ def main():
                 warps = (N.Warp * n)(*[N.Warp(i, (ctypes.c_float * 6)(*m_scale)) for i in range(n)])
                 map_hint = (N.Map * 1)(N.Map(d_xy.data_ptr(), 0, hint))
                 map_plain = (N.Map * 1)(N.Map(d_xy.data_ptr(), 0, 0))
+                map_lin = cubic and (N.Map * 1)(N.Map(d_xy.data_ptr(), 0, ts.remap_lds_hint(xy, W, H)))  # (leg (c) only)
                 pref, sref, pfull = ctypes.byref(p), None if spec is None else ctypes.byref(spec), ctypes.byref(p_full)
                 grid = grid1.expand(n, -1, -1, -1)
                 last_b = [None]
 
                 def leg_remap(ctx, maps):
-                    if spec is None:
+                    if cubic:
+                        def fn(k):
+                            if L.tsvpp_convert_remap_bicubic(ctx, n, frame_arrs[k % calls], 1, maps, n, remaps, pref, sref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
+                                raise RuntimeError("tsvpp_convert_remap_bicubic failed")
+                    elif spec is None:
                         def fn(k):
                             if L.tsvpp_convert_remap(ctx, n, frame_arrs[k % calls], 1, maps, n, remaps, pref, -1, -1, -1, out_arrs[k % sets], raw) != 0:
                                 raise RuntimeError("tsvpp_convert_remap failed")
@@ -177,8 +194,19 @@ def main():
                                 raise RuntimeError("tsvpp_convert_remap_tensor failed")
                     return fn
 
-                def leg_w(k):
+                def leg_c(k):
+                    plin = ctypes.byref(p_lin)
                     if spec is None:
+                        sts = L.tsvpp_convert_remap(vpp._ctx, n, frame_arrs[k % calls], 1, map_lin, n, remaps, plin, -1, -1, -1, out_arrs[k % sets], raw)
+                    else:
+                        sts = L.tsvpp_convert_remap_tensor(vpp._ctx, n, frame_arrs[k % calls], 1, map_lin, n, remaps, plin, sref, -1, -1, -1, out_arrs[k % sets], raw)
+                    if sts != 0:
+                        raise RuntimeError("tsvpp_convert_remap failed")
+
+                def leg_w(k):
+                    if cubic:
+                        sts = L.tsvpp_convert_warp_bicubic(vpp._ctx, n, frame_arrs[k % calls], n, warps, pref, sref, -1, -1, -1, out_arrs[k % sets], raw)
+                    elif spec is None:
                         sts = L.tsvpp_convert_warp(vpp._ctx, n, frame_arrs[k % calls], n, warps, pref, -1, -1, -1, out_arrs[k % sets], raw)
                     else:
                         sts = L.tsvpp_convert_warp_tensor(vpp._ctx, n, frame_arrs[k % calls], n, warps, pref, sref, -1, -1, -1, out_arrs[k % sets], raw)
@@ -189,22 +217,25 @@ def main():
                     buf = full[k % full_sets]
                     if L.tsvpp_convert_batch(vpp._ctx, n, frame_arrs[k % calls], pfull, full_arrs[k % full_sets], raw) != 0:
                         raise RuntimeError("tsvpp_convert_batch failed")
-                    x = F.grid_sample(buf, grid, mode="bilinear", padding_mode="border", align_corners=False)
+                    x = F.grid_sample(buf, grid, mode="bicubic" if cubic else "bilinear", padding_mode="border", align_corners=False)
                     last_b[0] = x if spec is None else x.sub(t_mean).mul(t_scale).half()
 
                 def expected(leg, i):
                     """call 0: output i samples frame i of the pool"""
-                    key = ("w" if leg == "w" else "a", dst, i)
+                    key = (leg if leg in ("w", "c") else "a", dst, i)
                     if key not in virtual:
                         y, uv = host_frame(i)
-                        virtual[key] = WU.virtual_frame(y, uv, W, H, m_scale, *dst) if leg == "w" else RU.virtual_frame_from_map(y, uv, W, H, xy)
+                        if leg == "w":
+                            virtual[key] = (WB if cubic else WU).virtual_frame(y, uv, W, H, m_scale, *dst)
+                        else:
+                            virtual[key] = (RB if cubic and leg != "c" else RU).virtual_frame_from_map(y, uv, W, H, xy)
                     q = O.convert(virtual[key][0], virtual[key][1], fourcc=BGR24, planes=PLANAR, normalization=True)[0]
                     return q.ravel().view(np.uint8) if dtype is None else T.expected(q, 3, spec_ms, dtype)
 
                 res, diff_ba = {}, float("nan")
                 iters = max(2, 40 // n) if dst[0] > 1000 else max(4, 160 // n)
                 with torch.cuda.stream(stream):
-                    legs = (("a", leg_remap(vpp._ctx, map_hint)), ("a40", leg_remap(vpp._ctx, map_plain)), ("ag", leg_remap(vpp_gather._ctx, map_plain)), ("b", leg_b), ("w", leg_w))
+                    legs = (("a", leg_remap(vpp._ctx, map_hint)), ("a40", leg_remap(vpp._ctx, map_plain)), ("ag", leg_remap(vpp_gather._ctx, map_plain)), ("b", leg_b), ("w", leg_w)) + ((("c", leg_c),) if cubic else ())
                     for leg, fn in legs:
                         # parity first, on call 0 and output set 0
                         for t_ in pool:
@@ -222,16 +253,19 @@ def main():
                         res[leg] = timed(fn, stream, a.repeats, iters, warm=max(3, iters // 2))
                 m = {k: statistics.median(v) for k, v in res.items()}
                 sp = lambda v: f"{min(v):9.2f}..{max(v):<8.2f}"  # noqa: E731
+                c_cols = f"{m['c']:9.2f} {sp(res['c'])} {m['a'] / m['c']:6.2f} | " if cubic else ""
                 lines.append(f"{n:>3} | {m['a']:9.2f} {sp(res['a'])} {n * moved1[elem] / (m['a'] * 1e-6) / HBM:8.4f} | {m['a40']:9.2f} {sp(res['a40'])} | {m['ag']:9.2f} {sp(res['ag'])} | "
-                             f"{m['b']:9.2f} {sp(res['b'])} | {m['w']:9.2f} {sp(res['w'])} | {m['b'] / m['a']:6.2f} {m['a'] / m['w']:6.2f} {m['a'] / m['ag']:6.2f} {m['a'] / m['a40']:7.2f} | "
+                             f"{m['b']:9.2f} {sp(res['b'])} | {m['w']:9.2f} {sp(res['w'])} | {c_cols}{m['b'] / m['a']:6.2f} {m['a'] / m['w']:6.2f} {m['a'] / m['ag']:6.2f} {m['a'] / m['a40']:7.2f} | "
                              f"{diff_ba:7.4f}")
                 print(lines[-1], flush=True)
-                faster = faster and m["a"] < m["b"]
+                faster = faster and m["b"] - m["a"] > (max(res["b"]) - min(res["b"]) if cubic else 0.0)
                 del pool, out_arrs, full, full_arrs, last_b
                 torch.cuda.empty_cache()
-    lines += ["", "# parity: (a), (a40), (ag) bit-exact against tests/remap_util.py's model and (w) against tests/warp_util.py's, through the CPU oracle, first and last output of call 0, before "
+    models = ("tests/remap_bicubic_util.py's model, (c) against tests/remap_util.py's and (w) against tests/warp_bicubic_util.py's" if cubic else
+              "tests/remap_util.py's model and (w) against tests/warp_util.py's")
+    lines += ["", f"# parity: (a), (a40), (ag) bit-exact against {models}, through the CPU oracle, first and last output of call 0, before "
               "timing; (b) is torch's arithmetic",
-              f"# condition ((a) faster than (b) in every row): {'met' if faster else 'NOT MET'}"]
+              f"# condition ((a) faster than (b) in every row" + (", by more than the spread of (b)'s blocks" if cubic else "") + f"): {'met' if faster else 'NOT MET'}"]
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:

@@ -381,6 +381,46 @@ int tsvpp_convert_letterbox_area(tsvpp_ctx *ctx, int n, const tsvpp_nv12 *in, co
                                  const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
 int tsvpp_describe_letterbox_area(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n, const tsvpp_nv12 *in, const tsvpp_rect *rects,
                                   int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- 10-bit sources: tsvpp_convert_letterbox_p010 ----
+ * The letterbox call for P010 frames, what VCN / VA-API decoders deliver for HEVC Main10, VP9 profile 2 and 10-bit AV1: the NV12 layout in 16-bit little-endian
+ * words, the ten significant bits in the HIGH bits of each word (AV_PIX_FMT_P010LE: y = AVFrame::data[0], uv = data[1], pitches = linesize[0] / [1] in BYTES).
+ * One pair of entry points; `spec` null gives the flavours of tsvpp_convert_letterbox (RGB24 / BGR24 planar and merged, Y800; uint8 or fp32 by
+ * p->normalization), `spec` given those of tsvpp_convert_letterbox_tensor (planar and Y800 as fp32 / fp16 / bf16; merged: TSVPP_UNSUPPORTED).  Everything not
+ * named here is tsvpp_convert_letterbox's: rectangles and tsvpp_letterbox_rect, the evenness rules, TSVPP_MAX_LETTERBOX_P010 frames per launch with their records
+ * by value in the kernarg segment, no device allocation, no copy, no host synchronisation, legal under stream capture (a request of more than 32 frames takes one host
+ * array of n 32-byte records for the call; if that fails: TSVPP_ERROR), TSVPP_OPT_COLOR_G_TERM and the context's coefficient block honoured.  The reference has no 10-bit path: the arithmetic below IS the contract.
+ *   sample   s = word >> 6, 0..1023; the six low bits are ignored whatever they hold.
+ *   resize   NEAREST and BILINEAR.  Coordinates, weights, edge clamps, tap order and the fused multiply-adds are tsvpp_convert_letterbox's, bit for bit, evaluated
+ *            on the sample values as floats and truncated toward zero to an integer 0..1023; chroma by the same rule on the half-size grid.
+ *   colour   (RGB24 / BGR24) the library's expression with the two offsets scaled by four (exact): yl = max(0, Y - 4 y_offset), yv = yl * y_scale,
+ *            rv = fma(v_to_r, V - 4 c_offset, round_bias), bv alike, gv the G-term variant the context selects; each channel k = clamp(trunc(yv + term), 0, 1023).
+ *            Y800 keeps the luma sample, k = Y.
+ *   stored   p->normalization != 0: q = k / 1023, the correctly rounded fp32 quotient for all 1024 values of k.  p->normalization == 0: the byte
+ *            min(255, (k + 2) >> 2).  With a spec: cvt(dtype, (q - mean[c]) * scale[c]), as tsvpp_convert_letterbox_tensor words it.
+ *   pad      pad_y / pad_u / pad_v are one P010 SAMPLE each, 0..1023 -- (64, 512, 512) is black, (456, 512, 512) gray 114 -- and go through the same colour
+ *            expression and store as every sample.
+ * Status, decided before any device is touched (the describe call returns the same one): tsvpp_convert_letterbox's, in its order, with TSVPP_ERROR also for a pitch
+ * below 2 * width bytes, an odd pitch and a pad component outside 0..1023 -- and, converting, for a plane pointer that is not 2-byte aligned -- and
+ * TSVPP_UNSUPPORTED also for BICUBIC (as for AREA and unknown resize types) and for a plane span (rows - 1) * pitch + 2 * width bytes (chroma: 2 * width bytes per
+ * row too) at or above TSVPP_SOURCE_SPAN_LIMIT; then, with a spec, rules 2 and 3 of the tensor entry points.
+ * tsvpp_describe_letterbox_p010 prints tsvpp_describe_letterbox's keys with "src=p010" in front of frames=, kernel=vpp_letterbox_p010<...> /
+ * vpp_letterbox_p010_tensor<...> and limit=32; lds= counts the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks).
+ * Not here, each a follow-up: BICUBIC and AREA on P010; P010 through tsvpp_convert, the ROI, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
+ * presets (the coefficient block already lets a caller set them); 10-bit or 16-bit integer outputs; merged tensors. */
+typedef struct tsvpp_p010 {
+    const uint16_t *y;  /* AVFrame::data[0]: one 16-bit word per luma sample */
+    const uint16_t *uv; /* AVFrame::data[1]: interleaved U, V words */
+    int32_t pitch_y;    /* BYTES, AVFrame::linesize[0]; 0 means 2 * width */
+    int32_t pitch_uv;   /* BYTES */
+    int32_t width, height;
+} tsvpp_p010;
+#define TSVPP_MAX_LETTERBOX_P010 32 /* frames per launch; more are split */
+int tsvpp_convert_letterbox_p010(tsvpp_ctx *ctx, int n, const tsvpp_p010 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */,
+                                 const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
+int tsvpp_describe_letterbox_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n, const tsvpp_p010 *in, const tsvpp_rect *rects,
+                                  int aligned_outputs, char *buf, size_t buf_len);
+
 /* DEBUG ONLY (tests), host only: tsvpp_roi_area_rows as tsvpp_convert_letterbox_area's kernel produces the rows -- the generator begun at the jump start of
  * (scale, first), the largest multiple of the pattern's period that is <= first (0 where the pattern does not close in 1 .. first), which *start receives.
  * Arguments, result and statuses as tsvpp_roi_area_rows. */

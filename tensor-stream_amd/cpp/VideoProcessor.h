@@ -144,6 +144,13 @@ public:
                              std::string consumerName);
     int ConvertLetterboxArea(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                              const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertLetterbox for 10-bit P010 frames (tsvpp_convert_letterbox_p010, include/tsvpp.h; AV_PIX_FMT_P010LE: data[0] / data[1] hold 16-bit words with the sample
+    // in the ten high bits, linesize[] stays in bytes): NEAREST and BILINEAR; (padY, padU, padV) is one P010 sample, each 0..1023 -- (64, 512, 512) is black.
+    // Plain, and with a tensor spec (null: the plain call).
+    int ConvertLetterboxP010(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                             std::string consumerName);
+    int ConvertLetterboxP010(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                             const tsvpp_tensor_spec *spec, std::string consumerName);
     // Boxes that each go to their OWN output size (tsvpp_convert_rois_sized, include/tsvpp.h; not in the reference): text lines of one height and their own widths,
     // the levels of a pyramid, the inputs of several heads behind one detector pass.  rois[i] carries the box and its dst_width x dst_height; deviceOuts[i] holds
     // tsvpp_rois_sized_bytes bytes.  options.resize.width and height must be 0 (the sizes are the boxes') and options.crop empty; options.resize.type is NEAREST,

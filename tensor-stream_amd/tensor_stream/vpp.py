@@ -360,6 +360,32 @@ class VideoProcessor:
         dtype / mean / std: as convert_letterbox (the same entry point with a tensor spec)."""
         return self._convert_letterbox(True, ys, uvs, params, pad, rects, out, width, height, tensor_spec(dtype, mean, std))
 
+    def convert_letterbox_p010(self, ys, uvs, params, pad=(64, 512, 512), rects=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_letterbox for 10-bit P010 frames (tsvpp_convert_letterbox_p010), what VCN / VA-API decoders deliver for HEVC Main10, VP9 profile 2 and 10-bit
+        AV1: planes of 16-bit words with the sample in the ten high bits.  ys / uvs: 3-D int16 or uint16 tensors (n, rows, pitch in words) or lists of 2-D
+        tensors; pad: (Y, U, V) as P010 samples, each 0..1023 ((64, 512, 512): black, (456, 512, 512): gray 114).  NEAREST and BILINEAR.  The samples keep their
+        ten bits through the resize and the colour conversion: fp32 outputs are k / 1023, uint8 outputs min(255, (k + 2) >> 2).  Everything else -- rects, out,
+        width / height, dtype / mean / std, the result (out, rects) -- as convert_letterbox."""
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        spec = tensor_spec(dtype, mean, std)
+        n = len(ys)
+        if n == 0:
+            raise RuntimeError("-3: convert_letterbox_p010 needs at least one frame")
+        widths, heights = _per_frame(width, n), _per_frame(height, n)
+        frames = (N.P010 * n)(*[_p010_frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(n)])
+        if out is None:
+            out = self._alloc_items(p, n, spec, "convert_letterbox_p010 needs an even, positive canvas size")
+        recs = None if rects is None else _rects(rects, n)
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        N.check(self._lib.tsvpp_convert_letterbox_p010(self._ctx, n, frames, ctypes.byref(p), None if spec is None else ctypes.byref(spec), recs, int(pad[0]), int(pad[1]),
+                                                       int(pad[2]), outs, stream))
+        if recs is None:
+            used = [letterbox_rect(frames[i].width, frames[i].height, p.dst_width, p.dst_height) for i in range(n)]
+        else:
+            used = [(r.left, r.top, r.width, r.height) for r in recs]
+        return out, used
+
     def _convert_letterbox(self, area, ys, uvs, params, pad, rects, out, width, height, spec):
         p = params.parameters if isinstance(params, FrameParameters) else params
         n = len(ys)
@@ -768,6 +794,30 @@ def describe_letterbox(params, frames, rects=None, aligned_outputs=True, dtype=N
         N.check(N.lib().tsvpp_describe_letterbox(ctypes.byref(p), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
     else:
         N.check(N.lib().tsvpp_describe_letterbox_tensor(ctypes.byref(p), ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def _p010_frame(y, uv, width, height):
+    """One P010 frame as a tsvpp_p010 record: 2-D int16 / uint16 device planes, pitches in bytes."""
+    for t in (y, uv):
+        if not t.is_cuda or t.element_size() != 2 or t.is_floating_point() or t.dim() != 2 or t.stride(1) != 1:
+            raise RuntimeError("-3: a P010 plane is a 2-D int16 / uint16 device tensor with unit column stride")
+    h = y.shape[0] if height is None else height
+    w = y.shape[1] if width is None else width
+    return N.P010(y.data_ptr(), uv.data_ptr(), 2 * y.stride(0), 2 * uv.stride(0), w, h)
+
+
+def describe_letterbox_p010(params, frames, rects=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_letterbox_p010 of this request would launch, as a dict (tsvpp_describe_letterbox_p010: describe_letterbox's keys with src = "p010") -- host
+    logic only, works without a GPU.  Arguments as describe_letterbox; pitches are in BYTES (0: 2 * width)."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = [N.P010(None, None, r.pitch_y, r.pitch_uv, r.width, r.height) for r in _geometry_records(frames)]
+    fr = (N.P010 * max(len(recs), 1))(*recs)
+    rc = None if rects is None else _rects(rects, len(recs))
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    N.check(N.lib().tsvpp_describe_letterbox_p010(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf,
+                                                  len(buf)))
     return _parse_selection(buf.value.decode())
 
 

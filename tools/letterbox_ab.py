@@ -6,6 +6,7 @@ tsvpp_convert_letterbox -- on one stream, timed with HIP events.
     python tools/letterbox_ab.py [--out profiles/letterbox_ab.txt] [--repeats 20] [--iters 30] [--ns 1,8,32]
     python tools/letterbox_ab.py --dtype f16 [--mean a,b,c] [--std a,b,c]     the tensor legs: tsvpp_convert_letterbox_tensor (see tensor_main; appends to profiles/tensor_ab.txt)
     python tools/letterbox_ab.py --area [--out profiles/letterbox_area_ab.txt]  tsvpp_convert_letterbox_area against the loop it replaces and the BILINEAR letterbox (see area_main)
+    python tools/letterbox_ab.py --p010 [--out profiles/letterbox_p010_ab.txt]  tsvpp_convert_letterbox_p010 against torch's narrowing to NV12 + the 8-bit letterbox call (see p010_main)
 
 Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the MEDIAN
 block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next n frames of a pool of 96 distinct frames (316 MB) and the next
@@ -352,6 +353,136 @@ def area_main(a):
     vpp.Close()
 
 
+P010_PITCH = 4096  # bytes, luma and chroma alike: beyond 2 * 1920
+
+
+def p010_main(a):
+    """tsvpp_convert_letterbox_p010, same protocol (one stream, sources and canvases rotating through more than 256 MiB, median of the blocks with their spread, every
+    leg parity-checked, bit for bit, on the first canvas set BEFORE it is timed and on the last one it wrote): 1080p P010 frames at a pitch of 4096 bytes into
+    640 x 640, BILINEAR, n = 1, 8, 32, in three flavours.
+      (a) one tsvpp_convert_letterbox_p010 call, pad (456, 512, 512): parity against tests/p010_util.py, the contract's numpy restatement
+      (b) what a caller does without it: torch `>> 8` and a narrowing copy of both planes into NV12 buffers (four kernels, the n frames of a call at once) on the same
+          stream, then tsvpp_convert_letterbox / _tensor, pad (114, 128, 128): parity against the CPU oracle on the narrowed frame
+      (c) the 8-bit call of (b) alone on frames narrowed beforehand: the cost floor of the 8-bit path (it reads half the source bytes of (a))"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import p010_util as M
+    import tensor_util as T
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    ns = [int(v) for v in a.ns.split(",")]
+    words = P010_PITCH // 2
+    nframes = max(a.frames, -(-(280 << 20) // (P010_PITCH * H * 3 // 2)))
+    nframes = (nframes + 31) // 32 * 32
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    ys16 = torch.randint(-32768, 32768, (nframes, H, words), dtype=torch.int16, device=dev, generator=gen)
+    uvs16 = torch.randint(-32768, 32768, (nframes, H // 2, words), dtype=torch.int16, device=dev, generator=gen)
+    ys8 = torch.bitwise_right_shift(ys16, 8).to(torch.uint8)  # the narrowed frames of (c); (b) rewrites them, with the same bytes
+    uvs8 = torch.bitwise_right_shift(uvs16, 8).to(torch.uint8)
+    tmp_y, tmp_uv = torch.empty_like(ys16[:max(ns)]), torch.empty_like(uvs16[:max(ns)])
+    fr16 = [N.P010(ys16[k].data_ptr(), uvs16[k].data_ptr(), P010_PITCH, P010_PITCH, W, H) for k in range(nframes)]
+    fr8 = [N.NV12(ys8[k].data_ptr(), uvs8[k].data_ptr(), words, words, W, H) for k in range(nframes)]
+    rect = ts.letterbox_rect(W, H, CW, CH)
+    pad10 = (4 * PAD[0], 4 * PAD[1], 4 * PAD[2])
+    lines = [f"# tools/letterbox_ab.py --p010: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, {nframes} 1080p P010 frames at a pitch of {P010_PITCH} bytes "
+             f"({nframes * P010_PITCH * H * 3 // 2 >> 20} MiB) -> 640x640 BILINEAR, median of {a.repeats} blocks of {a.iters} iterations, one stream, canvases rotating through > 256 MiB",
+             "# (a) = 1 x tsvpp_convert_letterbox_p010   (b) = torch >> 8 + narrowing copy of both planes into NV12 buffers, then the 8-bit letterbox call   "
+             "(c) = the 8-bit letterbox call alone on frames narrowed beforehand", "# us per call, [min .. max of the blocks]"]
+    verdicts = []
+    for fname, fcc, planes, norm, dtype in AREA_FLAVOURS:
+        p = ts.FrameParameters(width=CW, height=CH, resize_type=1, pixel_format=fcc, planes_pos=planes, normalization=norm).parameters
+        spec = ts.tensor_spec(dtype=T.TORCH[dtype], mean=IMAGENET[0], std=IMAGENET[1]) if dtype else None
+        tdt = T.TORCH[dtype] if dtype else None
+        canvas_bytes = 3 * CW * CH * (T.ESIZE[dtype] if dtype else (4 if norm else 1))
+        d = ts.describe_letterbox_p010(ts.FrameParameters(width=CW, height=CH, resize_type=1, pixel_format=fcc, planes_pos=planes, normalization=norm), (W, H, P010_PITCH),
+                                       **(dict(dtype=tdt, mean=IMAGENET[0], std=IMAGENET[1]) if dtype else {}))
+        lines += ["", f"## {fname}: kernel={d['kernel']} lds={d['lds']} staged={d['staged']}",
+                  f"{'n':>3} | {'(a) us':>9} {'spread':>19} | {'(b) us':>9} {'spread':>19} | {'(c) us':>9} {'spread':>19} | {'b / a':>6} {'a / c':>6}"]
+        refs = {}
+
+        def reference(f, ten):
+            if (f, ten) not in refs:
+                if ten:
+                    y, uv = ys16[f].cpu().numpy().view(np.uint16), uvs16[f].cpu().numpy().view(np.uint16)
+                    k = M.channels(*M.virtual_frame(y, uv, W, H, rect, (CW, CH), M.BILINEAR, pad10), fcc)
+                    refs[(f, ten)] = T.expected(M.quotient(k), 3, IMAGENET, dtype) if dtype else M.stored(k, planes, norm)
+                else:
+                    q = expected_geo(ys8[f].cpu().numpy(), uvs8[f].cpu().numpy(), W, rect, (CW, CH), 1, fcc, planes, norm)
+                    refs[(f, ten)] = T.expected(q, 3, IMAGENET, dtype) if dtype else q.ravel().view(np.uint8)
+            return refs[(f, ten)]
+
+        for n in ns:
+            sets = max(2, (300 << 20) // (n * canvas_bytes) + 1)
+            pool = [vpp._alloc(p, CW, CH, n, tdt) for _ in range(sets)]
+            groups = nframes // n
+            arr16 = [(N.P010 * n)(*fr16[g * n:(g + 1) * n]) for g in range(groups)]
+            arr8 = [(N.NV12 * n)(*fr8[g * n:(g + 1) * n]) for g in range(groups)]
+            out_arrs = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in pool]
+            pref, sref, ctx = ctypes.byref(p), (ctypes.byref(spec) if dtype else None), vpp._ctx
+
+            def leg_a(k):
+                if L.tsvpp_convert_letterbox_p010(ctx, n, arr16[k % groups], pref, sref, None, pad10[0], pad10[1], pad10[2], out_arrs[k % sets], raw) != 0:
+                    raise RuntimeError("tsvpp_convert_letterbox_p010 failed")
+
+            def leg_c(k):
+                if dtype:
+                    sts = L.tsvpp_convert_letterbox_tensor(ctx, n, arr8[k % groups], pref, sref, None, PAD[0], PAD[1], PAD[2], out_arrs[k % sets], raw)
+                else:
+                    sts = L.tsvpp_convert_letterbox(ctx, n, arr8[k % groups], pref, None, PAD[0], PAD[1], PAD[2], out_arrs[k % sets], raw)
+                if sts != 0:
+                    raise RuntimeError("the 8-bit letterbox call failed")
+
+            def leg_b(k):
+                g = k % groups
+                torch.bitwise_right_shift(ys16[g * n:(g + 1) * n], 8, out=tmp_y[:n])
+                ys8[g * n:(g + 1) * n].copy_(tmp_y[:n])
+                torch.bitwise_right_shift(uvs16[g * n:(g + 1) * n], 8, out=tmp_uv[:n])
+                uvs8[g * n:(g + 1) * n].copy_(tmp_uv[:n])
+                leg_c(k)
+
+            def parity(leg, last):
+                got = pool[last % sets]
+                for i in range(n):
+                    if not np.array_equal(T.bits(got[i]), reference((last % groups) * n + i, leg == "a")):
+                        raise SystemExit(f"PARITY FAILURE: leg ({leg}) {fname} n={n} canvas {i}")
+
+            res = {}
+            with torch.cuda.stream(stream):
+                for leg, fn in (("a", leg_a), ("b", leg_b), ("c", leg_c)):
+                    for t in pool:
+                        t.zero_()
+                    fn(0)  # parity first, on canvas set 0, then the timing (and parity once more on the last set written)
+                    stream.synchronize()
+                    parity(leg, 0)
+                    blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(5, a.iters // 2))
+                    parity(leg, last)
+                    res[leg] = blocks
+            m = {k: statistics.median(v) for k, v in res.items()}
+            sp = lambda v: f"{min(v):9.2f}..{max(v):<9.2f}"
+            lines.append(f"{n:>3} | " + " | ".join(f"{m[k]:9.2f} {sp(res[k])}" for k in "abc") + f" | {m['b'] / m['a']:6.2f} {m['a'] / m['c']:6.2f}")
+            print(lines[-1], flush=True)
+            if n >= 8:
+                spread = max(res["b"]) - min(res["b"])
+                verdicts.append((m["b"] - m["a"] > spread, f"{fname}, n = {n}: (b) - (a) = {m['b'] - m['a']:+.2f} us, spread of (b) {spread:.2f} us"))
+            del pool
+            torch.cuda.empty_cache()
+    lines += ["", "# parity: (a) bit-exact against tests/p010_util.py, (b) and (c) against the CPU oracle on the narrowed frames (fp16: tests/tensor_util.py on either), on the "
+              "first and on the last canvas set a leg wrote", "# expectation ((a) faster than (b) at n = 8 and n = 32 by more than the spread of (b)'s own blocks):"]
+    lines += [f"#   {'met    ' if ok else 'NOT MET'}  {text}" for ok, text in verdicts]
+    lines.append(f"# expectation as a whole: {'met' if all(ok for ok, _ in verdicts) else 'NOT MET'}")
+    lines.append("# unmeasured: the staged / gathered split under a larger LDS budget, the kernel's own time from a trace")
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -363,10 +494,13 @@ def main():
     ap.add_argument("--mean", default="0.485,0.456,0.406", help="per stored channel (with --dtype)")
     ap.add_argument("--std", default="0.229,0.224,0.225", help="per stored channel (with --dtype); the library is handed float32(1) / float32(std)")
     ap.add_argument("--area", action="store_true", help="tsvpp_convert_letterbox_area against the loop it replaces and the BILINEAR call; default output profiles/letterbox_area_ab.txt")
+    ap.add_argument("--p010", action="store_true", help="tsvpp_convert_letterbox_p010 against torch's narrowing to NV12 + the 8-bit call; default output profiles/letterbox_p010_ab.txt")
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "letterbox_area_ab.txt" if a.area else "tensor_ab.txt" if a.dtype else "letterbox_ab.txt")
+        a.out = os.path.join(ROOT, "profiles", "letterbox_p010_ab.txt" if a.p010 else "letterbox_area_ab.txt" if a.area else "tensor_ab.txt" if a.dtype else "letterbox_ab.txt")
+    if a.p010:
+        return p010_main(a)
     if a.area:
         return area_main(a)
     if a.dtype:

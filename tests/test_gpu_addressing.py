@@ -6,7 +6,8 @@ offsets cross the sign bit and come within a row of what the host accepts.
   sources   planes whose span, as seen from the address the kernel is handed, lies just past 2^31 (class A) and within one row under TSVPP_SOURCE_SPAN_LIMIT
             (class B), luma and chroma each with a pitch of its own, at pitches that are multiples of 16 (the LDS-DMA staging) and 6 mod 16: the cheapest request
             of tests/dispatch_grid.py per kernel name through tsvpp_convert (one frame, and a batch of 3 whose frames interleave in memory), and the tile calls
-            (ROI, AREA-ROI, letterbox, warp, perspective, remap, mesh; replicate and constant border; staged and gathering contexts; one tensor form);
+            (ROI, AREA-ROI, letterbox, warp, perspective, remap, mesh; replicate and constant border; staged and gathering contexts; one tensor form), and
+            the P010 letterbox call, whose 16-bit planes double every byte span (expected bits: the model of tests/p010_util.py);
   outputs   of more than 2^31 bytes and of just under 2^32: one per store routine of the audit (S1 .. S9 and S11; each case asserts the kernel it launched), in the
             flavours the suite's time allows.  Section 5 of the audit names the routine (S10) and the flavours that are left out, with the oracle's measured time.
 
@@ -353,6 +354,47 @@ def test_a_tensor_form_reads_such_planes_too(vpp, oracle, arena, tile_frames):
             for p in placed:
                 arena.erase(p[0])
                 arena.erase(p[1])
+
+
+# ---- sources: 16-bit planes -- the P010 letterbox call, whose every byte span is twice the 8-bit call's ----------------------------------------------------------------
+# (canvas, rectangles, frames of the launch that stage): 322 x 182 into 128 x 128 stages every tile, into a 32 x 32 rectangle one tile's footprint is the whole
+# frame and gathers
+P010_REQUESTS = [((128, 128), None, N_BATCH), ((32, 32), [(0, 0, 32, 32)] * N_BATCH, 0)]
+
+
+def test_the_p010_letterbox_reads_planes_whose_span_crosses_2_31_and_comes_within_a_row_of_the_limit(vpp, arena):
+    """three P010 frames interleaved in the arena, classes A and B, luma at a multiple of 16 bytes and chroma at 6 mod 16 (pairs that are not 4-byte aligned) and
+    the other way round, a staged and a gathering request, fp32 planar and uint8 merged: the model's bits on the tight frame, every element"""
+    import tensor_stream as ts
+    import p010_cases as PC
+    host = [PC.frame(TW, TH, 7300 + k) for k in range(N_BATCH)]
+    tight = [(torch.from_numpy(y.view(np.uint8)).cuda(), torch.from_numpy(uv.view(np.uint8)).cuda()) for y, uv in host]
+    region, pad = (0, 0, 2 * TW, TH), (456, 512, 512)
+    words = lambda p: arena.buf.view(torch.int16).as_strided((2, TW), (p.pitch // 2, 1), p.base // 2)  # (arena.handle for 16-bit words)
+    for res in ((0, 6), (6, 0)):
+        for cls in "AB":
+            pitches = _class_pitches(region, res, cls)
+            assert pitches[0] != pitches[1] and (pitches[0] % 16, pitches[1] % 16) == res
+            assert all((AU.span(rows, 2 * TW, p) > (1 << 31)) and AU.span(rows, 2 * TW, p) < AU.SPAN_LIMIT for rows, p in ((TH, pitches[0]), (TH // 2, pitches[1])))
+            placed = _place_frames(arena, tight, region, pitches)
+            try:
+                for canvas, rects, staged in P010_REQUESTS:
+                    for flavour in ("f32_planar", "u8_merged"):
+                        fp, _ = PC.params(canvas, BILINEAR, flavour)
+                        d = ts.describe_letterbox_p010(fp, [(TW, TH) + pitches] * N_BATCH, rects=rects)
+                        assert d["staged"] == staged and ("staged" in d["kernel"]) == (staged > 0), d
+                        got, used = vpp.convert_letterbox_p010([words(p[0]) for p in placed], [words(p[1]) for p in placed], fp, pad=pad, rects=rects, width=TW, height=TH)
+                        torch.cuda.synchronize()
+                        assert [tuple(u) for u in used] == PC.rects_of([(TW, TH)] * N_BATCH, canvas, rects)
+                        for k in range(N_BATCH):
+                            want = _cached(("p010", k, canvas, flavour), lambda: torch.from_numpy(np.ascontiguousarray(
+                                PC.want(host[k], (TW, TH), tuple(used[k]), canvas, BILINEAR, flavour, pad))).cuda())
+                            _same_bits(got[k].contiguous().view(-1).view(torch.uint8), want, f"p010 output {k} -> {canvas}, class {cls}, pitches {pitches}, {flavour}")
+            finally:
+                for p in placed:
+                    arena.erase(p[0])
+                    arena.erase(p[1])
+    assert arena.untouched(0, AU.MARGIN), "a conversion wrote into the margin in front of its sources"
 
 
 # ---- outputs between 2^31 and 2^32 bytes ------------------------------------------------------------------------------------------------------------------------------

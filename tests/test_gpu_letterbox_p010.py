@@ -11,62 +11,9 @@ import p010_util as M
 import tensor_util as T
 from cpp_check import run_check, write_nv12
 from letterbox_util import default_rect
+from p010_cases import BLACK, FLAVOURS, FOUR, check, convert, dev, frame, want
 
 pytestmark = pytest.mark.gpu
-
-BLACK = (64, 512, 512)
-# name -> (fourcc, planes, normalization, (dtype, spec) of a tensor or None)
-FLAVOURS = {"u8_merged": (M.RGB24, M.MERGED, False, None), "f32_planar": (M.BGR24, M.PLANAR, True, None), "f16_tensor": (M.RGB24, M.PLANAR, True, (T.F16, T.IMAGENET)),
-            "y800_f32": (M.Y800, M.MERGED, True, None), "y800_u8": (M.Y800, M.MERGED, False, None), "y800_f16": (M.Y800, M.MERGED, True, (T.F16, T.IDENTITY)),
-            "f32_merged": (M.RGB24, M.MERGED, True, None), "u8_planar": (M.BGR24, M.PLANAR, False, None), "bf16_tensor": (M.BGR24, M.PLANAR, True, (T.BF16, T.IMAGENET)),
-            "f32_tensor": (M.RGB24, M.PLANAR, True, (T.F32, T.IMAGENET))}
-FOUR = ["u8_merged", "f32_planar", "f16_tensor", "y800_f32"]
-
-
-def frame(w, h, seed, pitch=None, fill=None):
-    """(y, uv) uint16 planes of `pitch` words: random samples with random low six bits; `fill`: the words of the padding columns"""
-    rng = np.random.default_rng(seed)
-    pitch = pitch or w
-    y = rng.integers(0, 65536, (h, pitch), dtype=np.uint16)
-    uv = rng.integers(0, 65536, (h // 2, pitch), dtype=np.uint16)
-    if fill is not None:
-        y[:, w:] = fill
-        uv[:, w:] = fill
-    return y, uv
-
-
-def dev(a):
-    return torch.from_numpy(a.view(np.int16)).cuda()
-
-
-def want(fr, size, rect, canvas, mode, flavour, pad):
-    fcc, planes, norm, tensor = FLAVOURS[flavour]
-    if tensor is None:
-        return M.expected(fr[0], fr[1], *size, rect, canvas, mode, fcc, planes, norm, pad)
-    k = M.channels(*M.virtual_frame(fr[0], fr[1], *size, rect, canvas, mode, pad), fcc)
-    return T.expected(M.quotient(k), k.shape[0], tensor[1], tensor[0])
-
-
-def convert(vpp, frames, sizes, canvas, mode, flavour, pad=BLACK, rects=None, planes_dev=None):
-    import tensor_stream as ts
-    fcc, planes, norm, tensor = FLAVOURS[flavour]
-    fp = ts.FrameParameters(width=canvas[0], height=canvas[1], resize_type=mode, pixel_format=fcc, planes_pos=planes, normalization=norm)
-    kw = {} if tensor is None else dict(dtype=T.TORCH[tensor[0]], mean=tensor[1][0], std=tensor[1][1])
-    ys, uvs = planes_dev or ([dev(f[0]) for f in frames], [dev(f[1]) for f in frames])
-    return vpp.convert_letterbox_p010(ys, uvs, fp, pad=pad, rects=rects, width=[s[0] for s in sizes], height=[s[1] for s in sizes], **kw)
-
-
-def check(vpp, frames, sizes, canvas, mode, flavour, pad=BLACK, rects=None):
-    got, used = convert(vpp, frames, sizes, canvas, mode, flavour, pad, rects)
-    torch.cuda.synchronize()
-    for k, (fr, size) in enumerate(zip(frames, sizes)):
-        rect = tuple(rects[k]) if rects else default_rect(*size, *canvas)
-        assert tuple(used[k]) == rect
-        ref, g = want(fr, size, rect, canvas, mode, flavour, pad), T.bits(got[k])
-        assert g.size == ref.size
-        bad = np.flatnonzero(g != ref)
-        assert bad.size == 0, f"frame {k} {size} -> {canvas} rect {rect} mode={mode} {flavour}: {bad.size} bytes differ, first at {bad[:4]}"
-    return got
 
 
 @pytest.mark.parametrize("flavour,chroma", [("y800_f32", 512), ("y800_u8", 512), ("y800_f16", 512)] + [(f, c) for f in FOUR[:3] for c in (512, 0, 1023)])

@@ -76,6 +76,7 @@ typedef struct tsvpp_nv12 {
  * plane (height / 2, width) each, with each plane's own pitch.  The region, and the address it is seen from, is
  *   tsvpp_convert / _batch / _table, tsvpp_describe      the crop box where Convert's crop stage applies (the planes advanced to its origin), else the frame;
  *   tsvpp_convert_rois / _rois_area / _rois_tensor       each box (the planes advanced to the box's origin): a small box in a huge frame is legal;
+ *   tsvpp_convert_rois_p010                              each box likewise, rows counted in 2 * width BYTES (its section, below);
  *   letterbox, warp, perspective, remap, mesh            the whole frame.
  * A request with a span at or above the limit is TSVPP_UNSUPPORTED, from the describe call and the convert call alike, before anything is launched.  It comes
  * after the TSVPP_ERROR rules on the request itself (sizes, crop, boxes, pitches), which the describe calls share; the convert calls look at their pointers
@@ -406,7 +407,7 @@ int tsvpp_describe_letterbox_area(const tsvpp_params *p, const tsvpp_tensor_spec
  * row too) at or above TSVPP_SOURCE_SPAN_LIMIT; then, with a spec, rules 2 and 3 of the tensor entry points.
  * tsvpp_describe_letterbox_p010 prints tsvpp_describe_letterbox's keys with "src=p010" in front of frames=, kernel=vpp_letterbox_p010<...> /
  * vpp_letterbox_p010_tensor<...> and limit=32; lds= counts the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks).
- * Not here, each a follow-up: BICUBIC and AREA on P010; P010 through tsvpp_convert, the ROI, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
+ * Not here, each a follow-up: BICUBIC and AREA on P010; P010 through tsvpp_convert, the per-box-size, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
  * presets (the coefficient block already lets a caller set them); 10-bit or 16-bit integer outputs; merged tensors. */
 typedef struct tsvpp_p010 {
     const uint16_t *y;  /* AVFrame::data[0]: one 16-bit word per luma sample */
@@ -420,6 +421,38 @@ int tsvpp_convert_letterbox_p010(tsvpp_ctx *ctx, int n, const tsvpp_p010 *in, co
                                  const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
 int tsvpp_describe_letterbox_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n, const tsvpp_p010 *in, const tsvpp_rect *rects,
                                   int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- 10-bit sources: tsvpp_convert_rois_p010 ----
+ * tsvpp_convert_rois for P010 frames (tsvpp_p010, above): the stage behind the detector that tsvpp_convert_letterbox_p010 feeds, on the same decoded frame, with no
+ * narrowing to 8 bits in between.  One pair of entry points; `spec` null gives the flavours of tsvpp_convert_rois (RGB24 / BGR24 planar and merged, Y800; uint8 or
+ * fp32 by p->normalization), `spec` given those of tsvpp_convert_rois_tensor (planar and Y800 as fp32 / fp16 / bf16; merged: TSVPP_UNSUPPORTED).  Everything not
+ * named here is tsvpp_convert_rois's: boxes that may overlap, touch the edges or be smaller than the output, frames of mixed sizes and pitches, host arrays that
+ * may be freed on return, ceil(n_rois / TSVPP_MAX_ROIS_P010) launches with the per-box records by value in the kernarg segment, no device allocation, no copy, no
+ * host synchronisation, legal under stream capture (a request of more than 64 FRAMES takes one host array of n_frames 32-byte records for the call; if that fails:
+ * TSVPP_ERROR), TSVPP_OPT_COLOR_G_TERM and the context's coefficient block honoured.
+ * Contract.  The reference has no 10-bit path, so this is the definition: output i is, bit for bit and in every flavour, what
+ * tsvpp_convert_letterbox_p010 returns for a P010 frame that consists of box i alone -- luma words rows [top, bottom) x columns [left, right), chroma pairs rows
+ * [top / 2, bottom / 2) x pairs [left / 2, right / 2) -- with the rectangle equal to the whole dst_width x dst_height canvas.  It follows: sample = word >> 6;
+ * NEAREST and BILINEAR with that call's coordinates, clamps, tap order and fused steps on the values 0..1023, xr = (float)width / dst_width, yr alike; the colour
+ * expression with the two offsets scaled by four; k / 1023 correctly rounded, or the byte min(255, (k + 2) >> 2), or cvt(dtype, (q - mean[c]) * scale[c]).  No
+ * word outside the box influences its output: every edge clamp is to the box.
+ * A box needs an even `left` and an even `top` as well as an even width and height; an odd origin is TSVPP_UNSUPPORTED.  tsvpp_convert_rois's rule that an odd
+ * `left` swaps U and V is the reference's crop quirk (its chroma offset is counted in bytes) and is not carried into a contract of our own: a chroma PAIR has no
+ * half.
+ * Status, decided before any device is touched (the describe call returns the same one): tsvpp_convert_rois's, in its order, with TSVPP_ERROR also for a pitch
+ * below 2 * width bytes and an odd pitch -- and, converting, for a plane pointer that is not 2-byte aligned -- and TSVPP_UNSUPPORTED also for an odd `left` or
+ * `top`, for BICUBIC (as for AREA and unknown resize types) and for a plane span of a box, seen from the box's origin as the source limit (above) states it for the
+ * ROI calls, (rows - 1) * pitch + 2 * width bytes (chroma: rows = height / 2, 2 * width bytes per row too), at or above TSVPP_SOURCE_SPAN_LIMIT; then, with a
+ * spec, rules 2 and 3 of the tensor entry points.
+ * tsvpp_describe_rois_p010 prints tsvpp_describe_rois's keys with "src=p010" in front of rois=, kernel=vpp_rois_p010<...> / vpp_rois_p010_tensor<...> and
+ * limit=64; lds= and staged= count the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks): a tile that the
+ * 8-bit call stages may gather here.
+ * Not here: what tsvpp_convert_letterbox_p010 lists, and odd box origins. */
+#define TSVPP_MAX_ROIS_P010 64 /* boxes per launch; more are split */
+int tsvpp_convert_rois_p010(tsvpp_ctx *ctx, int n_frames, const tsvpp_p010 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
+                            const tsvpp_tensor_spec *spec /* may be NULL */, void *const *outs, void *stream);
+int tsvpp_describe_rois_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_p010 *frames, int n_rois,
+                             const tsvpp_roi *rois, int aligned_outputs, char *buf, size_t buf_len);
 
 /* DEBUG ONLY (tests), host only: tsvpp_roi_area_rows as tsvpp_convert_letterbox_area's kernel produces the rows -- the generator begun at the jump start of
  * (scale, first), the largest multiple of the pattern's period that is <= first (0 where the pattern does not close in 1 .. first), which *start receives.

@@ -267,22 +267,40 @@ int VideoProcessor::ConvertLetterboxArea(AVFrame *const *inputs, int n, const ts
     return ConvertLetterboxArea(inputs, n, rects, padY, padU, padV, deviceOuts, options, nullptr, consumerName);
 }
 
-// the AVFrames' planes as 16-bit words, linesize in bytes; `spec` may be null (the library's flavours)
+// the P010 calls: the AVFrames' planes as 16-bit words, linesize in bytes
+static std::vector<tsvpp_p010> p010Frames(const tsvpp_nv12 *frames, int n) {
+    std::vector<tsvpp_p010> in((size_t)n);
+    for (int f = 0; f < n; f++)
+        in[(size_t)f] = tsvpp_p010{ (const uint16_t *)frames[f].y, (const uint16_t *)frames[f].uv, frames[f].pitch_y, frames[f].pitch_uv, frames[f].width, frames[f].height };
+    return in;
+}
+
+// `spec` may be null (the library's flavours)
 int VideoProcessor::ConvertLetterboxP010(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
                                          FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
     return convertTiles(ctx, isClosed, inputs, n, true, deviceOuts, options, consumerName, "ConvertLetterboxP010",
                         [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
-                            std::vector<tsvpp_p010> in((size_t)n);
-                            for (int f = 0; f < n; f++)
-                                in[(size_t)f] = tsvpp_p010{ (const uint16_t *)frames[f].y, (const uint16_t *)frames[f].uv, frames[f].pitch_y, frames[f].pitch_uv, frames[f].width,
-                                                            frames[f].height };
-                            return tsvpp_convert_letterbox_p010(ctx, n, in.data(), p, spec, rects, padY, padU, padV, deviceOuts, stream);
+                            return tsvpp_convert_letterbox_p010(ctx, n, p010Frames(frames, n).data(), p, spec, rects, padY, padU, padV, deviceOuts, stream);
                         });
 }
 
 int VideoProcessor::ConvertLetterboxP010(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
                                          FrameParameters &options, std::string consumerName) {
     return ConvertLetterboxP010(inputs, n, rects, padY, padU, padV, deviceOuts, options, nullptr, consumerName);
+}
+
+// `spec` may be null (the library's flavours)
+int VideoProcessor::ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                    const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRoisP010",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_rois_p010(ctx, nInputs, p010Frames(frames, nInputs).data(), nRois, rois, p, spec, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                    std::string consumerName) {
+    return ConvertRoisP010(inputs, nInputs, rois, nRois, deviceOuts, options, nullptr, consumerName);
 }
 
 int VideoProcessor::ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,

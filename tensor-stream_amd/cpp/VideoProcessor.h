@@ -151,6 +151,11 @@ public:
                              std::string consumerName);
     int ConvertLetterboxP010(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                              const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertRois for 10-bit P010 frames (tsvpp_convert_rois_p010, include/tsvpp.h): the boxes of the detector that ConvertLetterboxP010 fed, cut out of the same
+    // decoded frames; NEAREST and BILINEAR; a box needs an even left and top as well as an even width and height.  Plain, and with a tensor spec (null: the plain call).
+    int ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
+    int ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                        const tsvpp_tensor_spec *spec, std::string consumerName);
     // Boxes that each go to their OWN output size (tsvpp_convert_rois_sized, include/tsvpp.h; not in the reference): text lines of one height and their own widths,
     // the levels of a pyramid, the inputs of several heads behind one detector pass.  rois[i] carries the box and its dst_width x dst_height; deviceOuts[i] holds
     // tsvpp_rois_sized_bytes bytes.  options.resize.width and height must be 0 (the sizes are the boxes') and options.crop empty; options.resize.type is NEAREST,

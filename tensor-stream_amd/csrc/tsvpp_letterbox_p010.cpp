@@ -2,8 +2,7 @@
 // whose `spec` may be null (the plain flavours) or given (the tensor flavours); TSVPP_MAX_LETTERBOX_P010 frames per launch, kernels vpp_letterbox_p010.hip and
 // vpp_letterbox_p010_tensor.hip.  The request rules are letterbox_plan's (tsvpp_plan.cpp) on the frames seen as byte planes, with this file's additions in front of
 // and behind them; the skeletons of both calls are tsvpp_tiles.h's.
-#include <vector>
-
+#include "tsvpp_p010.h"
 #include "tsvpp_tiles.h"
 #include "vpp_letterbox_p010.h"
 
@@ -13,44 +12,13 @@ static_assert(TSVPP_MAX_LETTERBOX_P010 == TSVPP_MAX_LETTERBOX, "the P010 entry p
 
 namespace {
 
-inline int p010_pitch(int pitch, int width) { return pitch ? pitch : 2 * width; } // an unset pitch means 2 * width bytes
-
-// The frames as the tile skeletons and letterbox_plan read them: the same planes, pitches in bytes, sizes in samples.  Up to one launch's frames live on the
-// stack; a larger request takes one host array of n records (32 bytes each) for the call -- the only host allocation of the path, and no device allocation ever.
-struct P010Frames {
-    tsvpp_nv12 local[TSVPP_MAX_LETTERBOX_P010];
-    std::vector<tsvpp_nv12> heap;
-    const tsvpp_nv12 *data = nullptr;
-    P010Frames(int n, const tsvpp_p010 *in) {
-        if (!in || n <= 0) return;
-        tsvpp_nv12 *fr = local;
-        if (n > (int)TSVPP_MAX_LETTERBOX_P010) {
-            try {
-                heap.resize((size_t)n);
-            } catch (...) { // no exception crosses the C boundary: the request is answered as one without frames, TSVPP_ERROR
-                return;
-            }
-            fr = heap.data();
-        }
-        for (int f = 0; f < n; f++)
-            fr[f] = tsvpp_nv12{ (const uint8_t *)in[f].y, (const uint8_t *)in[f].uv, p010_pitch(in[f].pitch_y, in[f].width), p010_pitch(in[f].pitch_uv, in[f].width), in[f].width,
-                                in[f].height };
-        data = fr;
-    }
-};
-
 // The status of a request, in the order that is part of the ABI: the letterbox call's, with the P010 rules in its two classes
 // (`converting`: the planes are read, so their addresses must hold 16-bit words)
 int p010_plan(const tsvpp_params *p, int n, const tsvpp_nv12 *fr, const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, bool converting, RoiPlan &pl) {
     if (!p || !fr || n <= 0) return TSVPP_ERROR;
-    for (int f = 0; f < n; f++) {
-        if (fr[f].width <= 0 || fr[f].height <= 0) return TSVPP_ERROR;
-        if (fr[f].pitch_y < 2 * (long)fr[f].width || fr[f].pitch_uv < 2 * (long)fr[f].width) return TSVPP_ERROR;
-        if ((fr[f].pitch_y | fr[f].pitch_uv) & 1) return TSVPP_ERROR;
-    }
+    if (p010_frames_error(n, fr) != TSVPP_OK) return TSVPP_ERROR;
     if (pad_y < 0 || pad_y > 1023 || pad_u < 0 || pad_u > 1023 || pad_v < 0 || pad_v > 1023) return TSVPP_ERROR;
-    for (int f = 0; converting && f < n; f++)
-        if (((uintptr_t)fr[f].y | (uintptr_t)fr[f].uv) & 1) return TSVPP_ERROR;
+    if (converting && p010_planes_error(n, fr) != TSVPP_OK) return TSVPP_ERROR;
     const int sts = letterbox_plan(p, n, fr, rects, 0, 0, 0, pl); // (its pitch and span rules are weaker than the ones here)
     if (sts != TSVPP_OK) return sts;
     if (pl.mode != M_NEAREST && pl.mode != M_BILINEAR) return TSVPP_UNSUPPORTED; // BICUBIC (AREA and unknown types: letterbox_plan's answer)
@@ -156,13 +124,13 @@ extern "C" {
 
 int tsvpp_convert_letterbox_p010(tsvpp_ctx *ctx, int n, const tsvpp_p010 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec, const tsvpp_rect *rects, int pad_y,
                                  int pad_u, int pad_v, void *const *outs, void *stream) {
-    const P010Frames fr(n, in);
+    const P010Frames<TSVPP_MAX_LETTERBOX_P010> fr(n, in);
     return tile_convert(LbP010Path{ spec != nullptr, p, spec, n, fr.data, rects, pad_y, pad_u, pad_v, true }, ctx, outs, stream);
 }
 
 int tsvpp_describe_letterbox_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spec, int n, const tsvpp_p010 *in, const tsvpp_rect *rects, int aligned_outputs,
                                   char *buf, size_t buf_len) {
-    const P010Frames fr(n, in);
+    const P010Frames<TSVPP_MAX_LETTERBOX_P010> fr(n, in);
     return tile_describe(LbP010Path{ spec != nullptr, p, spec, n, fr.data, rects, 0, 0, 0, false }, aligned_outputs, buf, buf_len); // (the pad is no part of what is launched)
 }
 

@@ -14,6 +14,7 @@ TSVPP_MAX_ROIS_AREA = 64  # ... of tsvpp_convert_rois_area
 TSVPP_MAX_ROIS_SIZED = 48  # ... of tsvpp_convert_rois_sized (64-byte records)
 TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
 TSVPP_MAX_LETTERBOX_P010 = 32  # ... of tsvpp_convert_letterbox_p010
+TSVPP_MAX_ROIS_P010 = 64  # boxes per launch of tsvpp_convert_rois_p010
 TSVPP_MAX_WARPS = 32  # outputs per launch of tsvpp_convert_warp
 TSVPP_MAX_PERSP = 32  # outputs per launch of tsvpp_convert_perspective
 TSVPP_MAX_REMAPS = 32  # outputs per launch of tsvpp_convert_remap
@@ -109,7 +110,7 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_letterbox_rect", "tsvpp_convert_letterbox", "tsvpp_describe_letterbox",
            "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor",
            "tsvpp_convert_letterbox_area", "tsvpp_describe_letterbox_area", "tsvpp_letterbox_area_rows",
-           "tsvpp_convert_letterbox_p010", "tsvpp_describe_letterbox_p010",
+           "tsvpp_convert_letterbox_p010", "tsvpp_describe_letterbox_p010", "tsvpp_convert_rois_p010", "tsvpp_describe_rois_p010",
            "tsvpp_rois_sized_bytes", "tsvpp_convert_rois_sized", "tsvpp_describe_rois_sized", "tsvpp_convert_rois_sized_tensor", "tsvpp_describe_rois_sized_tensor",
            "tsvpp_rois_sized_tile",
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
@@ -208,6 +209,10 @@ def lib():
     L.tsvpp_convert_letterbox_p010.restype = i32
     L.tsvpp_describe_letterbox_p010.argtypes = [pp, ps, i32, ctypes.POINTER(P010), pc, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_describe_letterbox_p010.restype = i32
+    L.tsvpp_convert_rois_p010.argtypes = [vp, i32, ctypes.POINTER(P010), i32, pr, pp, ps, ctypes.POINTER(vp), vp]  # (spec may be None)
+    L.tsvpp_convert_rois_p010.restype = i32
+    L.tsvpp_describe_rois_p010.argtypes = [pp, ps, i32, ctypes.POINTER(P010), i32, pr, i32, ctypes.c_char_p, ctypes.c_size_t]
+    L.tsvpp_describe_rois_p010.restype = i32
     L.tsvpp_letterbox_area_rows.argtypes = [ctypes.c_float, i32, i32, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.tsvpp_letterbox_area_rows.restype = i32
     pz = ctypes.POINTER(RoiSized)

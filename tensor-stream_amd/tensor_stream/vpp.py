@@ -386,6 +386,29 @@ class VideoProcessor:
             used = [(r.left, r.top, r.width, r.height) for r in recs]
         return out, used
 
+    def convert_rois_p010(self, ys, uvs, rois, params, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_rois for 10-bit P010 frames (tsvpp_convert_rois_p010): the boxes of a detector that convert_letterbox_p010 fed, cut out of the same decoded
+        frame with no narrowing to 8 bits in between, one launch per 64 boxes.  ys / uvs: the planes of ONE frame (a pair of 2-D int16 / uint16 tensors: rows x
+        pitch in words) or lists of them, as convert_letterbox_p010 takes them; rois, params, out, width / height, dtype / mean / std and the result: as
+        convert_rois.  NEAREST and BILINEAR; a box needs an even left and top as well as an even width and height.  Output i equals, bit for bit,
+        convert_letterbox_p010 of a frame that consists of box i alone with the rectangle equal to the canvas: fp32 outputs are k / 1023, uint8 outputs
+        min(255, (k + 2) >> 2)."""
+        p = params.parameters if isinstance(params, FrameParameters) else params
+        spec = tensor_spec(dtype, mean, std)
+        ys, uvs, boxes = _normalize_rois(ys, uvs, rois)
+        widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
+        frames = (N.P010 * len(ys))(*[_p010_frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
+        n = len(boxes)
+        if n == 0:
+            raise RuntimeError("-3: convert_rois_p010 needs at least one box")
+        if out is None:
+            out = self._alloc_items(p, n, spec, "convert_rois_p010 needs an even, positive output size")
+        recs = (N.Roi * n)(*[N.Roi(*b) for b in boxes])
+        outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        N.check(self._lib.tsvpp_convert_rois_p010(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), None if spec is None else ctypes.byref(spec), outs, stream))
+        return out
+
     def _convert_letterbox(self, area, ys, uvs, params, pad, rects, out, width, height, spec):
         p = params.parameters if isinstance(params, FrameParameters) else params
         n = len(ys)
@@ -818,6 +841,21 @@ def describe_letterbox_p010(params, frames, rects=None, aligned_outputs=True, dt
     spec = tensor_spec(dtype, mean, std)
     N.check(N.lib().tsvpp_describe_letterbox_p010(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf,
                                                   len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def describe_rois_p010(params, frames, rois, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_rois_p010 of this request would launch, as a dict (tsvpp_describe_rois_p010: describe_rois's keys with src = "p010"; lds and staged count
+    the footprints as 16-bit words) -- host logic only, works without a GPU.  Arguments as describe_rois; pitches are in BYTES (0: 2 * width)."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = [N.P010(None, None, r.pitch_y, r.pitch_uv, r.width, r.height) for r in _geometry_records(frames)]
+    _, _, boxes = _normalize_rois([None] * len(recs), [None] * len(recs), rois)
+    fr = (N.P010 * max(len(recs), 1))(*recs)
+    bx = (N.Roi * max(len(boxes), 1))(*[N.Roi(*b) for b in boxes])
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    N.check(N.lib().tsvpp_describe_rois_p010(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0,
+                                             buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

@@ -5,6 +5,7 @@ before tsvpp_convert_rois) against (b) ONE tsvpp_convert_rois -- on one stream, 
     python tools/rois_ab.py [--out profiles/rois_ab.txt] [--repeats 20] [--iters 50] [--ns 1,4,16,32,64]
     python tools/rois_ab.py --area [--out profiles/rois_area_ab.txt]      the AREA leg: tsvpp_convert_rois_area (see area_main)
     python tools/rois_ab.py --dtype f16 [--mean a,b,c] [--std a,b,c]      the tensor legs: tsvpp_convert_rois_tensor (see tensor_main; appends to profiles/tensor_ab.txt)
+    python tools/rois_ab.py --p010 [--out profiles/rois_p010_ab.txt]      10-bit sources: tsvpp_convert_rois_p010 against narrowing + tsvpp_convert_rois (see p010_main)
 
 Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the
 MEDIAN block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next frame of a pool of 96 distinct 1080p frames
@@ -288,9 +289,136 @@ def tensor_main(a):
     vpp.Close()
 
 
+P010_CONFIGS = [("224x224 BILINEAR BGR24 planar fp32", (224, 224), 2, 0, True, None),
+                ("112x112 BILINEAR RGB24 merged uint8", (112, 112), 1, 1, False, None),
+                ("224x224 BILINEAR RGB24 planar fp16, ImageNet mean / std", (224, 224), 1, 0, True, "f16")]
+P010_PITCH = 4096  # bytes: what a decoder hands over for 1080p
+
+
+def p010_main(a):
+    """10-bit sources, same protocol (seeded boxes with sides 64 .. 512 -- origins rounded down to even -- of a 1080p frame, the P010 frame at a pitch of 4096
+    bytes, one stream, frames and outputs rotating through more than 256 MiB, median of the blocks with their spread):
+      (a) one tsvpp_convert_rois_p010 call
+      (b) what a caller does without it: torch `>> 8` and a narrowing copy of both planes into NV12 buffers on the same stream, once per frame, then
+          tsvpp_convert_rois (the fp16 configuration: tsvpp_convert_rois_tensor)
+      (c) the 8-bit call of (b) alone, on frames narrowed beforehand
+    Every leg is parity-checked, every box bit for bit, before and after its timing: (a) against tests/p010_util.py, (b) and (c) against the CPU oracle on the
+    narrowed planes (tests/tensor_util.py for fp16)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import p010_util as M
+    import tensor_util as T
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    nf, PW = a.frames, P010_PITCH // 2
+    base_y = torch.randint(-32768, 32768, (H, PW), dtype=torch.int16, device=dev, generator=gen)
+    base_uv = torch.randint(-32768, 32768, (H // 2, PW), dtype=torch.int16, device=dev, generator=gen)
+    ys = [base_y + 2357 * k for k in range(nf)]  # distinct frames: every word + 2357 k (mod 2^16)
+    uvs = [base_uv + 2357 * k for k in range(nf)]
+    ys8 = [(t[:, :W] >> 8).to(torch.uint8) for t in ys]  # the narrowed frames of leg (c); leg (b) writes its own
+    uvs8 = [(t[:, :W] >> 8).to(torch.uint8) for t in uvs]
+    by8, buv8 = [torch.empty_like(t) for t in ys8], [torch.empty_like(t) for t in uvs8]
+    fr16 = [(N.P010 * 1)(N.P010(ys[k].data_ptr(), uvs[k].data_ptr(), P010_PITCH, P010_PITCH, W, H)) for k in range(nf)]
+    fr8c = [(N.NV12 * 1)(N.NV12(ys8[k].data_ptr(), uvs8[k].data_ptr(), W, W, W, H)) for k in range(nf)]
+    fr8b = [(N.NV12 * 1)(N.NV12(by8[k].data_ptr(), buv8[k].data_ptr(), W, W, W, H)) for k in range(nf)]
+    pool_mib = nf * (P010_PITCH * H * 3 // 2) >> 20
+    lines = [f"# tools/rois_ab.py --p010: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {nf} x 1080p P010 at pitch {P010_PITCH} ({pool_mib} MiB), "
+             f"median of {a.repeats} blocks of {a.iters} iterations, one stream",
+             "# (a) = 1 x tsvpp_convert_rois_p010   (b) = torch >> 8 + narrowing copy of both planes, then 1 x tsvpp_convert_rois   (c) = the 8-bit call alone on frames narrowed beforehand",
+             "# us per call, [min .. max of the blocks]; staged = boxes of the P010 call whose every tile stages in LDS / of the 8-bit call"]
+    met = True
+    for name, dst, fcc, planes, norm, dt in P010_CONFIGS:
+        fp = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=1, pixel_format=fcc, planes_pos=planes, normalization=norm)
+        p = fp.parameters
+        tdt = None if dt is None else T.TORCH[dt]
+        spec = None if dt is None else ts.tensor_spec(dtype=tdt, mean=T.IMAGENET[0], std=T.IMAGENET[1])
+        kw = {} if dt is None else dict(dtype=tdt, mean=T.IMAGENET[0], std=T.IMAGENET[1])
+        sref = None if spec is None else ctypes.byref(spec)
+        out_bytes = 3 * dst[0] * dst[1] * (2 if dt else (4 if norm else 1))
+        lines += ["", f"## {name}", f"{'n':>3} | {'(a) us':>8} {'spread':>15} | {'(b) us':>8} {'spread':>15} | {'(c) us':>8} {'spread':>15} | {'b / a':>6} {'a / c':>6} | {'staged':>9} | a < b by more than (b)'s spread"]
+        for n in [int(v) for v in a.ns.split(",")]:
+            boxes = [(l & ~1, t & ~1, (l & ~1) + r - l, (t & ~1) + b - t) for l, t, r, b in boxes_for(n, seed=100 + n)]
+            sets = max(2, min(64, (300 << 20) // (n * out_bytes) + 1))
+            pool = [vpp._alloc(p, dst[0], dst[1], n, tdt) if dt else vpp._alloc(p, dst[0], dst[1], n) for _ in range(sets)]
+            recs = (N.Roi * n)(*[N.Roi(0, *b) for b in boxes])
+            out_arrs = [(ctypes.c_void_p * n)(*[pool[s][i].data_ptr() for i in range(n)]) for s in range(sets)]
+            ctx, pref = vpp._ctx, ctypes.byref(p)
+            d16 = ts.describe_rois_p010(fp, [(W, H, P010_PITCH)], boxes, **kw)["staged"]
+            d8 = ts.describe_rois(fp, [(W, H)], boxes, **kw)["staged"]
+
+            def leg_a(k):
+                if L.tsvpp_convert_rois_p010(ctx, 1, fr16[k % nf], n, recs, pref, sref, out_arrs[k % sets], raw) != 0:
+                    raise RuntimeError("tsvpp_convert_rois_p010 failed")
+
+            def rois8(frames, k):
+                sts = L.tsvpp_convert_rois(ctx, 1, frames[k % nf], n, recs, pref, out_arrs[k % sets], raw) if spec is None else \
+                    L.tsvpp_convert_rois_tensor(ctx, 1, frames[k % nf], n, recs, pref, sref, out_arrs[k % sets], raw)
+                if sts != 0:
+                    raise RuntimeError("tsvpp_convert_rois failed")
+
+            def leg_b(k):
+                f = k % nf
+                by8[f].copy_(ys[f][:, :W] >> 8)
+                buv8[f].copy_(uvs[f][:, :W] >> 8)
+                rois8(fr8b, k)
+
+            def leg_c(k):
+                rois8(fr8c, k)
+
+            def parity(leg, k):
+                f, got = k % nf, pool[k % sets]
+                torch.cuda.synchronize()
+                if leg == "a":
+                    y, uv = ys[f].cpu().numpy().view(np.uint16), uvs[f].cpu().numpy().view(np.uint16)
+                else:
+                    y, uv = ys8[f].cpu().numpy(), uvs8[f].cpu().numpy()
+                for i, (l, t, r, b) in enumerate(boxes):
+                    if leg == "a":
+                        k10 = M.channels(*M.virtual_frame(y[t:b, l:r], uv[t // 2:b // 2, l:r], r - l, b - t, (0, 0, *dst), dst, M.BILINEAR, (0, 0, 0)), fcc)
+                        ref = M.stored(k10, planes, norm) if dt is None else T.expected(M.quotient(k10), 3, T.IMAGENET, dt)
+                    else:
+                        q = O.convert(y[t:b, l:r], uv[t // 2:b // 2, l:r], dst=dst, resize_type=1, fourcc=fcc, planes=planes, normalization=norm, nthreads=8)[0]
+                        ref = q.view(np.uint8).ravel() if dt is None else T.expected(q, 3, T.IMAGENET, dt)
+                    if not np.array_equal(T.bits(got[i]), ref):
+                        raise SystemExit(f"PARITY FAILURE: leg ({leg}) {name} n={n} box {i} {(l, t, r, b)}")
+
+            res = {}
+            with torch.cuda.stream(stream):
+                for leg, fn in (("a", leg_a), ("b", leg_b), ("c", leg_c)):
+                    for t in pool:
+                        t.zero_()
+                    fn(0)
+                    parity(leg, 0)
+                    blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(10, a.iters // 2))
+                    parity(leg, last)
+                    res[leg] = blocks
+            m = {k: statistics.median(v) for k, v in res.items()}
+            sp = lambda v: f"{min(v):7.2f}..{max(v):<6.2f}"
+            ok = m["b"] - m["a"] > max(res["b"]) - min(res["b"])
+            met = met and ok
+            lines.append(f"{n:>3} | " + " | ".join(f"{m[k]:8.2f} {sp(res[k])}" for k in "abc") + f" | {m['b'] / m['a']:6.2f} {m['a'] / m['c']:6.2f} | {d16:>3} / {d8:<3} | {'met' if ok else 'NOT MET'}")
+            print(lines[-1], flush=True)
+            del pool
+            torch.cuda.empty_cache()
+    lines += ["", "# parity: every leg bit-exact on every box before and after its timing -- (a) against tests/p010_util.py, (b) and (c) against the CPU oracle on the narrowed planes",
+              f"# expectation ((a) faster than (b) in every row by more than the spread of (b)'s blocks): {'met' if met else 'NOT MET in the rows marked'}"]
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--area", action="store_true", help="the AREA leg (tsvpp_convert_rois_area); default output profiles/rois_area_ab.txt")
+    ap.add_argument("--p010", action="store_true", help="10-bit sources (tsvpp_convert_rois_p010); default output profiles/rois_p010_ab.txt, frame pool 48")
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--iters", type=int, default=50)
@@ -301,6 +429,12 @@ def main():
     ap.add_argument("--std", default="0.229,0.224,0.225", help="per stored channel (with --dtype); the library is handed float32(1) / float32(std)")
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
+    if a.p010:
+        a.out = a.out or os.path.join(ROOT, "profiles", "rois_p010_ab.txt")
+        if a.frames > 48:  # 48 P010 frames at pitch 4096: 303 MiB
+            print(f"--p010: frame pool of 48 frames (303 MiB) instead of --frames {a.frames}", flush=True)
+            a.frames = 48
+        return p010_main(a)
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "tensor_ab.txt" if a.dtype else ("rois_area_ab.txt" if a.area else "rois_ab.txt"))
     if a.dtype:

@@ -407,7 +407,8 @@ int tsvpp_describe_letterbox_area(const tsvpp_params *p, const tsvpp_tensor_spec
  * row too) at or above TSVPP_SOURCE_SPAN_LIMIT; then, with a spec, rules 2 and 3 of the tensor entry points.
  * tsvpp_describe_letterbox_p010 prints tsvpp_describe_letterbox's keys with "src=p010" in front of frames=, kernel=vpp_letterbox_p010<...> /
  * vpp_letterbox_p010_tensor<...> and limit=32; lds= counts the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks).
- * Not here, each a follow-up: BICUBIC and AREA on P010; P010 through tsvpp_convert, the per-box-size, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
+ * Not here, each a follow-up: BICUBIC on P010, and AREA for the boxes of tsvpp_convert_rois_p010 (the letterbox has it: tsvpp_convert_letterbox_p010_area, below);
+ * P010 through tsvpp_convert, the per-box-size, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
  * presets (the coefficient block already lets a caller set them); 10-bit or 16-bit integer outputs; merged tensors. */
 typedef struct tsvpp_p010 {
     const uint16_t *y;  /* AVFrame::data[0]: one 16-bit word per luma sample */
@@ -421,6 +422,38 @@ int tsvpp_convert_letterbox_p010(tsvpp_ctx *ctx, int n, const tsvpp_p010 *in, co
                                  const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
 int tsvpp_describe_letterbox_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n, const tsvpp_p010 *in, const tsvpp_rect *rects,
                                   int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- 10-bit sources: tsvpp_convert_letterbox_p010_area ----
+ * tsvpp_convert_letterbox_p010 with an exact box filter, the averaging filter a 1080p or 4K Main10 frame into a 640 x 640 canvas should get: at those exact
+ * ratios 3 and 6 every BILINEAR weight is zero and the call above point-samples one source sample in nine, or in 36.  Signatures as the pair above.  Everything not
+ * stated here is tsvpp_convert_letterbox_p010's, word for word: tsvpp_p010 frames, rectangles, the evenness rules, the pad as a P010 sample triple, 32 frames per
+ * launch with their records by value in the kernarg segment, no allocation, no copy, legal under stream capture, the colour expression with the offsets scaled by
+ * four, the G-term option and the coefficient block, the stored forms k / 1023 and min(255, (k + 2) >> 2), the tensor forms with a spec, and the status rules
+ * in their order.  p->resize_type must be TSVPP_AREA; any other type is TSVPP_UNSUPPORTED (and tsvpp_convert_letterbox_p010 keeps answering TSVPP_UNSUPPORTED for AREA).
+ *   resize   per plane and separable, in unsigned 32-bit integers: Y from W x H samples to the rectangle's w x h, U and V each from W/2 x H/2 to w/2 x h/2.  One
+ *            axis with N source and n output samples, in units in which a source sample is n wide: output j covers [j N, (j + 1) N), its taps are
+ *            i = floor(j N / n) .. floor(((j + 1) N - 1) / n), and tap i weighs o(i, j) = min((i + 1) n, (j + 1) N) - max(i n, j N) -- positive integers that
+ *            sum to N.  Horizontal pass, per source row: hx = sum o_x s, then r = (64 hx + N_x / 2) / N_x, the row mean in 1/64 sample steps, 0..65472.
+ *            Vertical pass: v = sum o_y r, then k = (v + 32 N_y) / (64 N_y), 0..1023.  All divisions are floor divisions.  k takes the place of the BILINEAR
+ *            call's truncated blend.  There is no float and no dependence on order; k lies within 0.5 + 1/128 of the exact rational mean (1/128: the rounding
+ *            of r) and a flat frame comes back unchanged.  The same formula holds on an axis that is not shrunk: N = n is the identity, N < n gives one or
+ *            two taps -- an up-scaled axis gets box coverage; callers who want a smooth up-scale use the BILINEAR call.
+ *   limits   TSVPP_UNSUPPORTED, decided before a device is touched and returned alike by describe: a side of a frame or of its rectangle above
+ *            TSVPP_BOX_P010_MAX_SIDE (the 32-bit integers above need it: n N stays below 2^32), and more than TSVPP_BOX_P010_MAX_TAPS taps on an axis of either
+ *            plane (ratios up to 16: 7680 -> 480).
+ * tsvpp_describe_letterbox_p010_area prints tsvpp_describe_letterbox_p010's keys with mode=area and kernel=vpp_letterbox_p010_area<...> /
+ * vpp_letterbox_p010_area_tensor<...> (staged= counts every frame: every tile walks its footprint through LDS), then "taps=<largest per axis, XxY> band=<source rows per band>";
+ * lds= is the two band buffers and the row means of one band.
+ * tsvpp_box_p010_plane is the contract's executable form, on the host: it resizes one plane of SAMPLES (0..1023, src_w x src_h, rows of src_w) to dst_w x dst_h
+ * with the functions the kernel is compiled from (csrc/vpp_box_p010.h).  TSVPP_ERROR for null pointers or sizes below 1, TSVPP_UNSUPPORTED for a side above
+ * TSVPP_BOX_P010_MAX_SIDE; the tap limit is the kernel's and does not apply. */
+#define TSVPP_BOX_P010_MAX_SIDE 16384
+#define TSVPP_BOX_P010_MAX_TAPS 17
+int tsvpp_convert_letterbox_p010_area(tsvpp_ctx *ctx, int n, const tsvpp_p010 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */,
+                                      const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
+int tsvpp_describe_letterbox_p010_area(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n, const tsvpp_p010 *in, const tsvpp_rect *rects,
+                                       int aligned_outputs, char *buf, size_t buf_len);
+int tsvpp_box_p010_plane(const uint16_t *src, int src_w, int src_h, uint16_t *dst, int dst_w, int dst_h);
 
 /* ---- 10-bit sources: tsvpp_convert_rois_p010 ----
  * tsvpp_convert_rois for P010 frames (tsvpp_p010, above): the stage behind the detector that tsvpp_convert_letterbox_p010 feeds, on the same decoded frame, with no

@@ -151,6 +151,13 @@ public:
                              std::string consumerName);
     int ConvertLetterboxP010(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                              const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertLetterboxP010 with ResizeType AREA (tsvpp_convert_letterbox_p010_area, include/tsvpp.h): an exact integer box filter per plane -- every source sample
+    // is averaged, where BILINEAR point-samples one in nine at 1080p -> 640; a frame side above 16384 or more than 17 taps on an axis is refused, as is every other
+    // resize type (and ConvertLetterboxP010 refuses AREA).  Plain, and with a tensor spec (null: the plain call).
+    int ConvertLetterboxP010Area(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                                 std::string consumerName);
+    int ConvertLetterboxP010Area(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
+                                 const tsvpp_tensor_spec *spec, std::string consumerName);
     // ConvertRois for 10-bit P010 frames (tsvpp_convert_rois_p010, include/tsvpp.h): the boxes of the detector that ConvertLetterboxP010 fed, cut out of the same
     // decoded frames; NEAREST and BILINEAR; a box needs an even left and top as well as an even width and height.  Plain, and with a tensor spec (null: the plain call).
     int ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);

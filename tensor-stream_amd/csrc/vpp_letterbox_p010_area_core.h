@@ -1,0 +1,200 @@
+// vpp_letterbox_p010_area_core.h -- the P010 AREA letterbox kernel (see vpp_letterbox_p010_area.hip for what it does), as a template that two translation units
+// instantiate: vpp_letterbox_p010_area.hip with the library's output flavours (EL_LIB) and vpp_letterbox_p010_area_tensor.hip with the tensor store.
+//
+// Called, not copied: the canvas grid (tile_index), the descriptor fill (tile_desc), the rectangle's part of a tile (tile_inner_range), the shifted last tile
+// column (roi_tile_col0), describe_plane and the LDS-DMA loop (stage_plane_dma), the chroma pair reader (p010_pair), and everything behind the samples
+// (p010_store_tile, vpp_letterbox_p010_core.h) -- on integer-valued Yf / Uf / Vf, as the NEAREST / BILINEAR kernel hands them over.  The arithmetic is
+// vpp_box_p010.h's, shared with the host.  New here: the sampling stage, a walk over the tile's source footprint in bands of rows.
+#pragma once
+#include "vpp_letterbox_p010_area.h"
+#include "vpp_letterbox_p010_core.h"
+
+#pragma clang fp contract(off)
+
+namespace tsvpp {
+
+// What one plane's walk needs to know of its plane and of the tile's part of it.  Luma: columns are samples of 2 bytes; chroma: (U, V) pairs of 4 bytes, and an
+// "output column" of the row means is a pair's U or V -- 16 pairs x 2 fill the 32 columns that 32 luma outputs fill.
+struct BoxPlane {
+    const uint8_t *base;
+    int pitch;
+    int xlo, xhi, ylo, yhi; // the footprint, in samples / pairs and rows: exact, clamped into the plane
+    uint32_t Nx, nx, Ny, ny; // the plane's two axes, source -> rectangle
+    int c0, ncols;           // first output column / pair of the tile's part, and how many
+};
+
+// One band: rows [row_lo, row_lo + nrows) of the footprint as raw words into `buf`, 16-byte chunks by LDS-DMA.  The caller waits and barriers.
+template <int BYTES> __device__ __forceinline__ LdsPlane box_issue_band(const BoxPlane &pl, uint8_t *buf, int row_lo, int nrows, int cpr, uint32_t magic) {
+    const uint8_t *a0;
+    const LdsPlane lp = describe_plane(buf, pl.base, pl.pitch, row_lo, BYTES * pl.xlo, cpr, a0);
+    stage_plane_dma(buf, a0, lp, pl.pitch, nrows, BYTES * (pl.xhi - pl.xlo + 1), magic, ROI_THREADS);
+    return lp;
+}
+
+// The walk of one plane.  NR = output rows of a lane's thread tile in this plane (luma 2, chroma 1); jr[] = those rows, col[] = the four columns of the row
+// means the lane adds up (luma: its four output columns; chroma: U, V of its two pairs), both as indices of the tile's part; acc[][] = sum o_y r.
+//
+// Per band: (1) all 128 lanes form r for (source row x output column): lane -> column `tid & 31` (chroma: pair `tid & 15`), rows `tid >> 5` + 4 k (chroma
+// `tid >> 4` + 8 k) -- a lane keeps its column through the whole walk, so its first tap and its two edge weights are computed once, in front of the first band,
+// and the lanes of a wave read neighbouring taps of the same one or two rows.  (2) each lane adds the band's rows that overlap its own output rows, times the
+// overlap, into acc.  Band b + 1 is issued before band b is reduced; two barriers per band order the buffers and the row means.
+template <bool CHROMA, int NR>
+__device__ __forceinline__ void box_walk_plane(const BoxPlane &pl, bool uv4, int band, int buf_bytes, bool sample, const int jr[NR], const int col[4], uint32_t acc[NR][4]) {
+    constexpr int BYTES = CHROMA ? 4 : 2, LANES = CHROMA ? 16 : 32, RSTEP = ROI_THREADS / LANES;
+    uint32_t *const rbuf = (uint32_t *)lds_raw;
+    uint8_t *const buf0 = lds_raw + band * 128;
+    const int cpr = roi_chunks(BYTES * (pl.xhi - pl.xlo + 1));
+    band = min(band, (buf_bytes >> 4) / cpr); // (never smaller for a launch the host sized: the buffers hold `band` rows of the launch's widest footprint)
+    if (band < 1) return;
+    const uint32_t magic = 0xFFFFFFFFu / (uint32_t)cpr + 1u;
+    const BoxDiv dnx = box_div_of(pl.nx), dny = box_div_of(pl.ny), dNx = box_div_of(pl.Nx);
+
+    // horizontal: this lane's column
+    const int hc = (int)threadIdx.x & (LANES - 1), hr0 = (int)threadIdx.x / LANES;
+    const bool hon = hc < pl.ncols;
+    BoxTaps tx = box_taps((uint32_t)(pl.c0 + min(hc, pl.ncols - 1)), pl.Nx, pl.nx, dnx);
+    tx.first = (uint32_t)clampi((int)tx.first, pl.xlo, pl.xhi); // (no input can make a read leave the band buffer; for every valid request the clamps never fire)
+    tx.count = min(min(tx.count, (uint32_t)BOX_P010_MAX_TAPS), (uint32_t)pl.xhi - tx.first + 1u);
+    // vertical: this lane's rows
+    BoxTaps ty[NR];
+#pragma unroll
+    for (int rr = 0; rr < NR; rr++) ty[rr] = box_taps((uint32_t)jr[rr], pl.Ny, pl.ny, dny);
+
+    const int rows = pl.yhi - pl.ylo + 1, bands = (rows + band - 1) / band;
+    LdsPlane lp = box_issue_band<BYTES>(pl, buf0, pl.ylo, min(band, rows), cpr, magic), lp_next = lp;
+    for (int b = 0; b < bands; b++) {
+        const int y0 = pl.ylo + b * band, nr = min(band, pl.yhi + 1 - y0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // band b has landed; behind the barrier: for both waves, and band b - 1 is reduced
+        __syncthreads();
+        if (b + 1 < bands) lp_next = box_issue_band<BYTES>(pl, buf0 + ((b + 1) & 1) * buf_bytes, y0 + band, min(band, pl.yhi + 1 - (y0 + band)), cpr, magic);
+        if (hon) {
+            for (int r = hr0; r < nr; r += RSTEP) {
+                const uint8_t *p = lp.base + r * lp.lp + ((lp.m0 + r * lp.pm) & 15) + BYTES * ((int)tx.first - pl.xlo);
+                if constexpr (!CHROMA) {
+                    uint32_t mid = 0, s0 = (uint32_t)(*(const uint16_t *)p >> 6), s1 = 0;
+                    for (uint32_t t = 1; t + 1 < tx.count; t++) mid += (uint32_t)(*(const uint16_t *)(p + 2 * t) >> 6);
+                    if (tx.count > 1) s1 = (uint32_t)(*(const uint16_t *)(p + 2 * (tx.count - 1)) >> 6);
+                    rbuf[r * 32 + hc] = box_row_mean(tx.w_first * s0 + pl.nx * mid + tx.w_last * s1, dNx);
+                } else { // U and V of a pair: one dword where the plane is 4-byte aligned
+                    const uint32_t a = p010_pair(p, uv4);
+                    uint32_t mu = 0, mv = 0, u1 = 0, v1 = 0;
+                    for (uint32_t t = 1; t + 1 < tx.count; t++) {
+                        const uint32_t m = p010_pair(p + 4 * t, uv4);
+                        mu += (m >> 6) & 1023u;
+                        mv += m >> 22;
+                    }
+                    if (tx.count > 1) {
+                        const uint32_t z = p010_pair(p + 4 * (tx.count - 1), uv4);
+                        u1 = (z >> 6) & 1023u;
+                        v1 = z >> 22;
+                    }
+                    rbuf[r * 32 + 2 * hc] = box_row_mean(tx.w_first * ((a >> 6) & 1023u) + pl.nx * mu + tx.w_last * u1, dNx);
+                    rbuf[r * 32 + 2 * hc + 1] = box_row_mean(tx.w_first * (a >> 22) + pl.nx * mv + tx.w_last * v1, dNx);
+                }
+            }
+        }
+        __syncthreads();
+        if (sample) {
+#pragma unroll
+            for (int rr = 0; rr < NR; rr++) {
+                const int f = max((int)ty[rr].first, y0), l = min((int)(ty[rr].first + ty[rr].count) - 1, y0 + nr - 1);
+                for (int y = f; y <= l; y++) {
+                    const uint32_t o = box_overlap((uint32_t)y, (uint32_t)jr[rr], pl.Ny, pl.ny);
+                    const uint32_t *row = rbuf + (y - y0) * 32;
+#pragma unroll
+                    for (int c = 0; c < 4; c++) acc[rr][c] += o * row[col[c]];
+                }
+            }
+        }
+        lp = lp_next;
+    }
+}
+
+template <int OUT, bool VEC, int EL = EL_LIB> __global__ __launch_bounds__(ROI_THREADS) void vpp_letterbox_p010_area_kernel(const LbBoxLaunch L) {
+    using T = typename OutT<OUT>::type;
+    typedef __attribute__((address_space(1))) uint8_t *GP; // the records hold GLOBAL addresses
+    const TileIndex tix = tile_index(L.tiles_x, L.tiles_y);
+    const int frame = tix.item, tyi = tix.tyi, txi = tix.txi;
+    if (frame >= L.n_frames) return;
+    const LbRec &r = L.r[frame]; // wave-uniform index: scalar loads
+
+    LaunchDesc d = {};
+    tile_desc<OUT, VEC>(L, r, d);
+    d.k.y_offset = 4.0f * d.k.y_offset; // the contract's scaled offsets (exact)
+    d.k.c_offset = 4.0f * d.k.c_offset;
+
+    const bool uv4 = (((uint32_t)r.uv | (uint32_t)r.pitch_uv) & 3u) == 0u;
+    T *const out = (T *)(GP)(uintptr_t)r.out;
+    const int lx = threadIdx.x & (ROI_TX - 1), ly = threadIdx.x >> ROI_TX_SHIFT;
+    const int j_first = roi_tile_col0(txi, L.dst_w, d.last_col0), i_first = tyi * ROI_TILE_H;
+    const int j0 = j_first + lx * PXW, i0 = i_first + ly * PXH;
+    const bool active = j0 < L.dst_w && i0 < L.dst_h && !(VEC && is_row_tail(d, j0));
+    const int ncol = VEC ? PXW : min(PXW, L.dst_w - j0);
+
+    // the part of the rectangle this tile covers (wave-uniform)
+    LbPart t;
+    tile_inner_range(j_first, tile_last(j_first, ROI_TILE_W, L.dst_w), r.left, r.width, t.a0, t.a1);
+    tile_inner_range(i_first, tile_last(i_first, ROI_TILE_H, L.dst_h), r.top, r.height, t.b0, t.b1);
+    float Uf[2] = { L.pad_u, L.pad_u }, Vf[2] = { L.pad_v, L.pad_v }, Yf[PXH][PXW];
+#pragma unroll
+    for (int rr = 0; rr < PXH; rr++)
+#pragma unroll
+        for (int c = 0; c < PXW; c++) Yf[rr][c] = L.pad_y;
+    if (t.a0 > t.a1 || t.b0 > t.b1) { // none of it: pad, through the colour expression and store of every sample
+        if (active) p010_store_tile<OUT, VEC, EL>(Yf, Uf, Vf, d, L.spec, out, i0, j0, ncol);
+        return;
+    }
+
+    // which chroma pairs of this lane's thread tile lie inside the rectangle; a thread tile wholly outside adds up nothing
+    const bool rows_in = i0 >= r.top && i0 < r.top + r.height;
+    bool in[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) in[c] = rows_in && j0 + 2 * c >= r.left && j0 + 2 * c < r.left + r.width;
+    const bool sample = active && (in[0] || in[1]);
+    const int buf_bytes = box_band_buffer(L.band, L.band_cpr);
+
+    { // luma
+        BoxPlane pl = { (const uint8_t *)(GP)(uintptr_t)r.y, r.pitch_y, 0, 0, 0, 0, (uint32_t)r.src_w, (uint32_t)r.width, (uint32_t)r.src_h, (uint32_t)r.height, t.a0, t.a1 - t.a0 + 1 };
+        box_span(t.a0, t.a1, r.src_w, r.width, pl.xlo, pl.xhi);
+        box_span(t.b0, t.b1, r.src_h, r.height, pl.ylo, pl.yhi);
+        roi_clamp(pl.xlo, pl.xhi, r.src_w);
+        roi_clamp(pl.ylo, pl.yhi, r.src_h);
+        int jr[PXH], col[PXW];
+#pragma unroll
+        for (int rr = 0; rr < PXH; rr++) jr[rr] = clampi(i0 - r.top + rr, t.b0, t.b1);
+#pragma unroll
+        for (int c = 0; c < PXW; c++) col[c] = clampi(j0 - r.left + c, t.a0, t.a1) - t.a0;
+        uint32_t acc[PXH][PXW] = {};
+        box_walk_plane<false, PXH>(pl, uv4, L.band, buf_bytes, sample, jr, col, acc);
+        const BoxDiv dv = box_div_of(64u * pl.Ny);
+#pragma unroll
+        for (int rr = 0; rr < PXH; rr++)
+#pragma unroll
+            for (int c = 0; c < PXW; c++) Yf[rr][c] = in[c >> 1] ? (float)box_sample(acc[rr][c], pl.Ny, dv) : L.pad_y;
+    }
+    if constexpr (!kLumaOnly<OUT>) {
+        BoxPlane pl = { (const uint8_t *)(GP)(uintptr_t)r.uv, r.pitch_uv, 0, 0, 0, 0, (uint32_t)r.src_w >> 1, (uint32_t)r.width >> 1, (uint32_t)r.src_h >> 1, (uint32_t)r.height >> 1, t.a0 >> 1, (t.a1 >> 1) - (t.a0 >> 1) + 1 };
+        box_span(t.a0 >> 1, t.a1 >> 1, r.src_w >> 1, r.width >> 1, pl.xlo, pl.xhi);
+        box_span(t.b0 >> 1, t.b1 >> 1, r.src_h >> 1, r.height >> 1, pl.ylo, pl.yhi);
+        roi_clamp(pl.xlo, pl.xhi, r.src_w >> 1);
+        roi_clamp(pl.ylo, pl.yhi, r.src_h >> 1);
+        const int jr[1] = { clampi((i0 - r.top) >> 1, t.b0 >> 1, t.b1 >> 1) }, cj0 = (j0 - r.left) >> 1;
+        int col[4];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            col[2 * c] = 2 * (clampi(cj0 + c, t.a0 >> 1, t.a1 >> 1) - (t.a0 >> 1));
+            col[2 * c + 1] = col[2 * c] + 1;
+        }
+        uint32_t acc[1][4] = {};
+        box_walk_plane<true, 1>(pl, uv4, L.band, buf_bytes, sample, jr, col, acc);
+        const BoxDiv dv = box_div_of(64u * pl.Ny);
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            Uf[c] = in[c] ? (float)box_sample(acc[0][2 * c], pl.Ny, dv) : L.pad_u;
+            Vf[c] = in[c] ? (float)box_sample(acc[0][2 * c + 1], pl.Ny, dv) : L.pad_v;
+        }
+    }
+    if (active) p010_store_tile<OUT, VEC, EL>(Yf, Uf, Vf, d, L.spec, out, i0, j0, ncol);
+}
+
+} // namespace tsvpp

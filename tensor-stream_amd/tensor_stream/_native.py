@@ -15,6 +15,7 @@ TSVPP_MAX_ROIS_SIZED = 48  # ... of tsvpp_convert_rois_sized (64-byte records)
 TSVPP_MAX_LETTERBOX = 32  # frames per launch of tsvpp_convert_letterbox
 TSVPP_MAX_LETTERBOX_P010 = 32  # ... of tsvpp_convert_letterbox_p010
 TSVPP_MAX_ROIS_P010 = 64  # boxes per launch of tsvpp_convert_rois_p010
+TSVPP_BOX_P010_MAX_SIDE, TSVPP_BOX_P010_MAX_TAPS = 16384, 17  # limits of tsvpp_convert_letterbox_p010_area
 TSVPP_MAX_WARPS = 32  # outputs per launch of tsvpp_convert_warp
 TSVPP_MAX_PERSP = 32  # outputs per launch of tsvpp_convert_perspective
 TSVPP_MAX_REMAPS = 32  # outputs per launch of tsvpp_convert_remap
@@ -111,6 +112,7 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_tensor_bytes", "tsvpp_convert_rois_tensor", "tsvpp_describe_rois_tensor", "tsvpp_convert_letterbox_tensor", "tsvpp_describe_letterbox_tensor",
            "tsvpp_convert_letterbox_area", "tsvpp_describe_letterbox_area", "tsvpp_letterbox_area_rows",
            "tsvpp_convert_letterbox_p010", "tsvpp_describe_letterbox_p010", "tsvpp_convert_rois_p010", "tsvpp_describe_rois_p010",
+           "tsvpp_convert_letterbox_p010_area", "tsvpp_describe_letterbox_p010_area", "tsvpp_box_p010_plane",
            "tsvpp_rois_sized_bytes", "tsvpp_convert_rois_sized", "tsvpp_describe_rois_sized", "tsvpp_convert_rois_sized_tensor", "tsvpp_describe_rois_sized_tensor",
            "tsvpp_rois_sized_tile",
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
@@ -209,6 +211,12 @@ def lib():
     L.tsvpp_convert_letterbox_p010.restype = i32
     L.tsvpp_describe_letterbox_p010.argtypes = [pp, ps, i32, ctypes.POINTER(P010), pc, i32, ctypes.c_char_p, ctypes.c_size_t]
     L.tsvpp_describe_letterbox_p010.restype = i32
+    L.tsvpp_convert_letterbox_p010_area.argtypes = L.tsvpp_convert_letterbox_p010.argtypes
+    L.tsvpp_convert_letterbox_p010_area.restype = i32
+    L.tsvpp_describe_letterbox_p010_area.argtypes = L.tsvpp_describe_letterbox_p010.argtypes
+    L.tsvpp_describe_letterbox_p010_area.restype = i32
+    L.tsvpp_box_p010_plane.argtypes = [vp, i32, i32, vp, i32, i32]
+    L.tsvpp_box_p010_plane.restype = i32
     L.tsvpp_convert_rois_p010.argtypes = [vp, i32, ctypes.POINTER(P010), i32, pr, pp, ps, ctypes.POINTER(vp), vp]  # (spec may be None)
     L.tsvpp_convert_rois_p010.restype = i32
     L.tsvpp_describe_rois_p010.argtypes = [pp, ps, i32, ctypes.POINTER(P010), i32, pr, i32, ctypes.c_char_p, ctypes.c_size_t]

@@ -366,20 +366,30 @@ class VideoProcessor:
         tensors; pad: (Y, U, V) as P010 samples, each 0..1023 ((64, 512, 512): black, (456, 512, 512): gray 114).  NEAREST and BILINEAR.  The samples keep their
         ten bits through the resize and the colour conversion: fp32 outputs are k / 1023, uint8 outputs min(255, (k + 2) >> 2).  Everything else -- rects, out,
         width / height, dtype / mean / std, the result (out, rects) -- as convert_letterbox."""
+        return self._convert_letterbox_p010("convert_letterbox_p010", ys, uvs, params, pad, rects, out, width, height, tensor_spec(dtype, mean, std))
+
+    def convert_letterbox_p010_area(self, ys, uvs, params, pad=(64, 512, 512), rects=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_letterbox_p010 for ResizeType.AREA (tsvpp_convert_letterbox_p010_area), same arguments and result: an exact integer box filter -- every
+        source sample is averaged into the output sample whose interval it overlaps, where BILINEAR point-samples one sample in nine at 1080p -> 640 and one in
+        36 at 4K.  Per plane and separable, in 32-bit integers (the row mean in 1/64 sample steps, then the column mean, each rounded to nearest): within
+        0.5 + 1/128 of the exact mean, a flat frame unchanged, no float and no dependence on order.  An axis that is not shrunk gets box coverage (equal sizes:
+        the identity).  A frame side above 16384 or more than 17 taps on an axis (ratios above 16) is refused, as is any other resize type."""
+        return self._convert_letterbox_p010("convert_letterbox_p010_area", ys, uvs, params, pad, rects, out, width, height, tensor_spec(dtype, mean, std))
+
+    def _convert_letterbox_p010(self, call, ys, uvs, params, pad, rects, out, width, height, spec):
         p = params.parameters if isinstance(params, FrameParameters) else params
-        spec = tensor_spec(dtype, mean, std)
         n = len(ys)
         if n == 0:
-            raise RuntimeError("-3: convert_letterbox_p010 needs at least one frame")
+            raise RuntimeError(f"-3: {call} needs at least one frame")
         widths, heights = _per_frame(width, n), _per_frame(height, n)
         frames = (N.P010 * n)(*[_p010_frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(n)])
         if out is None:
-            out = self._alloc_items(p, n, spec, "convert_letterbox_p010 needs an even, positive canvas size")
+            out = self._alloc_items(p, n, spec, f"{call} needs an even, positive canvas size")
         recs = None if rects is None else _rects(rects, n)
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(self._lib.tsvpp_convert_letterbox_p010(self._ctx, n, frames, ctypes.byref(p), None if spec is None else ctypes.byref(spec), recs, int(pad[0]), int(pad[1]),
-                                                       int(pad[2]), outs, stream))
+        N.check(getattr(self._lib, "tsvpp_" + call)(self._ctx, n, frames, ctypes.byref(p), None if spec is None else ctypes.byref(spec), recs, int(pad[0]), int(pad[1]),
+                                                    int(pad[2]), outs, stream))
         if recs is None:
             used = [letterbox_rect(frames[i].width, frames[i].height, p.dst_width, p.dst_height) for i in range(n)]
         else:
@@ -841,6 +851,20 @@ def describe_letterbox_p010(params, frames, rects=None, aligned_outputs=True, dt
     spec = tensor_spec(dtype, mean, std)
     N.check(N.lib().tsvpp_describe_letterbox_p010(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf,
                                                   len(buf)))
+    return _parse_selection(buf.value.decode())
+
+
+def describe_letterbox_p010_area(params, frames, rects=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_letterbox_p010_area of this request would launch, as a dict (tsvpp_describe_letterbox_p010_area: describe_letterbox_p010's keys, then
+    taps = "XxY", the largest tap counts per axis, and band = the source rows a workgroup stages per band) -- host logic only, works without a GPU."""
+    p = params.parameters if isinstance(params, FrameParameters) else params
+    recs = [N.P010(None, None, r.pitch_y, r.pitch_uv, r.width, r.height) for r in _geometry_records(frames)]
+    fr = (N.P010 * max(len(recs), 1))(*recs)
+    rc = None if rects is None else _rects(rects, len(recs))
+    buf = ctypes.create_string_buffer(512)
+    spec = tensor_spec(dtype, mean, std)
+    N.check(N.lib().tsvpp_describe_letterbox_p010_area(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0,
+                                                       buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

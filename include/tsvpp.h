@@ -407,7 +407,8 @@ int tsvpp_describe_letterbox_area(const tsvpp_params *p, const tsvpp_tensor_spec
  * row too) at or above TSVPP_SOURCE_SPAN_LIMIT; then, with a spec, rules 2 and 3 of the tensor entry points.
  * tsvpp_describe_letterbox_p010 prints tsvpp_describe_letterbox's keys with "src=p010" in front of frames=, kernel=vpp_letterbox_p010<...> /
  * vpp_letterbox_p010_tensor<...> and limit=32; lds= counts the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks).
- * Not here, each a follow-up: BICUBIC on P010, and AREA for the boxes of tsvpp_convert_rois_p010 (the letterbox has it: tsvpp_convert_letterbox_p010_area, below);
+ * Not here, each a follow-up: BICUBIC for the letterbox (the boxes have it: tsvpp_convert_rois_p010_bicubic, below), and AREA for the boxes of
+ * tsvpp_convert_rois_p010 (the letterbox has it: tsvpp_convert_letterbox_p010_area, below);
  * P010 through tsvpp_convert, the per-box-size, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
  * presets (the coefficient block already lets a caller set them); 10-bit or 16-bit integer outputs; merged tensors. */
 typedef struct tsvpp_p010 {
@@ -480,12 +481,56 @@ int tsvpp_box_p010_plane(const uint16_t *src, int src_w, int src_h, uint16_t *ds
  * tsvpp_describe_rois_p010 prints tsvpp_describe_rois's keys with "src=p010" in front of rois=, kernel=vpp_rois_p010<...> / vpp_rois_p010_tensor<...> and
  * limit=64; lds= and staged= count the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks): a tile that the
  * 8-bit call stages may gather here.
- * Not here: what tsvpp_convert_letterbox_p010 lists, and odd box origins. */
+ * Not here: what tsvpp_convert_letterbox_p010 lists -- BICUBIC for boxes is a call of its own, tsvpp_convert_rois_p010_bicubic, below -- and odd box origins. */
 #define TSVPP_MAX_ROIS_P010 64 /* boxes per launch; more are split */
 int tsvpp_convert_rois_p010(tsvpp_ctx *ctx, int n_frames, const tsvpp_p010 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
                             const tsvpp_tensor_spec *spec /* may be NULL */, void *const *outs, void *stream);
 int tsvpp_describe_rois_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_p010 *frames, int n_rois,
                              const tsvpp_roi *rois, int aligned_outputs, char *buf, size_t buf_len);
+
+/* ---- 10-bit sources: tsvpp_convert_rois_p010_bicubic ----
+ * tsvpp_convert_rois_p010 with a cubic resize, the filter a 40-80 pixel face, plate or text box should get on its way UP to 112 x 112 or 224 x 224, where BILINEAR
+ * visibly softens it -- on all ten bits: narrowing to 8 bits first drops the two low bits in front of the one filter that overshoots and so amplifies
+ * quantisation steps.  Signatures as the pair above.  Everything not stated here is tsvpp_convert_rois_p010's, word for word: tsvpp_p010 frames, boxes with even
+ * origins and sizes, "no word outside the box influences its output", 64 boxes per launch with their records by value in the kernarg segment, no allocation, no
+ * copy, legal under stream capture, the colour expression with the offsets scaled by four, the G-term option and the coefficient block, the stored forms
+ * k / 1023 and min(255, (k + 2) >> 2), the tensor forms with a spec, and the status rules in their order.  p->resize_type must be TSVPP_BICUBIC; any other type
+ * is TSVPP_UNSUPPORTED (and tsvpp_convert_rois_p010 keeps answering TSVPP_UNSUPPORTED for BICUBIC).
+ * The 8-bit calls' BICUBIC is the reference's arithmetic (fp64 four-term sums, pow, round-half-away) and exists to match its goldens.  The reference has no 10-bit
+ * path, so this arithmetic is our own, chosen to be exact, order-free and cheap on gfx950:
+ *   resize   per plane and separable, in signed 32-bit integers: Y from the box's W x H samples to w x h, U and V each from W/2 x H/2 to w/2 x h/2.  One axis with
+ *            N source samples and n outputs; output j: t = (2 j + 1) N - n (the pixel-centre alignment (j + 1/2) N / n - 1/2 over the denominator 2 n),
+ *            p = floor(t / (2 n)) (-1 exactly when t < 0), rem = t - 2 n p in [0, 2 n), phase F = floor(32 rem / n) in 0..63, G = 64 - F.  The four weights are
+ *            Keys' cubic with a = -3/4 at x = F / 64, times 2^20 -- exact integers that sum to 2^20:
+ *                w0 = -3 F G^2    w1 = 5 F^3 - 576 F^2 + 2^20    w2 = 5 G^3 - 576 G^2 + 2^20    w3 = -3 F^2 G
+ *            on the samples at clamp(p - 1 + k, 0, N - 1), k = 0..3: the clamp is to the BOX, never to the frame.  Horizontal pass, per source row:
+ *            h = (sum w_k s_k + 2^19) >> 20 -- an arithmetic shift, i.e. a floor -- NOT clamped.  Vertical pass, on the h values:
+ *            k = clamp((sum w_k h_k + 2^19) >> 20, 0, 1023).  k takes the place of the BILINEAR call's truncated blend.
+ *   bounds   |sum_h| <= 1023 * 1.375 * 2^20 < 2^31 (1.375: the largest sum of |w| / 2^20, at F = 32); h lies in [-192, 1215], which fits 16 bits;
+ *            |sum_v| <= 1215.5 * 1.375 * 2^20 < 2^31.
+ *   it follows  there is no float and no dependence on order; a flat frame comes back unchanged; N = n is the identity (F = 0); an exact 2 x up-scale has the
+ *            phases 16 and 48; k lies within 0.5 + 0.6875 of the real-valued separable cubic at the quantised phase (0.6875: half a unit of h-rounding times
+ *            the largest sum of |w|, 1.375).
+ * This is a 4-tap interpolator, not an anti-aliased filter: beyond a ratio near 2 it aliases as the 8-bit calls' BICUBIC does.  AREA for P010 boxes is still a
+ * follow-up.
+ *   limits   TSVPP_UNSUPPORTED, decided before a device is touched and returned alike by describe: a box side or an output side above
+ *            TSVPP_CUBIC_P010_MAX_SIDE, and N > TSVPP_CUBIC_P010_MAX_RATIO * n on an axis of either plane.  The ratio limit bounds the intermediate rows a tile
+ *            keeps in LDS (32 * 8 + 3 rows of 64 bytes); it is not a quality recommendation.  A request whose largest tile does not fit the workgroup's LDS
+ *            budget even with one-row bands is TSVPP_UNSUPPORTED too; at the default budget no request within the limits is.
+ * tsvpp_describe_rois_p010_bicubic prints tsvpp_describe_rois_p010's keys with mode=bicubic and kernel=vpp_rois_p010_bicubic<...> /
+ * vpp_rois_p010_bicubic_tensor<...> (staged= counts every box: every tile walks its footprint through LDS; there is no gathering variant), then
+ * "band=<source rows per band>"; lds= is the intermediate rows and the two band buffers.
+ * tsvpp_cubic_p010_plane is the contract's executable form, on the host: it resizes one plane of SAMPLES (0..1023, src_w x src_h, rows of src_w) to dst_w x dst_h
+ * with the functions the kernel is compiled from (csrc/vpp_cubic_p010.h).  Statuses as tsvpp_box_p010_plane's, with TSVPP_CUBIC_P010_MAX_SIDE; the ratio limit
+ * is the kernel's and does not apply.
+ * Not here: BICUBIC for the P010 letterbox, per-box output sizes, and what tsvpp_convert_rois_p010 lists. */
+#define TSVPP_CUBIC_P010_MAX_SIDE 16384
+#define TSVPP_CUBIC_P010_MAX_RATIO 8
+int tsvpp_convert_rois_p010_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_p010 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
+                                    const tsvpp_tensor_spec *spec /* may be NULL */, void *const *outs, void *stream);
+int tsvpp_describe_rois_p010_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_p010 *frames, int n_rois,
+                                     const tsvpp_roi *rois, int aligned_outputs, char *buf, size_t buf_len);
+int tsvpp_cubic_p010_plane(const uint16_t *src, int src_w, int src_h, uint16_t *dst, int dst_w, int dst_h);
 
 /* DEBUG ONLY (tests), host only: tsvpp_roi_area_rows as tsvpp_convert_letterbox_area's kernel produces the rows -- the generator begun at the jump start of
  * (scale, first), the largest multiple of the pattern's period that is <= first (0 where the pattern does not close in 1 .. first), which *start receives.

@@ -163,6 +163,13 @@ public:
     int ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);
     int ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                         const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertRoisP010 with a cubic resize (tsvpp_convert_rois_p010_bicubic, include/tsvpp.h): a separable Keys cubic in 32-bit integers on all ten bits, for small
+    // boxes that go UP to the network's input size.  options.resize.type must be BICUBIC; a box may be at most 8 times the output on an axis and no side above
+    // 16384.  Plain, and with a tensor spec (null: the plain call).
+    int ConvertRoisP010Bicubic(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                               std::string consumerName);
+    int ConvertRoisP010Bicubic(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                               const tsvpp_tensor_spec *spec, std::string consumerName);
     // Boxes that each go to their OWN output size (tsvpp_convert_rois_sized, include/tsvpp.h; not in the reference): text lines of one height and their own widths,
     // the levels of a pyramid, the inputs of several heads behind one detector pass.  rois[i] carries the box and its dst_width x dst_height; deviceOuts[i] holds
     // tsvpp_rois_sized_bytes bytes.  options.resize.width and height must be 0 (the sizes are the boxes') and options.crop empty; options.resize.type is NEAREST,

@@ -49,4 +49,8 @@ inline int p010_planes_error(int n, const tsvpp_nv12 *fr) {
     return TSVPP_OK;
 }
 
+// (tsvpp_rois_p010.cpp) the status of a P010 ROI request, NEAREST / BILINEAR; `converting`: the planes are read.  tsvpp_rois_p010_bicubic.cpp asks it with a type
+// it accepts, so that every rule in front of the type is this one's
+int p010_rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *fr, int n_rois, const tsvpp_roi *rois, bool converting, RoiPlan &pl);
+
 } // namespace tsvpp

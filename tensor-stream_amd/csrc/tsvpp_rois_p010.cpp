@@ -8,10 +8,10 @@
 
 using namespace tsvpp;
 
-namespace {
+namespace tsvpp {
 
 // The status of a request, in the order that is part of the ABI: the ROI call's, with the P010 rules in its two classes
-// (`converting`: the planes are read, so their addresses must hold 16-bit words)
+// (`converting`: the planes are read, so their addresses must hold 16-bit words).  Declared in tsvpp_p010.h: the BICUBIC call asks it too
 int p010_rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *fr, int n_rois, const tsvpp_roi *rois, bool converting, RoiPlan &pl) {
     if (!p || !fr || !rois || n_frames <= 0 || n_rois <= 0) return TSVPP_ERROR;
     if (p010_frames_error(n_frames, fr) != TSVPP_OK) return TSVPP_ERROR;
@@ -28,6 +28,10 @@ int p010_rois_plan(const tsvpp_params *p, int n_frames, const tsvpp_nv12 *fr, in
     }
     return TSVPP_OK;
 }
+
+} // namespace tsvpp
+
+namespace {
 
 // The request of one call, as tsvpp_tiles.h asks for it
 struct RoiP010Path {

@@ -403,20 +403,28 @@ class VideoProcessor:
         convert_rois.  NEAREST and BILINEAR; a box needs an even left and top as well as an even width and height.  Output i equals, bit for bit,
         convert_letterbox_p010 of a frame that consists of box i alone with the rectangle equal to the canvas: fp32 outputs are k / 1023, uint8 outputs
         min(255, (k + 2) >> 2)."""
+        return self._convert_rois_p010("convert_rois_p010", ys, uvs, rois, params, out, width, height, tensor_spec(dtype, mean, std))
+
+    def convert_rois_p010_bicubic(self, ys, uvs, rois, params, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_rois_p010 with a cubic resize (tsvpp_convert_rois_p010_bicubic): a separable Keys cubic (a = -3/4) in 32-bit integers on all ten bits, the
+        filter for small boxes that go UP to the network's input size.  Arguments and result as convert_rois_p010; params' resize type must be BICUBIC; a box
+        may be at most 8 times the output on an axis and no side above 16384.  A 4-tap interpolator, not an anti-aliased filter."""
+        return self._convert_rois_p010("convert_rois_p010_bicubic", ys, uvs, rois, params, out, width, height, tensor_spec(dtype, mean, std))
+
+    def _convert_rois_p010(self, name, ys, uvs, rois, params, out, width, height, spec):
         p = params.parameters if isinstance(params, FrameParameters) else params
-        spec = tensor_spec(dtype, mean, std)
         ys, uvs, boxes = _normalize_rois(ys, uvs, rois)
         widths, heights = _per_frame(width, len(ys)), _per_frame(height, len(ys))
         frames = (N.P010 * len(ys))(*[_p010_frame(ys[i], uvs[i], widths[i], heights[i]) for i in range(len(ys))])
         n = len(boxes)
         if n == 0:
-            raise RuntimeError("-3: convert_rois_p010 needs at least one box")
+            raise RuntimeError("-3: %s needs at least one box" % name)
         if out is None:
-            out = self._alloc_items(p, n, spec, "convert_rois_p010 needs an even, positive output size")
+            out = self._alloc_items(p, n, spec, name + " needs an even, positive output size")
         recs = (N.Roi * n)(*[N.Roi(*b) for b in boxes])
         outs = (ctypes.c_void_p * n)(*[out[i].data_ptr() for i in range(n)])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(self._lib.tsvpp_convert_rois_p010(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), None if spec is None else ctypes.byref(spec), outs, stream))
+        N.check(getattr(self._lib, "tsvpp_" + name)(self._ctx, len(ys), frames, n, recs, ctypes.byref(p), None if spec is None else ctypes.byref(spec), outs, stream))
         return out
 
     def _convert_letterbox(self, area, ys, uvs, params, pad, rects, out, width, height, spec):
@@ -871,15 +879,23 @@ def describe_letterbox_p010_area(params, frames, rects=None, aligned_outputs=Tru
 def describe_rois_p010(params, frames, rois, aligned_outputs=True, dtype=None, mean=None, std=None):
     """What a convert_rois_p010 of this request would launch, as a dict (tsvpp_describe_rois_p010: describe_rois's keys with src = "p010"; lds and staged count
     the footprints as 16-bit words) -- host logic only, works without a GPU.  Arguments as describe_rois; pitches are in BYTES (0: 2 * width)."""
+    return _describe_rois_p010(N.lib().tsvpp_describe_rois_p010, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
+
+
+def describe_rois_p010_bicubic(params, frames, rois, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_rois_p010_bicubic of this request would launch, as a dict (tsvpp_describe_rois_p010_bicubic: describe_rois_p010's keys with mode =
+    "bicubic", then band = the source rows a workgroup stages per band; staged counts every box) -- host logic only, works without a GPU."""
+    return _describe_rois_p010(N.lib().tsvpp_describe_rois_p010_bicubic, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
+
+
+def _describe_rois_p010(entry, params, frames, rois, aligned_outputs, spec):
     p = params.parameters if isinstance(params, FrameParameters) else params
     recs = [N.P010(None, None, r.pitch_y, r.pitch_uv, r.width, r.height) for r in _geometry_records(frames)]
     _, _, boxes = _normalize_rois([None] * len(recs), [None] * len(recs), rois)
     fr = (N.P010 * max(len(recs), 1))(*recs)
     bx = (N.Roi * max(len(boxes), 1))(*[N.Roi(*b) for b in boxes])
     buf = ctypes.create_string_buffer(512)
-    spec = tensor_spec(dtype, mean, std)
-    N.check(N.lib().tsvpp_describe_rois_p010(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0,
-                                             buf, len(buf)))
+    N.check(entry(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, len(boxes), bx, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

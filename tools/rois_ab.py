@@ -6,6 +6,8 @@ before tsvpp_convert_rois) against (b) ONE tsvpp_convert_rois -- on one stream, 
     python tools/rois_ab.py --area [--out profiles/rois_area_ab.txt]      the AREA leg: tsvpp_convert_rois_area (see area_main)
     python tools/rois_ab.py --dtype f16 [--mean a,b,c] [--std a,b,c]      the tensor legs: tsvpp_convert_rois_tensor (see tensor_main; appends to profiles/tensor_ab.txt)
     python tools/rois_ab.py --p010 [--out profiles/rois_p010_ab.txt]      10-bit sources: tsvpp_convert_rois_p010 against narrowing + tsvpp_convert_rois (see p010_main)
+    python tools/rois_ab.py --p010 --bicubic [--out profiles/rois_p010_bicubic_ab.txt]   the same with BICUBIC: tsvpp_convert_rois_p010_bicubic, a BILINEAR leg (d) and
+                                                                          a second set of small boxes that go UP to 112 x 112
 
 Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the
 MEDIAN block, the spread (min .. max of the blocks) is printed beside it.  Every iteration takes the next frame of a pool of 96 distinct 1080p frames
@@ -293,6 +295,17 @@ P010_CONFIGS = [("224x224 BILINEAR BGR24 planar fp32", (224, 224), 2, 0, True, N
                 ("112x112 BILINEAR RGB24 merged uint8", (112, 112), 1, 1, False, None),
                 ("224x224 BILINEAR RGB24 planar fp16, ImageNet mean / std", (224, 224), 1, 0, True, "f16")]
 P010_PITCH = 4096  # bytes: what a decoder hands over for 1080p
+SMALL = "112x112 BILINEAR RGB24 merged uint8, boxes 32 .. 96 (up-scaling)"  # --bicubic: the case the cubic call exists for
+
+
+def small_boxes_for(n, seed):
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        bw, bh = 2 * int(rng.integers(16, 49)), 2 * int(rng.integers(16, 49))  # sides 32 .. 96
+        l, t = int(rng.integers(0, W - bw)), int(rng.integers(0, H - bh))
+        out.append((l, t, l + bw, t + bh))
+    return out
 
 
 def p010_main(a):
@@ -303,8 +316,11 @@ def p010_main(a):
           tsvpp_convert_rois (the fp16 configuration: tsvpp_convert_rois_tensor)
       (c) the 8-bit call of (b) alone, on frames narrowed beforehand
     Every leg is parity-checked, every box bit for bit, before and after its timing: (a) against tests/p010_util.py, (b) and (c) against the CPU oracle on the
-    narrowed planes (tests/tensor_util.py for fp16)."""
+    narrowed planes (tests/tensor_util.py for fp16).
+    --bicubic: (a) is tsvpp_convert_rois_p010_bicubic (parity against tests/p010_cubic_util.py), (b) and (c) run the 8-bit BICUBIC, leg (d) is
+    tsvpp_convert_rois_p010 with BILINEAR on the same boxes, and a fourth configuration takes boxes with sides 32 .. 96 up to 112 x 112."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import p010_cubic_util as Q
     import p010_util as M
     import tensor_util as T
     O.build()
@@ -327,32 +343,43 @@ def p010_main(a):
     fr8c = [(N.NV12 * 1)(N.NV12(ys8[k].data_ptr(), uvs8[k].data_ptr(), W, W, W, H)) for k in range(nf)]
     fr8b = [(N.NV12 * 1)(N.NV12(by8[k].data_ptr(), buv8[k].data_ptr(), W, W, W, H)) for k in range(nf)]
     pool_mib = nf * (P010_PITCH * H * 3 // 2) >> 20
-    lines = [f"# tools/rois_ab.py --p010: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {nf} x 1080p P010 at pitch {P010_PITCH} ({pool_mib} MiB), "
+    cubic = a.bicubic
+    rt, call_a = (2, "tsvpp_convert_rois_p010_bicubic") if cubic else (1, "tsvpp_convert_rois_p010")
+    convert_a, describe_a, legs = getattr(L, call_a), (ts.describe_rois_p010_bicubic if cubic else ts.describe_rois_p010), ("abcd" if cubic else "abc")
+    lines = [f"# tools/rois_ab.py --p010{' --bicubic' if cubic else ''}: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {nf} x 1080p P010 at pitch {P010_PITCH} ({pool_mib} MiB), "
              f"median of {a.repeats} blocks of {a.iters} iterations, one stream",
-             "# (a) = 1 x tsvpp_convert_rois_p010   (b) = torch >> 8 + narrowing copy of both planes, then 1 x tsvpp_convert_rois   (c) = the 8-bit call alone on frames narrowed beforehand",
+             f"# (a) = 1 x {call_a}   (b) = torch >> 8 + narrowing copy of both planes, then 1 x tsvpp_convert_rois   (c) = the 8-bit call alone on frames narrowed beforehand"
+             + ("   (d) = 1 x tsvpp_convert_rois_p010, BILINEAR" if cubic else ""),
              "# us per call, [min .. max of the blocks]; staged = boxes of the P010 call whose every tile stages in LDS / of the 8-bit call"]
     met = True
-    for name, dst, fcc, planes, norm, dt in P010_CONFIGS:
-        fp = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=1, pixel_format=fcc, planes_pos=planes, normalization=norm)
+    for name, dst, fcc, planes, norm, dt in P010_CONFIGS + ([(SMALL, *P010_CONFIGS[1][1:])] if cubic else []):
+        small, name = name == SMALL, (name.replace("BILINEAR", "BICUBIC") if cubic else name)
+        fp = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=rt, pixel_format=fcc, planes_pos=planes, normalization=norm)
         p = fp.parameters
+        p_bil = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=1, pixel_format=fcc, planes_pos=planes, normalization=norm).parameters
         tdt = None if dt is None else T.TORCH[dt]
         spec = None if dt is None else ts.tensor_spec(dtype=tdt, mean=T.IMAGENET[0], std=T.IMAGENET[1])
         kw = {} if dt is None else dict(dtype=tdt, mean=T.IMAGENET[0], std=T.IMAGENET[1])
         sref = None if spec is None else ctypes.byref(spec)
         out_bytes = 3 * dst[0] * dst[1] * (2 if dt else (4 if norm else 1))
-        lines += ["", f"## {name}", f"{'n':>3} | {'(a) us':>8} {'spread':>15} | {'(b) us':>8} {'spread':>15} | {'(c) us':>8} {'spread':>15} | {'b / a':>6} {'a / c':>6} | {'staged':>9} | a < b by more than (b)'s spread"]
+        lines += ["", f"## {name}", f"{'n':>3} | {'(a) us':>8} {'spread':>15} | {'(b) us':>8} {'spread':>15} | {'(c) us':>8} {'spread':>15} | {'b / a':>6} {'a / c':>6} | {'staged':>9} | a < b by more than (b)'s spread"
+                  + (f" | {'(d) us':>8} {'spread':>15} {'a / d':>6}" if cubic else "")]
         for n in [int(v) for v in a.ns.split(",")]:
-            boxes = [(l & ~1, t & ~1, (l & ~1) + r - l, (t & ~1) + b - t) for l, t, r, b in boxes_for(n, seed=100 + n)]
+            boxes = [(l & ~1, t & ~1, (l & ~1) + r - l, (t & ~1) + b - t) for l, t, r, b in (small_boxes_for if small else boxes_for)(n, seed=100 + n)]
             sets = max(2, min(64, (300 << 20) // (n * out_bytes) + 1))
             pool = [vpp._alloc(p, dst[0], dst[1], n, tdt) if dt else vpp._alloc(p, dst[0], dst[1], n) for _ in range(sets)]
             recs = (N.Roi * n)(*[N.Roi(0, *b) for b in boxes])
             out_arrs = [(ctypes.c_void_p * n)(*[pool[s][i].data_ptr() for i in range(n)]) for s in range(sets)]
             ctx, pref = vpp._ctx, ctypes.byref(p)
-            d16 = ts.describe_rois_p010(fp, [(W, H, P010_PITCH)], boxes, **kw)["staged"]
+            d16 = describe_a(fp, [(W, H, P010_PITCH)], boxes, **kw)["staged"]
             d8 = ts.describe_rois(fp, [(W, H)], boxes, **kw)["staged"]
 
             def leg_a(k):
-                if L.tsvpp_convert_rois_p010(ctx, 1, fr16[k % nf], n, recs, pref, sref, out_arrs[k % sets], raw) != 0:
+                if convert_a(ctx, 1, fr16[k % nf], n, recs, pref, sref, out_arrs[k % sets], raw) != 0:
+                    raise RuntimeError(call_a + " failed")
+
+            def leg_d(k):
+                if L.tsvpp_convert_rois_p010(ctx, 1, fr16[k % nf], n, recs, ctypes.byref(p_bil), sref, out_arrs[k % sets], raw) != 0:
                     raise RuntimeError("tsvpp_convert_rois_p010 failed")
 
             def rois8(frames, k):
@@ -373,23 +400,25 @@ def p010_main(a):
             def parity(leg, k):
                 f, got = k % nf, pool[k % sets]
                 torch.cuda.synchronize()
-                if leg == "a":
+                if leg in "ad":
                     y, uv = ys[f].cpu().numpy().view(np.uint16), uvs[f].cpu().numpy().view(np.uint16)
                 else:
                     y, uv = ys8[f].cpu().numpy(), uvs8[f].cpu().numpy()
                 for i, (l, t, r, b) in enumerate(boxes):
-                    if leg == "a":
-                        k10 = M.channels(*M.virtual_frame(y[t:b, l:r], uv[t // 2:b // 2, l:r], r - l, b - t, (0, 0, *dst), dst, M.BILINEAR, (0, 0, 0)), fcc)
+                    if leg in "ad":
+                        yuv = Q.planes(y[t:b, l:r], uv[t // 2:b // 2, l:r], dst) if cubic and leg == "a" else \
+                            M.virtual_frame(y[t:b, l:r], uv[t // 2:b // 2, l:r], r - l, b - t, (0, 0, *dst), dst, M.BILINEAR, (0, 0, 0))
+                        k10 = M.channels(*yuv, fcc)
                         ref = M.stored(k10, planes, norm) if dt is None else T.expected(M.quotient(k10), 3, T.IMAGENET, dt)
                     else:
-                        q = O.convert(y[t:b, l:r], uv[t // 2:b // 2, l:r], dst=dst, resize_type=1, fourcc=fcc, planes=planes, normalization=norm, nthreads=8)[0]
+                        q = O.convert(y[t:b, l:r], uv[t // 2:b // 2, l:r], dst=dst, resize_type=rt, fourcc=fcc, planes=planes, normalization=norm, nthreads=8)[0]
                         ref = q.view(np.uint8).ravel() if dt is None else T.expected(q, 3, T.IMAGENET, dt)
                     if not np.array_equal(T.bits(got[i]), ref):
                         raise SystemExit(f"PARITY FAILURE: leg ({leg}) {name} n={n} box {i} {(l, t, r, b)}")
 
             res = {}
             with torch.cuda.stream(stream):
-                for leg, fn in (("a", leg_a), ("b", leg_b), ("c", leg_c)):
+                for leg, fn in (("a", leg_a), ("b", leg_b), ("c", leg_c), ("d", leg_d))[:len(legs)]:
                     for t in pool:
                         t.zero_()
                     fn(0)
@@ -401,11 +430,12 @@ def p010_main(a):
             sp = lambda v: f"{min(v):7.2f}..{max(v):<6.2f}"
             ok = m["b"] - m["a"] > max(res["b"]) - min(res["b"])
             met = met and ok
-            lines.append(f"{n:>3} | " + " | ".join(f"{m[k]:8.2f} {sp(res[k])}" for k in "abc") + f" | {m['b'] / m['a']:6.2f} {m['a'] / m['c']:6.2f} | {d16:>3} / {d8:<3} | {'met' if ok else 'NOT MET'}")
+            lines.append(f"{n:>3} | " + " | ".join(f"{m[k]:8.2f} {sp(res[k])}" for k in "abc") + f" | {m['b'] / m['a']:6.2f} {m['a'] / m['c']:6.2f} | {d16:>3} / {d8:<3} | {'met' if ok else 'NOT MET'}"
+                         + (f"{'':>27} | {m['d']:8.2f} {sp(res['d'])} {m['a'] / m['d']:6.2f}" if cubic else ""))
             print(lines[-1], flush=True)
             del pool
             torch.cuda.empty_cache()
-    lines += ["", "# parity: every leg bit-exact on every box before and after its timing -- (a) against tests/p010_util.py, (b) and (c) against the CPU oracle on the narrowed planes",
+    lines += ["", "# parity: every leg bit-exact on every box before and after its timing -- (a) against tests/p010_" + ("cubic_util.py, (d) against tests/p010_" if cubic else "") + "util.py, (b) and (c) against the CPU oracle on the narrowed planes",
               f"# expectation ((a) faster than (b) in every row by more than the spread of (b)'s blocks): {'met' if met else 'NOT MET in the rows marked'}"]
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -419,6 +449,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--area", action="store_true", help="the AREA leg (tsvpp_convert_rois_area); default output profiles/rois_area_ab.txt")
     ap.add_argument("--p010", action="store_true", help="10-bit sources (tsvpp_convert_rois_p010); default output profiles/rois_p010_ab.txt, frame pool 48")
+    ap.add_argument("--bicubic", action="store_true", help="with --p010: tsvpp_convert_rois_p010_bicubic; default output profiles/rois_p010_bicubic_ab.txt")
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--iters", type=int, default=50)
@@ -430,7 +461,7 @@ def main():
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
     if a.p010:
-        a.out = a.out or os.path.join(ROOT, "profiles", "rois_p010_ab.txt")
+        a.out = a.out or os.path.join(ROOT, "profiles", "rois_p010_bicubic_ab.txt" if a.bicubic else "rois_p010_ab.txt")
         if a.frames > 48:  # 48 P010 frames at pitch 4096: 303 MiB
             print(f"--p010: frame pool of 48 frames (303 MiB) instead of --frames {a.frames}", flush=True)
             a.frames = 48

@@ -407,8 +407,8 @@ int tsvpp_describe_letterbox_area(const tsvpp_params *p, const tsvpp_tensor_spec
  * row too) at or above TSVPP_SOURCE_SPAN_LIMIT; then, with a spec, rules 2 and 3 of the tensor entry points.
  * tsvpp_describe_letterbox_p010 prints tsvpp_describe_letterbox's keys with "src=p010" in front of frames=, kernel=vpp_letterbox_p010<...> /
  * vpp_letterbox_p010_tensor<...> and limit=32; lds= counts the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks).
- * Not here, each a follow-up: BICUBIC for the letterbox (the boxes have it: tsvpp_convert_rois_p010_bicubic, below), and AREA for the boxes of
- * tsvpp_convert_rois_p010 (the letterbox has it: tsvpp_convert_letterbox_p010_area, below);
+ * Not here, each a follow-up: BICUBIC for the letterbox (the boxes have it: tsvpp_convert_rois_p010_bicubic, below; AREA is a call of its own for the letterbox
+ * and for boxes: tsvpp_convert_letterbox_p010_area and tsvpp_convert_rois_p010_area, below);
  * P010 through tsvpp_convert, the per-box-size, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
  * presets (the coefficient block already lets a caller set them); 10-bit or 16-bit integer outputs; merged tensors. */
 typedef struct tsvpp_p010 {
@@ -481,7 +481,8 @@ int tsvpp_box_p010_plane(const uint16_t *src, int src_w, int src_h, uint16_t *ds
  * tsvpp_describe_rois_p010 prints tsvpp_describe_rois's keys with "src=p010" in front of rois=, kernel=vpp_rois_p010<...> / vpp_rois_p010_tensor<...> and
  * limit=64; lds= and staged= count the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks): a tile that the
  * 8-bit call stages may gather here.
- * Not here: what tsvpp_convert_letterbox_p010 lists -- BICUBIC for boxes is a call of its own, tsvpp_convert_rois_p010_bicubic, below -- and odd box origins. */
+ * Not here: what tsvpp_convert_letterbox_p010 lists -- BICUBIC and AREA for boxes are calls of their own, tsvpp_convert_rois_p010_bicubic and
+ * tsvpp_convert_rois_p010_area, below -- and odd box origins. */
 #define TSVPP_MAX_ROIS_P010 64 /* boxes per launch; more are split */
 int tsvpp_convert_rois_p010(tsvpp_ctx *ctx, int n_frames, const tsvpp_p010 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
                             const tsvpp_tensor_spec *spec /* may be NULL */, void *const *outs, void *stream);
@@ -511,8 +512,8 @@ int tsvpp_describe_rois_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spe
  *   it follows  there is no float and no dependence on order; a flat frame comes back unchanged; N = n is the identity (F = 0); an exact 2 x up-scale has the
  *            phases 16 and 48; k lies within 0.5 + 0.6875 of the real-valued separable cubic at the quantised phase (0.6875: half a unit of h-rounding times
  *            the largest sum of |w|, 1.375).
- * This is a 4-tap interpolator, not an anti-aliased filter: beyond a ratio near 2 it aliases as the 8-bit calls' BICUBIC does.  AREA for P010 boxes is still a
- * follow-up.
+ * This is a 4-tap interpolator, not an anti-aliased filter: beyond a ratio near 2 it aliases as the 8-bit calls' BICUBIC does; boxes that go down take
+ * tsvpp_convert_rois_p010_area, below.
  *   limits   TSVPP_UNSUPPORTED, decided before a device is touched and returned alike by describe: a box side or an output side above
  *            TSVPP_CUBIC_P010_MAX_SIDE, and N > TSVPP_CUBIC_P010_MAX_RATIO * n on an axis of either plane.  The ratio limit bounds the intermediate rows a tile
  *            keeps in LDS (32 * 8 + 3 rows of 64 bytes); it is not a quality recommendation.  A request whose largest tile does not fit the workgroup's LDS
@@ -531,6 +532,35 @@ int tsvpp_convert_rois_p010_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_p0
 int tsvpp_describe_rois_p010_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_p010 *frames, int n_rois,
                                      const tsvpp_roi *rois, int aligned_outputs, char *buf, size_t buf_len);
 int tsvpp_cubic_p010_plane(const uint16_t *src, int src_w, int src_h, uint16_t *dst, int dst_w, int dst_h);
+
+/* ---- 10-bit sources: tsvpp_convert_rois_p010_area ----
+ * tsvpp_convert_rois_p010 with the exact box filter of tsvpp_convert_letterbox_p010_area, the averaging filter a box should get on its way DOWN behind a detector:
+ * a 300 x 700 person box to 128 x 256 for re-identification, a 500-pixel vehicle box to 224 x 224.  At those ratios BILINEAR point-samples and the cubic
+ * aliases; narrowing the frame to 8 bits for tsvpp_convert_rois_area is an extra pass over the frame and drops two bits in front of the filter.  Signatures as
+ * the tsvpp_convert_rois_p010 pair.
+ * Contract.  Output i is, bit for bit and in every flavour, what tsvpp_convert_letterbox_p010_area returns for a P010 frame that consists of box i alone, with
+ * the rectangle equal to the whole dst_width x dst_height canvas.  Stated the other way round: per plane it is tsvpp_box_p010_plane on the box's samples -- Y
+ * from the box's W x H to w x h, U and V each from W/2 x H/2 to w/2 x h/2 -- then the P010 colour expression with the two offsets scaled by four, stored as
+ * k / 1023, min(255, (k + 2) >> 2), or cvt(dtype, (q - mean[c]) * scale[c]) with a spec.  No word outside the box influences its output: every footprint and
+ * every clamp is to the box's plane.  A box smaller than the output on an axis is legal and gets box coverage (one or two taps), as the letterbox call says of
+ * an axis that is not shrunk.
+ * Everything not stated here is tsvpp_convert_rois_p010's, word for word: boxes with even origins and sizes, frames of mixed sizes and pitches, 64 boxes per
+ * launch with their records by value in the kernarg segment, no allocation, no copy, no host synchronisation, legal under stream capture, the G-term option and
+ * the coefficient block, the tensor flavours with a spec (merged: TSVPP_UNSUPPORTED).
+ * Status, decided before any device is touched (the describe call returns the same one), in this order: (1) tsvpp_convert_rois_p010's rules in their order;
+ * (2) p->resize_type other than TSVPP_AREA is TSVPP_UNSUPPORTED (and tsvpp_convert_rois_p010 keeps answering TSVPP_UNSUPPORTED for AREA); (3) a box side or an
+ * output side above TSVPP_BOX_P010_MAX_SIDE is TSVPP_UNSUPPORTED; (4) more than TSVPP_BOX_P010_MAX_TAPS taps on an axis of either plane of any box is
+ * TSVPP_UNSUPPORTED (ratios up to 16, and the exact ratio 17).  A request whose widest tile does not fit the workgroup's LDS budget even with one-row bands is
+ * TSVPP_UNSUPPORTED too; at the default budget no request within the limits is.
+ * tsvpp_describe_rois_p010_area prints tsvpp_describe_rois_p010's keys with mode=area and kernel=vpp_rois_p010_area<...> / vpp_rois_p010_area_tensor<...>
+ * (staged= counts every box: every tile walks its footprint through LDS; there is no gathering variant), then "taps=<largest per axis, XxY over the boxes>
+ * band=<source rows per band>": the height the LDS budget holds at the launch's widest footprint row, one for the launch; lds= is the launch's dynamic LDS,
+ * the two band buffers and the row means of one band.
+ * Not here: per-box output sizes, and what tsvpp_convert_rois_p010 lists. */
+int tsvpp_convert_rois_p010_area(tsvpp_ctx *ctx, int n_frames, const tsvpp_p010 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
+                                 const tsvpp_tensor_spec *spec /* may be NULL */, void *const *outs, void *stream);
+int tsvpp_describe_rois_p010_area(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_p010 *frames, int n_rois,
+                                  const tsvpp_roi *rois, int aligned_outputs, char *buf, size_t buf_len);
 
 /* DEBUG ONLY (tests), host only: tsvpp_roi_area_rows as tsvpp_convert_letterbox_area's kernel produces the rows -- the generator begun at the jump start of
  * (scale, first), the largest multiple of the pattern's period that is <= first (0 where the pattern does not close in 1 .. first), which *start receives.

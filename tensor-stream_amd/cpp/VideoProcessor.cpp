@@ -331,6 +331,20 @@ int VideoProcessor::ConvertRoisP010Bicubic(AVFrame *const *inputs, int nInputs, 
     return ConvertRoisP010Bicubic(inputs, nInputs, rois, nRois, deviceOuts, options, nullptr, consumerName);
 }
 
+// `spec` may be null (the library's flavours)
+int VideoProcessor::ConvertRoisP010Area(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                        const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRoisP010Area",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_rois_p010_area(ctx, nInputs, p010Frames(frames, nInputs).data(), nRois, rois, p, spec, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertRoisP010Area(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                                        std::string consumerName) {
+    return ConvertRoisP010Area(inputs, nInputs, rois, nRois, deviceOuts, options, nullptr, consumerName);
+}
+
 int VideoProcessor::ConvertWarp(AVFrame *const *inputs, int nInputs, const tsvpp_warp *warps, int nWarps, int borderY, int borderU, int borderV, void *const *deviceOuts,
                                 FrameParameters &options, std::string consumerName) {
     return convertTiles(ctx, isClosed, inputs, nInputs, warps && nWarps > 0, deviceOuts, options, consumerName, "ConvertWarp",

@@ -170,6 +170,13 @@ public:
                                std::string consumerName);
     int ConvertRoisP010Bicubic(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertRoisP010 with the exact box filter (tsvpp_convert_rois_p010_area, include/tsvpp.h): ConvertLetterboxP010Area's averaging resize on all ten bits, for
+    // boxes that go DOWN to the network's input size.  options.resize.type must be AREA; at most 17 taps on an axis (ratios up to 16) and no side above 16384.
+    // Plain, and with a tensor spec (null: the plain call).
+    int ConvertRoisP010Area(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                            std::string consumerName);
+    int ConvertRoisP010Area(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
+                            const tsvpp_tensor_spec *spec, std::string consumerName);
     // Boxes that each go to their OWN output size (tsvpp_convert_rois_sized, include/tsvpp.h; not in the reference): text lines of one height and their own widths,
     // the levels of a pyramid, the inputs of several heads behind one detector pass.  rois[i] carries the box and its dst_width x dst_height; deviceOuts[i] holds
     // tsvpp_rois_sized_bytes bytes.  options.resize.width and height must be 0 (the sizes are the boxes') and options.crop empty; options.resize.type is NEAREST,

@@ -1,5 +1,5 @@
-// vpp_box_p010.h -- the arithmetic of tsvpp_convert_letterbox_p010_area (include/tsvpp.h), once, for the kernel
-// (vpp_letterbox_p010_area_core.h), the host path (tsvpp_letterbox_p010_area.cpp) and the host's executable form of the contract (tsvpp_box_p010_plane): an exact
+// vpp_box_p010.h -- the arithmetic of tsvpp_convert_letterbox_p010_area and tsvpp_convert_rois_p010_area (include/tsvpp.h), once, for the
+// kernels (vpp_box_p010_walk.h: vpp_letterbox_p010_area_core.h, vpp_rois_p010_area_core.h), the host paths (tsvpp_letterbox_p010_area.cpp) and the host's executable form of the contract (tsvpp_box_p010_plane): an exact
 // box filter in unsigned 32-bit integers.  One axis with N source samples and n output samples, in units in which a source sample is n wide: output j covers
 // [j N, (j + 1) N), its taps are i = floor(j N / n) .. floor(((j + 1) N - 1) / n), tap i weighs o(i, j) = min((i + 1) n, (j + 1) N) - max(i n, j N); the weights
 // are positive and sum to N.  Horizontal pass per source row: hx = sum o_x s, r = (64 hx + N_x / 2) / N_x (the row mean in 1/64 sample steps); vertical pass:
@@ -62,6 +62,13 @@ __host__ __device__ inline int box_max_taps(int N, int n) {
         b = t;
     }
     return (int)(((long)n - a + N - 1) / n) + 1;
+}
+// The exact source footprint of output indices [o0, o1] of an axis N -> n: first tap of o0, last tap of o1 (host and device alike: the host sizes the band
+// buffers with the numbers the kernel computes)
+__host__ __device__ inline void box_span(int o0, int o1, int N, int n, int &lo, int &hi) {
+    const BoxDiv dn = box_div_of((uint32_t)n);
+    lo = (int)box_quot((uint32_t)o0 * (uint32_t)N, dn);
+    hi = (int)box_quot(((uint32_t)o1 + 1u) * (uint32_t)N - 1u, dn);
 }
 // the two normalising divisions
 __host__ __device__ __forceinline__ uint32_t box_row_mean(uint32_t hx, const BoxDiv &dN) { return box_quot(64u * hx + (dN.d >> 1), dN); }

@@ -14,13 +14,6 @@ struct LbBoxLaunch : LbLaunch {
 };
 static_assert(sizeof(LbBoxLaunch) + 256 <= 4096, "LbBoxLaunch no longer fits the kernarg segment");
 
-// The exact source footprint of output indices [o0, o1] of an axis N -> n: first tap of o0, last tap of o1 (host and device alike: the host sizes the band
-// buffers with the numbers the kernel computes)
-__host__ __device__ inline void box_span(int o0, int o1, int N, int n, int &lo, int &hi) {
-    const BoxDiv dn = box_div_of((uint32_t)n);
-    lo = (int)box_quot((uint32_t)o0 * (uint32_t)N, dn);
-    hi = (int)box_quot(((uint32_t)o1 + 1u) * (uint32_t)N - 1u, dn);
-}
 // chunks per staged row of inner columns [a0, a1] (a0 even, a1 odd) of a frame src_w wide into a rectangle `width` wide: luma words, chroma (U, V) word pairs
 __host__ __device__ inline int box_cpr_y(int a0, int a1, int src_w, int width) {
     int lo, hi;

@@ -114,6 +114,7 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_convert_letterbox_p010", "tsvpp_describe_letterbox_p010", "tsvpp_convert_rois_p010", "tsvpp_describe_rois_p010",
            "tsvpp_convert_letterbox_p010_area", "tsvpp_describe_letterbox_p010_area", "tsvpp_box_p010_plane",
            "tsvpp_convert_rois_p010_bicubic", "tsvpp_describe_rois_p010_bicubic", "tsvpp_cubic_p010_plane",
+           "tsvpp_convert_rois_p010_area", "tsvpp_describe_rois_p010_area",
            "tsvpp_rois_sized_bytes", "tsvpp_convert_rois_sized", "tsvpp_describe_rois_sized", "tsvpp_convert_rois_sized_tensor", "tsvpp_describe_rois_sized_tensor",
            "tsvpp_rois_sized_tile",
            "tsvpp_convert_warp", "tsvpp_describe_warp", "tsvpp_convert_warp_tensor", "tsvpp_describe_warp_tensor", "tsvpp_warp_rotated_box", "tsvpp_warp_footprint",
@@ -228,6 +229,10 @@ def lib():
     L.tsvpp_describe_rois_p010_bicubic.restype = i32
     L.tsvpp_cubic_p010_plane.argtypes = [vp, i32, i32, vp, i32, i32]
     L.tsvpp_cubic_p010_plane.restype = i32
+    L.tsvpp_convert_rois_p010_area.argtypes = L.tsvpp_convert_rois_p010.argtypes  # (spec may be None)
+    L.tsvpp_convert_rois_p010_area.restype = i32
+    L.tsvpp_describe_rois_p010_area.argtypes = L.tsvpp_describe_rois_p010.argtypes
+    L.tsvpp_describe_rois_p010_area.restype = i32
     L.tsvpp_letterbox_area_rows.argtypes = [ctypes.c_float, i32, i32, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.tsvpp_letterbox_area_rows.restype = i32
     pz = ctypes.POINTER(RoiSized)

@@ -411,6 +411,13 @@ class VideoProcessor:
         may be at most 8 times the output on an axis and no side above 16384.  A 4-tap interpolator, not an anti-aliased filter."""
         return self._convert_rois_p010("convert_rois_p010_bicubic", ys, uvs, rois, params, out, width, height, tensor_spec(dtype, mean, std))
 
+    def convert_rois_p010_area(self, ys, uvs, rois, params, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_rois_p010 for ResizeType.AREA (tsvpp_convert_rois_p010_area): convert_letterbox_p010_area's exact integer box filter on all ten bits, the
+        filter for boxes that go DOWN to the network's input size (a 300 x 700 person box to 128 x 256), where BILINEAR point-samples and the cubic aliases.
+        Arguments and result as convert_rois_p010; output i equals, bit for bit, convert_letterbox_p010_area of a frame that consists of box i alone.  No side
+        above 16384 and at most 17 taps on an axis (ratios up to 16); a box smaller than the output on an axis gets box coverage."""
+        return self._convert_rois_p010("convert_rois_p010_area", ys, uvs, rois, params, out, width, height, tensor_spec(dtype, mean, std))
+
     def _convert_rois_p010(self, name, ys, uvs, rois, params, out, width, height, spec):
         p = params.parameters if isinstance(params, FrameParameters) else params
         ys, uvs, boxes = _normalize_rois(ys, uvs, rois)
@@ -886,6 +893,12 @@ def describe_rois_p010_bicubic(params, frames, rois, aligned_outputs=True, dtype
     """What a convert_rois_p010_bicubic of this request would launch, as a dict (tsvpp_describe_rois_p010_bicubic: describe_rois_p010's keys with mode =
     "bicubic", then band = the source rows a workgroup stages per band; staged counts every box) -- host logic only, works without a GPU."""
     return _describe_rois_p010(N.lib().tsvpp_describe_rois_p010_bicubic, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
+
+
+def describe_rois_p010_area(params, frames, rois, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_rois_p010_area of this request would launch, as a dict (tsvpp_describe_rois_p010_area: describe_rois_p010's keys with mode = "area", then
+    taps = "XxY", the largest tap counts per axis, and band = the source rows a workgroup stages per band, sized for the launch's widest tile; staged counts every box) -- host logic only, works without a GPU."""
+    return _describe_rois_p010(N.lib().tsvpp_describe_rois_p010_area, params, frames, rois, aligned_outputs, tensor_spec(dtype, mean, std))
 
 
 def _describe_rois_p010(entry, params, frames, rois, aligned_outputs, spec):

@@ -6,6 +6,8 @@ before tsvpp_convert_rois) against (b) ONE tsvpp_convert_rois -- on one stream, 
     python tools/rois_ab.py --area [--out profiles/rois_area_ab.txt]      the AREA leg: tsvpp_convert_rois_area (see area_main)
     python tools/rois_ab.py --dtype f16 [--mean a,b,c] [--std a,b,c]      the tensor legs: tsvpp_convert_rois_tensor (see tensor_main; appends to profiles/tensor_ab.txt)
     python tools/rois_ab.py --p010 [--out profiles/rois_p010_ab.txt]      10-bit sources: tsvpp_convert_rois_p010 against narrowing + tsvpp_convert_rois (see p010_main)
+    python tools/rois_ab.py --p010 --area [--out profiles/rois_p010_area_ab.txt]   the same with AREA: tsvpp_convert_rois_p010_area against narrowing plus
+                                                                         tsvpp_convert_rois_area, boxes near 2, 3 and 6 times 128 x 256 and 224 x 224, n = 1, 8, 32, 64
     python tools/rois_ab.py --p010 --bicubic [--out profiles/rois_p010_bicubic_ab.txt]   the same with BICUBIC: tsvpp_convert_rois_p010_bicubic, a BILINEAR leg (d) and
                                                                           a second set of small boxes that go UP to 112 x 112
 
@@ -308,6 +310,21 @@ def small_boxes_for(n, seed):
     return out
 
 
+AREA_P010_OUTPUTS = [("128x256 AREA RGB24 merged uint8", (128, 256), 1, 1, False, None), ("224x224 AREA BGR24 planar fp32", (224, 224), 2, 0, True, None)]
+AREA_P010_RATIOS = (2, 3, 6)
+
+
+def area_boxes_for(n, seed, dst, ratio):
+    """boxes near `ratio` times the output, each side 0 .. 8 % smaller, cut to the frame where ratio x output does not fit (6 x 256 rows: 1080)"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        bw, bh = (min(int(ratio * d * (1 - 0.08 * rng.random())), lim) & ~1 for d, lim in zip(dst, (W, H)))
+        l, t = int(rng.integers(0, W - bw + 1)), int(rng.integers(0, H - bh + 1))
+        out.append((l, t, l + bw, t + bh))
+    return out
+
+
 def p010_main(a):
     """10-bit sources, same protocol (seeded boxes with sides 64 .. 512 -- origins rounded down to even -- of a 1080p frame, the P010 frame at a pitch of 4096
     bytes, one stream, frames and outputs rotating through more than 256 MiB, median of the blocks with their spread):
@@ -318,8 +335,12 @@ def p010_main(a):
     Every leg is parity-checked, every box bit for bit, before and after its timing: (a) against tests/p010_util.py, (b) and (c) against the CPU oracle on the
     narrowed planes (tests/tensor_util.py for fp16).
     --bicubic: (a) is tsvpp_convert_rois_p010_bicubic (parity against tests/p010_cubic_util.py), (b) and (c) run the 8-bit BICUBIC, leg (d) is
-    tsvpp_convert_rois_p010 with BILINEAR on the same boxes, and a fourth configuration takes boxes with sides 32 .. 96 up to 112 x 112."""
+    tsvpp_convert_rois_p010 with BILINEAR on the same boxes, and a fourth configuration takes boxes with sides 32 .. 96 up to 112 x 112.
+    --area: (a) is tsvpp_convert_rois_p010_area (parity against tests/p010_area_util.py), (b) and (c) run tsvpp_convert_rois_area, leg (d) as with --bicubic;
+    the configurations are AREA_P010_OUTPUTS x AREA_P010_RATIOS with area_boxes_for's boxes, and parity is checked on at most eight boxes of a row, evenly
+    spread (the int64 model of a 1344 x 1080 box takes a second on the host)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import p010_area_util as A
     import p010_cubic_util as Q
     import p010_util as M
     import tensor_util as T
@@ -343,16 +364,21 @@ def p010_main(a):
     fr8c = [(N.NV12 * 1)(N.NV12(ys8[k].data_ptr(), uvs8[k].data_ptr(), W, W, W, H)) for k in range(nf)]
     fr8b = [(N.NV12 * 1)(N.NV12(by8[k].data_ptr(), buv8[k].data_ptr(), W, W, W, H)) for k in range(nf)]
     pool_mib = nf * (P010_PITCH * H * 3 // 2) >> 20
-    cubic = a.bicubic
-    rt, call_a = (2, "tsvpp_convert_rois_p010_bicubic") if cubic else (1, "tsvpp_convert_rois_p010")
-    convert_a, describe_a, legs = getattr(L, call_a), (ts.describe_rois_p010_bicubic if cubic else ts.describe_rois_p010), ("abcd" if cubic else "abc")
-    lines = [f"# tools/rois_ab.py --p010{' --bicubic' if cubic else ''}: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {nf} x 1080p P010 at pitch {P010_PITCH} ({pool_mib} MiB), "
+    area, cubic = a.area, a.bicubic or a.area  # (`cubic`: a leg (d) and the fourth column group; `area` on top: the AREA calls, configurations and model)
+    rt, call_a = (3, "tsvpp_convert_rois_p010_area") if area else ((2, "tsvpp_convert_rois_p010_bicubic") if a.bicubic else (1, "tsvpp_convert_rois_p010"))
+    describe_a = ts.describe_rois_p010_area if area else (ts.describe_rois_p010_bicubic if cubic else ts.describe_rois_p010)
+    convert_a, legs = getattr(L, call_a), ("abcd" if cubic else "abc")
+    call_8 = "tsvpp_convert_rois_area" if area else "tsvpp_convert_rois"
+    lines = [f"# tools/rois_ab.py --p010{' --area' if area else (' --bicubic' if cubic else '')}: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, frame pool {nf} x 1080p P010 at pitch {P010_PITCH} ({pool_mib} MiB), "
              f"median of {a.repeats} blocks of {a.iters} iterations, one stream",
-             f"# (a) = 1 x {call_a}   (b) = torch >> 8 + narrowing copy of both planes, then 1 x tsvpp_convert_rois   (c) = the 8-bit call alone on frames narrowed beforehand"
+             f"# (a) = 1 x {call_a}   (b) = torch >> 8 + narrowing copy of both planes, then 1 x {call_8}   (c) = the 8-bit call alone on frames narrowed beforehand"
              + ("   (d) = 1 x tsvpp_convert_rois_p010, BILINEAR" if cubic else ""),
              "# us per call, [min .. max of the blocks]; staged = boxes of the P010 call whose every tile stages in LDS / of the 8-bit call"]
     met = True
-    for name, dst, fcc, planes, norm, dt in P010_CONFIGS + ([(SMALL, *P010_CONFIGS[1][1:])] if cubic else []):
+    configs = P010_CONFIGS + ([(SMALL, *P010_CONFIGS[1][1:])] if cubic else [])
+    if area:
+        configs = [(f"{c[0]}, boxes near {r} x the output", *c[1:], r) for c in AREA_P010_OUTPUTS for r in AREA_P010_RATIOS]
+    for name, dst, fcc, planes, norm, dt, *ratio in configs:
         small, name = name == SMALL, (name.replace("BILINEAR", "BICUBIC") if cubic else name)
         fp = ts.FrameParameters(width=dst[0], height=dst[1], resize_type=rt, pixel_format=fcc, planes_pos=planes, normalization=norm)
         p = fp.parameters
@@ -365,14 +391,16 @@ def p010_main(a):
         lines += ["", f"## {name}", f"{'n':>3} | {'(a) us':>8} {'spread':>15} | {'(b) us':>8} {'spread':>15} | {'(c) us':>8} {'spread':>15} | {'b / a':>6} {'a / c':>6} | {'staged':>9} | a < b by more than (b)'s spread"
                   + (f" | {'(d) us':>8} {'spread':>15} {'a / d':>6}" if cubic else "")]
         for n in [int(v) for v in a.ns.split(",")]:
-            boxes = [(l & ~1, t & ~1, (l & ~1) + r - l, (t & ~1) + b - t) for l, t, r, b in (small_boxes_for if small else boxes_for)(n, seed=100 + n)]
+            drawn = area_boxes_for(n, 100 + n, dst, ratio[0]) if area else (small_boxes_for if small else boxes_for)(n, seed=100 + n)
+            boxes = [(l & ~1, t & ~1, (l & ~1) + r - l, (t & ~1) + b - t) for l, t, r, b in drawn]
+            checked = range(0, n, max(1, n // 8)) if area else range(n)
             sets = max(2, min(64, (300 << 20) // (n * out_bytes) + 1))
             pool = [vpp._alloc(p, dst[0], dst[1], n, tdt) if dt else vpp._alloc(p, dst[0], dst[1], n) for _ in range(sets)]
             recs = (N.Roi * n)(*[N.Roi(0, *b) for b in boxes])
             out_arrs = [(ctypes.c_void_p * n)(*[pool[s][i].data_ptr() for i in range(n)]) for s in range(sets)]
             ctx, pref = vpp._ctx, ctypes.byref(p)
             d16 = describe_a(fp, [(W, H, P010_PITCH)], boxes, **kw)["staged"]
-            d8 = ts.describe_rois(fp, [(W, H)], boxes, **kw)["staged"]
+            d8 = (ts.describe_rois_area if area else ts.describe_rois)(fp, [(W, H)], boxes, **kw)["staged"]
 
             def leg_a(k):
                 if convert_a(ctx, 1, fr16[k % nf], n, recs, pref, sref, out_arrs[k % sets], raw) != 0:
@@ -383,10 +411,10 @@ def p010_main(a):
                     raise RuntimeError("tsvpp_convert_rois_p010 failed")
 
             def rois8(frames, k):
-                sts = L.tsvpp_convert_rois(ctx, 1, frames[k % nf], n, recs, pref, out_arrs[k % sets], raw) if spec is None else \
+                sts = getattr(L, call_8)(ctx, 1, frames[k % nf], n, recs, pref, out_arrs[k % sets], raw) if spec is None else \
                     L.tsvpp_convert_rois_tensor(ctx, 1, frames[k % nf], n, recs, pref, sref, out_arrs[k % sets], raw)
                 if sts != 0:
-                    raise RuntimeError("tsvpp_convert_rois failed")
+                    raise RuntimeError(call_8 + " failed")
 
             def leg_b(k):
                 f = k % nf
@@ -404,9 +432,11 @@ def p010_main(a):
                     y, uv = ys[f].cpu().numpy().view(np.uint16), uvs[f].cpu().numpy().view(np.uint16)
                 else:
                     y, uv = ys8[f].cpu().numpy(), uvs8[f].cpu().numpy()
-                for i, (l, t, r, b) in enumerate(boxes):
+                for i in checked:
+                    l, t, r, b = boxes[i]
                     if leg in "ad":
-                        yuv = Q.planes(y[t:b, l:r], uv[t // 2:b // 2, l:r], dst) if cubic and leg == "a" else \
+                        yuv = A.virtual_frame(y[t:b, l:r], uv[t // 2:b // 2, l:r], r - l, b - t, (0, 0, *dst), dst, (0, 0, 0)) if area and leg == "a" else \
+                            Q.planes(y[t:b, l:r], uv[t // 2:b // 2, l:r], dst) if cubic and leg == "a" else \
                             M.virtual_frame(y[t:b, l:r], uv[t // 2:b // 2, l:r], r - l, b - t, (0, 0, *dst), dst, M.BILINEAR, (0, 0, 0))
                         k10 = M.channels(*yuv, fcc)
                         ref = M.stored(k10, planes, norm) if dt is None else T.expected(M.quotient(k10), 3, T.IMAGENET, dt)
@@ -435,7 +465,7 @@ def p010_main(a):
             print(lines[-1], flush=True)
             del pool
             torch.cuda.empty_cache()
-    lines += ["", "# parity: every leg bit-exact on every box before and after its timing -- (a) against tests/p010_" + ("cubic_util.py, (d) against tests/p010_" if cubic else "") + "util.py, (b) and (c) against the CPU oracle on the narrowed planes",
+    lines += ["", f"# parity: every leg bit-exact on {'at most eight evenly spread boxes of a row' if area else 'every box'} before and after its timing -- (a) against tests/p010_" + ("area_util.py, (d) against tests/p010_" if area else ("cubic_util.py, (d) against tests/p010_" if cubic else "")) + "util.py, (b) and (c) against the CPU oracle on the narrowed planes",
               f"# expectation ((a) faster than (b) in every row by more than the spread of (b)'s blocks): {'met' if met else 'NOT MET in the rows marked'}"]
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -447,7 +477,8 @@ def p010_main(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--area", action="store_true", help="the AREA leg (tsvpp_convert_rois_area); default output profiles/rois_area_ab.txt")
+    ap.add_argument("--area", action="store_true", help="the AREA leg (tsvpp_convert_rois_area); default output profiles/rois_area_ab.txt.  With --p010: tsvpp_convert_rois_p010_area; "
+                    "default output profiles/rois_p010_area_ab.txt, n = 1, 8, 32, 64")
     ap.add_argument("--p010", action="store_true", help="10-bit sources (tsvpp_convert_rois_p010); default output profiles/rois_p010_ab.txt, frame pool 48")
     ap.add_argument("--bicubic", action="store_true", help="with --p010: tsvpp_convert_rois_p010_bicubic; default output profiles/rois_p010_bicubic_ab.txt")
     ap.add_argument("--out", default=None)
@@ -461,7 +492,10 @@ def main():
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
     if a.p010:
-        a.out = a.out or os.path.join(ROOT, "profiles", "rois_p010_bicubic_ab.txt" if a.bicubic else "rois_p010_ab.txt")
+        assert not (a.area and a.bicubic), "--p010 takes --area or --bicubic"
+        a.out = a.out or os.path.join(ROOT, "profiles", "rois_p010_area_ab.txt" if a.area else ("rois_p010_bicubic_ab.txt" if a.bicubic else "rois_p010_ab.txt"))
+        if a.area and a.ns == ap.get_default("ns"):
+            a.ns = "1,8,32,64"
         if a.frames > 48:  # 48 P010 frames at pitch 4096: 303 MiB
             print(f"--p010: frame pool of 48 frames (303 MiB) instead of --frames {a.frames}", flush=True)
             a.frames = 48

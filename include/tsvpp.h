@@ -407,8 +407,8 @@ int tsvpp_describe_letterbox_area(const tsvpp_params *p, const tsvpp_tensor_spec
  * row too) at or above TSVPP_SOURCE_SPAN_LIMIT; then, with a spec, rules 2 and 3 of the tensor entry points.
  * tsvpp_describe_letterbox_p010 prints tsvpp_describe_letterbox's keys with "src=p010" in front of frames=, kernel=vpp_letterbox_p010<...> /
  * vpp_letterbox_p010_tensor<...> and limit=32; lds= counts the footprints as 16-bit words (twice the 8-bit call's bytes, rounded up to the staging loop's 64 chunks).
- * Not here, each a follow-up: BICUBIC for the letterbox (the boxes have it: tsvpp_convert_rois_p010_bicubic, below; AREA is a call of its own for the letterbox
- * and for boxes: tsvpp_convert_letterbox_p010_area and tsvpp_convert_rois_p010_area, below);
+ * BICUBIC and AREA are calls of their own, for the letterbox and for boxes: tsvpp_convert_letterbox_p010_bicubic, tsvpp_convert_letterbox_p010_area,
+ * tsvpp_convert_rois_p010_bicubic and tsvpp_convert_rois_p010_area, below.  Not here, each a follow-up:
  * P010 through tsvpp_convert, the per-box-size, warp and map calls; P012 / P016 and full-range or BT.709 / BT.2020
  * presets (the coefficient block already lets a caller set them); 10-bit or 16-bit integer outputs; merged tensors. */
 typedef struct tsvpp_p010 {
@@ -524,7 +524,7 @@ int tsvpp_describe_rois_p010(const tsvpp_params *p, const tsvpp_tensor_spec *spe
  * tsvpp_cubic_p010_plane is the contract's executable form, on the host: it resizes one plane of SAMPLES (0..1023, src_w x src_h, rows of src_w) to dst_w x dst_h
  * with the functions the kernel is compiled from (csrc/vpp_cubic_p010.h).  Statuses as tsvpp_box_p010_plane's, with TSVPP_CUBIC_P010_MAX_SIDE; the ratio limit
  * is the kernel's and does not apply.
- * Not here: BICUBIC for the P010 letterbox, per-box output sizes, and what tsvpp_convert_rois_p010 lists. */
+ * Not here: per-box output sizes, and what tsvpp_convert_rois_p010 lists.  The P010 letterbox has the same filter: tsvpp_convert_letterbox_p010_bicubic, below. */
 #define TSVPP_CUBIC_P010_MAX_SIDE 16384
 #define TSVPP_CUBIC_P010_MAX_RATIO 8
 int tsvpp_convert_rois_p010_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_p010 *frames, int n_rois, const tsvpp_roi *rois, const tsvpp_params *p,
@@ -532,6 +532,32 @@ int tsvpp_convert_rois_p010_bicubic(tsvpp_ctx *ctx, int n_frames, const tsvpp_p0
 int tsvpp_describe_rois_p010_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n_frames, const tsvpp_p010 *frames, int n_rois,
                                      const tsvpp_roi *rois, int aligned_outputs, char *buf, size_t buf_len);
 int tsvpp_cubic_p010_plane(const uint16_t *src, int src_w, int src_h, uint16_t *dst, int dst_w, int dst_h);
+
+/* ---- 10-bit sources: tsvpp_convert_letterbox_p010_bicubic ----
+ * tsvpp_convert_letterbox_p010 with the cubic resize of tsvpp_convert_rois_p010_bicubic, the filter a 640 x 360 or 720p Main10 frame should get on its way UP into
+ * a 1280 x 1280 canvas for a high-resolution detector -- on all ten bits, with no narrowing pass in front of the one filter that overshoots.  Signatures as the
+ * tsvpp_convert_letterbox_p010 pair.  Everything not stated here is tsvpp_convert_letterbox_p010's, word for word: tsvpp_p010 frames of mixed sizes and pitches,
+ * rectangles and tsvpp_letterbox_rect, the evenness rules, the pad as a P010 sample triple, 32 frames per launch with their records by value in the kernarg
+ * segment (one host array beyond 32 frames), no allocation, no copy, legal under stream capture, the colour expression with the offsets scaled by four, the
+ * G-term option and the coefficient block, the stored forms k / 1023 and min(255, (k + 2) >> 2), the tensor forms with a spec, and the status rules in their
+ * order.  p->resize_type must be TSVPP_BICUBIC; any other type is TSVPP_UNSUPPORTED, checked behind every rule the BILINEAR call checks first (and
+ * tsvpp_convert_letterbox_p010 keeps answering TSVPP_UNSUPPORTED for BICUBIC).
+ *   resize   inside the rectangle, per plane, tsvpp_cubic_p010_plane: Y from the frame's W x H samples to the rectangle's w x h, U and V each from W/2 x H/2 to
+ *            w/2 x h/2, in the signed 32-bit integers of tsvpp_convert_rois_p010_bicubic (term, phase, weights, the unclamped h, the clamped k).  Taps clamp at
+ *            the FRAME, never at a tile.  Outside the rectangle: the pad triple, through the same colour stage.
+ *   stated the other way round  with the rectangle equal to the whole canvas, canvas k is, bit for bit and in every flavour, what
+ *            tsvpp_convert_rois_p010_bicubic returns for the box that is all of frame k at the canvas size.
+ *   limits   the ROI call's, per frame on its rectangle: TSVPP_UNSUPPORTED, decided before a device is touched and returned alike by describe, for a side of a
+ *            frame or of its rectangle above TSVPP_CUBIC_P010_MAX_SIDE and for N > TSVPP_CUBIC_P010_MAX_RATIO * n on an axis of either plane.  A request whose
+ *            largest tile does not fit the workgroup's LDS budget even with one-row bands is TSVPP_UNSUPPORTED too; at the default budget no request within
+ *            the limits is.
+ * tsvpp_describe_letterbox_p010_bicubic prints tsvpp_describe_letterbox_p010's keys with mode=bicubic and kernel=vpp_letterbox_p010_bicubic<...> /
+ * vpp_letterbox_p010_bicubic_tensor<...> (staged= counts every frame: every tile that holds some of the rectangle walks its footprint through LDS), then
+ * "band=<source rows per band>"; lds= is the intermediate rows and the two band buffers, sized for the tile parts of the launch's frames. */
+int tsvpp_convert_letterbox_p010_bicubic(tsvpp_ctx *ctx, int n, const tsvpp_p010 *in, const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */,
+                                         const tsvpp_rect *rects, int pad_y, int pad_u, int pad_v, void *const *outs, void *stream);
+int tsvpp_describe_letterbox_p010_bicubic(const tsvpp_params *p, const tsvpp_tensor_spec *spec /* may be NULL */, int n, const tsvpp_p010 *in, const tsvpp_rect *rects,
+                                          int aligned_outputs, char *buf, size_t buf_len);
 
 /* ---- 10-bit sources: tsvpp_convert_rois_p010_area ----
  * tsvpp_convert_rois_p010 with the exact box filter of tsvpp_convert_letterbox_p010_area, the averaging filter a box should get on its way DOWN behind a detector:

@@ -304,6 +304,20 @@ int VideoProcessor::ConvertLetterboxP010Area(AVFrame *const *inputs, int n, cons
 }
 
 // `spec` may be null (the library's flavours)
+int VideoProcessor::ConvertLetterboxP010Bicubic(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
+                                                FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName) {
+    return convertTiles(ctx, isClosed, inputs, n, true, deviceOuts, options, consumerName, "ConvertLetterboxP010Bicubic",
+                        [&](const tsvpp_nv12 *frames, const tsvpp_params *p, void *stream) {
+                            return tsvpp_convert_letterbox_p010_bicubic(ctx, n, p010Frames(frames, n).data(), p, spec, rects, padY, padU, padV, deviceOuts, stream);
+                        });
+}
+
+int VideoProcessor::ConvertLetterboxP010Bicubic(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
+                                                FrameParameters &options, std::string consumerName) {
+    return ConvertLetterboxP010Bicubic(inputs, n, rects, padY, padU, padV, deviceOuts, options, nullptr, consumerName);
+}
+
+// `spec` may be null (the library's flavours)
 int VideoProcessor::ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options,
                                     const tsvpp_tensor_spec *spec, std::string consumerName) {
     return convertTiles(ctx, isClosed, inputs, nInputs, rois && nRois > 0, deviceOuts, options, consumerName, "ConvertRoisP010",

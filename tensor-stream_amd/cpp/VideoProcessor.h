@@ -158,6 +158,13 @@ public:
                                  std::string consumerName);
     int ConvertLetterboxP010Area(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts, FrameParameters &options,
                                  const tsvpp_tensor_spec *spec, std::string consumerName);
+    // ConvertLetterboxP010 with ResizeType BICUBIC (tsvpp_convert_letterbox_p010_bicubic, include/tsvpp.h): ConvertRoisP010Bicubic's separable integer cubic on all
+    // ten bits inside the rectangle, for frames that go UP into the canvas; taps clamp at the frame.  A frame may be at most 8 times its rectangle on an axis and no
+    // side above 16384; every other resize type is refused (and ConvertLetterboxP010 refuses BICUBIC).  Plain, and with a tensor spec (null: the plain call).
+    int ConvertLetterboxP010Bicubic(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
+                                    FrameParameters &options, std::string consumerName);
+    int ConvertLetterboxP010Bicubic(AVFrame *const *inputs, int n, const tsvpp_rect *rects, int padY, int padU, int padV, void *const *deviceOuts,
+                                    FrameParameters &options, const tsvpp_tensor_spec *spec, std::string consumerName);
     // ConvertRois for 10-bit P010 frames (tsvpp_convert_rois_p010, include/tsvpp.h): the boxes of the detector that ConvertLetterboxP010 fed, cut out of the same
     // decoded frames; NEAREST and BILINEAR; a box needs an even left and top as well as an even width and height.  Plain, and with a tensor spec (null: the plain call).
     int ConvertRoisP010(AVFrame *const *inputs, int nInputs, const tsvpp_roi *rois, int nRois, void *const *deviceOuts, FrameParameters &options, std::string consumerName);

@@ -1,22 +1,23 @@
 // vpp_letterbox_p010 -- letterboxes a few P010 frames into canvases of one size through the C++ class (VideoProcessor::ConvertLetterboxP010) and prints a CRC-32
 // per canvas (zlib's); tests/test_gpu_letterbox_p010.py compares each with the CRC of the expected canvas (tests/p010_util.py).
-//   vpp_letterbox_p010 [--area] [--dtype f16|bf16|f32] [--mean a,b,c] [--scale a,b,c] DW DH TYPE FOURCC PLANES NORM PADY PADU PADV  frame.p010 W H PITCH [frame.p010 W H PITCH ...]
+//   vpp_letterbox_p010 [--area | --bicubic] [--dtype f16|bf16|f32] [--mean a,b,c] [--scale a,b,c] DW DH TYPE FOURCC PLANES NORM PADY PADU PADV  frame.p010 W H PITCH [frame.p010 W H PITCH ...]
 // --area: through VideoProcessor::ConvertLetterboxP010Area (TYPE must then be 3, AREA; tests/test_gpu_letterbox_p010_area.py).
+// --bicubic: through VideoProcessor::ConvertLetterboxP010Bicubic (TYPE must then be 2, BICUBIC; tests/test_gpu_letterbox_p010_bicubic.py).
 // --dtype / --mean / --scale: through the overload that takes a tsvpp_tensor_spec.
 // A file holds H rows of PITCH BYTES of luma words, then H / 2 rows of PITCH bytes of chroma words (little-endian).  Every frame gets the default rectangle
 // (tsvpp_letterbox_rect).  Prints "<index> <crc> <bytes> <left> <top> <width> <height>" per canvas; exit code 0 = converted.
 #include "check_common.h"
 
 int main(int argc, char **argv) {
-    const bool area = argc > 1 && strcmp(argv[1], "--area") == 0;
-    if (area) {
+    const bool area = argc > 1 && strcmp(argv[1], "--area") == 0, bicubic = argc > 1 && strcmp(argv[1], "--bicubic") == 0;
+    if (area || bicubic) {
         argv++;
         argc--;
     }
     tsvpp_tensor_spec spec;
     const bool tensor = tensor_flags(argc, argv, spec);
     if (argc < 14 || (argc - 10) % 4 != 0) {
-        fprintf(stderr, "usage: vpp_letterbox_p010 [--area] " TENSOR_FLAGS_USAGE " DW DH TYPE FOURCC PLANES NORM PADY PADU PADV frame.p010 W H PITCH [frame.p010 W H PITCH ...]\n");
+        fprintf(stderr, "usage: vpp_letterbox_p010 [--area | --bicubic] " TENSOR_FLAGS_USAGE " DW DH TYPE FOURCC PLANES NORM PADY PADU PADV frame.p010 W H PITCH [frame.p010 W H PITCH ...]\n");
         return 200;
     }
     const int DW = atoi(argv[1]), DH = atoi(argv[2]), type = atoi(argv[3]);
@@ -46,6 +47,9 @@ int main(int argc, char **argv) {
         if (area)
             return tensor ? vpp.ConvertLetterboxP010Area(inputs.data(), count, rects, pad, padU, padV, arena.outs.data(), options, &spec, "letterbox_p010")
                           : vpp.ConvertLetterboxP010Area(inputs.data(), count, rects, pad, padU, padV, arena.outs.data(), options, "letterbox_p010");
+        if (bicubic)
+            return tensor ? vpp.ConvertLetterboxP010Bicubic(inputs.data(), count, rects, pad, padU, padV, arena.outs.data(), options, &spec, "letterbox_p010")
+                          : vpp.ConvertLetterboxP010Bicubic(inputs.data(), count, rects, pad, padU, padV, arena.outs.data(), options, "letterbox_p010");
         return tensor ? vpp.ConvertLetterboxP010(inputs.data(), count, rects, pad, padU, padV, arena.outs.data(), options, &spec, "letterbox_p010")
                       : vpp.ConvertLetterboxP010(inputs.data(), count, rects, pad, padU, padV, arena.outs.data(), options, "letterbox_p010");
     };

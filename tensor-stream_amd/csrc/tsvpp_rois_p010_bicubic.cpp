@@ -4,6 +4,7 @@
 // request rules are the P010 ROI call's with BICUBIC in the place of NEAREST / BILINEAR and this call's limits behind them; the skeletons of both calls are
 // tsvpp_tiles.h's.  Nothing here builds a table: the kernel computes every tap and weight in closed form from N and n, and what the host adds to the records
 // is the LDS carve-up of the launch.
+#include "tsvpp_cubic_p010.h"
 #include "tsvpp_p010.h"
 #include "tsvpp_tiles.h"
 #include "vpp_rois_p010_bicubic.h"
@@ -117,26 +118,6 @@ struct RoiCubicPath {
     const char *mode_name(const RoiPlan &) const { return "bicubic"; }
     void suffix(char *buf, size_t len, const RoiPlan &) const { std::snprintf(buf, len, " band=%d", band ? *band : 0); }
 };
-
-// TSVPP_UNSUPPORTED where the largest tile of a launch does not fit the workgroup's LDS budget even with one-row bands; decided on the host, before the skeleton
-// touches a device.  The default budget holds every request within the limits (Hbuf of 259 rows and two one-row bands of the widest row: 18.2 KiB, behind at
-// most 12 KiB of the store side's static LDS), so the launch groups are only walked where a knob has shrunk it.  `outs`: the convert call's (null: describe,
-// which says `aligned`).  A request the plan refuses is left to the skeleton.
-int cubic_fit_status(const RoiCubicPath &path, const Knobs &kn, void *const *outs, bool aligned) {
-    const int widest = std::max(roi_chunks(2 * CUBIC_TILE_MAX_HROWS), roi_chunks(4 * (CUBIC_TILE_MAX_HROWS / 2 + 2)));
-    if (!kn.force_gather && kn.lds_budget_kb * 1024 - roi_static_lds(O_F32_MERGED, true) >= cubic_lds(CUBIC_TILE_MAX_HROWS, 1, widest)) return TSVPP_OK;
-    RoiPlan pl;
-    if (tile_request(path, pl) != TSVPP_OK) return TSVPP_OK;
-    const int n = path.items(), limit = path.limit(pl);
-    for (int base = 0; base < n; base += limit) {
-        const int cnt = std::min(n - base, limit);
-        const bool vec = (outs ? outs_aligned16(outs + base, cnt) : aligned) && !narrow_tail(pl);
-        RoiCubicLaunch L;
-        tile_fill(path, kn, pl, nullptr, base, cnt, vec, L);
-        if (L.band < 1) return TSVPP_UNSUPPORTED;
-    }
-    return TSVPP_OK;
-}
 
 } // namespace
 

@@ -114,6 +114,7 @@ SYMBOLS = ["tsvpp_create", "tsvpp_destroy", "tsvpp_consumer_stream", "tsvpp_out_
            "tsvpp_convert_letterbox_p010", "tsvpp_describe_letterbox_p010", "tsvpp_convert_rois_p010", "tsvpp_describe_rois_p010",
            "tsvpp_convert_letterbox_p010_area", "tsvpp_describe_letterbox_p010_area", "tsvpp_box_p010_plane",
            "tsvpp_convert_rois_p010_bicubic", "tsvpp_describe_rois_p010_bicubic", "tsvpp_cubic_p010_plane",
+           "tsvpp_convert_letterbox_p010_bicubic", "tsvpp_describe_letterbox_p010_bicubic",
            "tsvpp_convert_rois_p010_area", "tsvpp_describe_rois_p010_area",
            "tsvpp_rois_sized_bytes", "tsvpp_convert_rois_sized", "tsvpp_describe_rois_sized", "tsvpp_convert_rois_sized_tensor", "tsvpp_describe_rois_sized_tensor",
            "tsvpp_rois_sized_tile",
@@ -229,6 +230,10 @@ def lib():
     L.tsvpp_describe_rois_p010_bicubic.restype = i32
     L.tsvpp_cubic_p010_plane.argtypes = [vp, i32, i32, vp, i32, i32]
     L.tsvpp_cubic_p010_plane.restype = i32
+    L.tsvpp_convert_letterbox_p010_bicubic.argtypes = L.tsvpp_convert_letterbox_p010.argtypes
+    L.tsvpp_convert_letterbox_p010_bicubic.restype = i32
+    L.tsvpp_describe_letterbox_p010_bicubic.argtypes = L.tsvpp_describe_letterbox_p010.argtypes
+    L.tsvpp_describe_letterbox_p010_bicubic.restype = i32
     L.tsvpp_convert_rois_p010_area.argtypes = L.tsvpp_convert_rois_p010.argtypes  # (spec may be None)
     L.tsvpp_convert_rois_p010_area.restype = i32
     L.tsvpp_describe_rois_p010_area.argtypes = L.tsvpp_describe_rois_p010.argtypes

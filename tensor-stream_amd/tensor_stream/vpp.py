@@ -376,6 +376,13 @@ class VideoProcessor:
         the identity).  A frame side above 16384 or more than 17 taps on an axis (ratios above 16) is refused, as is any other resize type."""
         return self._convert_letterbox_p010("convert_letterbox_p010_area", ys, uvs, params, pad, rects, out, width, height, tensor_spec(dtype, mean, std))
 
+    def convert_letterbox_p010_bicubic(self, ys, uvs, params, pad=(64, 512, 512), rects=None, out=None, width=None, height=None, dtype=None, mean=None, std=None):
+        """convert_letterbox_p010 for ResizeType.BICUBIC (tsvpp_convert_letterbox_p010_bicubic), same arguments and result: convert_rois_p010_bicubic's separable
+        Keys cubic (a = -3/4) in 32-bit integers on all ten bits inside the rectangle, the filter for frames that go UP into the canvas (640 x 360 or 720p into
+        1280 x 1280).  Taps clamp at the frame; with the rectangle equal to the canvas, canvas k equals, bit for bit, convert_rois_p010_bicubic of the box that
+        is all of frame k.  A frame may be at most 8 times its rectangle on an axis and no side above 16384; any other resize type is refused."""
+        return self._convert_letterbox_p010("convert_letterbox_p010_bicubic", ys, uvs, params, pad, rects, out, width, height, tensor_spec(dtype, mean, std))
+
     def _convert_letterbox_p010(self, call, ys, uvs, params, pad, rects, out, width, height, spec):
         p = params.parameters if isinstance(params, FrameParameters) else params
         n = len(ys)
@@ -858,28 +865,28 @@ def _p010_frame(y, uv, width, height):
 def describe_letterbox_p010(params, frames, rects=None, aligned_outputs=True, dtype=None, mean=None, std=None):
     """What a convert_letterbox_p010 of this request would launch, as a dict (tsvpp_describe_letterbox_p010: describe_letterbox's keys with src = "p010") -- host
     logic only, works without a GPU.  Arguments as describe_letterbox; pitches are in BYTES (0: 2 * width)."""
-    p = params.parameters if isinstance(params, FrameParameters) else params
-    recs = [N.P010(None, None, r.pitch_y, r.pitch_uv, r.width, r.height) for r in _geometry_records(frames)]
-    fr = (N.P010 * max(len(recs), 1))(*recs)
-    rc = None if rects is None else _rects(rects, len(recs))
-    buf = ctypes.create_string_buffer(512)
-    spec = tensor_spec(dtype, mean, std)
-    N.check(N.lib().tsvpp_describe_letterbox_p010(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf,
-                                                  len(buf)))
-    return _parse_selection(buf.value.decode())
+    return _describe_letterbox_p010(N.lib().tsvpp_describe_letterbox_p010, params, frames, rects, aligned_outputs, tensor_spec(dtype, mean, std))
 
 
 def describe_letterbox_p010_area(params, frames, rects=None, aligned_outputs=True, dtype=None, mean=None, std=None):
     """What a convert_letterbox_p010_area of this request would launch, as a dict (tsvpp_describe_letterbox_p010_area: describe_letterbox_p010's keys, then
     taps = "XxY", the largest tap counts per axis, and band = the source rows a workgroup stages per band) -- host logic only, works without a GPU."""
+    return _describe_letterbox_p010(N.lib().tsvpp_describe_letterbox_p010_area, params, frames, rects, aligned_outputs, tensor_spec(dtype, mean, std))
+
+
+def describe_letterbox_p010_bicubic(params, frames, rects=None, aligned_outputs=True, dtype=None, mean=None, std=None):
+    """What a convert_letterbox_p010_bicubic of this request would launch, as a dict (tsvpp_describe_letterbox_p010_bicubic: describe_letterbox_p010's keys with
+    mode = "bicubic", then band = the source rows a workgroup stages per band; staged counts every frame) -- host logic only, works without a GPU."""
+    return _describe_letterbox_p010(N.lib().tsvpp_describe_letterbox_p010_bicubic, params, frames, rects, aligned_outputs, tensor_spec(dtype, mean, std))
+
+
+def _describe_letterbox_p010(entry, params, frames, rects, aligned_outputs, spec):
     p = params.parameters if isinstance(params, FrameParameters) else params
     recs = [N.P010(None, None, r.pitch_y, r.pitch_uv, r.width, r.height) for r in _geometry_records(frames)]
     fr = (N.P010 * max(len(recs), 1))(*recs)
     rc = None if rects is None else _rects(rects, len(recs))
     buf = ctypes.create_string_buffer(512)
-    spec = tensor_spec(dtype, mean, std)
-    N.check(N.lib().tsvpp_describe_letterbox_p010_area(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0,
-                                                       buf, len(buf)))
+    N.check(entry(ctypes.byref(p), None if spec is None else ctypes.byref(spec), len(recs), fr, rc, 1 if aligned_outputs else 0, buf, len(buf)))
     return _parse_selection(buf.value.decode())
 
 

@@ -7,6 +7,7 @@ tsvpp_convert_letterbox -- on one stream, timed with HIP events.
     python tools/letterbox_ab.py --dtype f16 [--mean a,b,c] [--std a,b,c]     the tensor legs: tsvpp_convert_letterbox_tensor (see tensor_main; appends to profiles/tensor_ab.txt)
     python tools/letterbox_ab.py --area [--out profiles/letterbox_area_ab.txt]  tsvpp_convert_letterbox_area against the loop it replaces and the BILINEAR letterbox (see area_main)
     python tools/letterbox_ab.py --p010 --area                                  tsvpp_convert_letterbox_p010_area against narrowing + the 8-bit AREA call (see p010_area_main)
+    python tools/letterbox_ab.py --p010 --bicubic                               tsvpp_convert_letterbox_p010_bicubic against narrowing + the 8-bit BICUBIC call (see p010_bicubic_main)
     python tools/letterbox_ab.py --p010 [--out profiles/letterbox_p010_ab.txt]  tsvpp_convert_letterbox_p010 against torch's narrowing to NV12 + the 8-bit letterbox call (see p010_main)
 
 Method: per (configuration, n, leg) a warm-up, then `repeats` timed blocks of `iters` iterations each between two events on the stream; the figure is the MEDIAN
@@ -619,6 +620,145 @@ def p010_area_main(a):
     vpp.Close()
 
 
+def p010_bicubic_main(a):
+    """tsvpp_convert_letterbox_p010_bicubic, p010_area_main's protocol (one stream, sources and canvases rotating through more than 256 MiB, median of the blocks with
+    their spread, every leg parity-checked, bit for bit, on the first and the last canvas of the first set BEFORE it is timed and of the last set it wrote):
+    1920 x 1080 at a pitch of 4096 bytes (3 : 2 down) and 640 x 360 at 1280 (exact 2 x up) into 1280 x 1280, n = 1, 8, 32, in three flavours.
+      (a) one tsvpp_convert_letterbox_p010_bicubic call: parity against tests/p010_cubic_util.py
+      (b) what a caller does today for a cubic canvas: torch `>> 8` and a narrowing copy of both planes into NV12 on the same stream, then
+          tsvpp_convert_letterbox BICUBIC: parity against the CPU oracle on the narrowed frame
+      (c) tsvpp_convert_letterbox BICUBIC alone on frames narrowed beforehand
+      (d) tsvpp_convert_letterbox_p010 BILINEAR: parity against tests/p010_util.py"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import p010_util as M
+    import tensor_util as T
+    from test_gpu_letterbox_p010_bicubic import virtual_frame  # the model's canvas before the colour stage
+    O.build()
+    L = N.lib()
+    vpp = ts.VideoProcessor(device=0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    raw = stream.cuda_stream
+    ns = [int(v) for v in a.ns.split(",")]
+    cw = ch = 1280
+    pad10 = (4 * PAD[0], 4 * PAD[1], 4 * PAD[2])
+    lines = [f"# tools/letterbox_ab.py --p010 --bicubic: {torch.cuda.get_device_name(0)}, {L.tsvpp_version().decode()}, P010 frames -> {cw}x{ch}, median of {a.repeats} blocks of "
+             f"{a.iters} iterations, one stream, sources and canvases rotating through > 256 MiB",
+             "# (a) = 1 x tsvpp_convert_letterbox_p010_bicubic   (b) = torch >> 8 + narrowing copy of both planes into NV12, then tsvpp_convert_letterbox BICUBIC   "
+             "(c) = tsvpp_convert_letterbox BICUBIC alone on frames narrowed beforehand   (d) = tsvpp_convert_letterbox_p010 BILINEAR",
+             "# us per call, [min .. max of the blocks]; roof = (source planes + canvases) of (a) / time, as a share of 8 TB/s"]
+    verdicts = []
+    for gw, gh, pitch in ((1920, 1080, 4096), (640, 360, 1280)):
+        words = pitch // 2
+        nframes = (max(a.frames, -(-(280 << 20) // (pitch * gh * 3 // 2))) + 31) // 32 * 32
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(7)
+        ys16 = torch.randint(-32768, 32768, (nframes, gh, words), dtype=torch.int16, device=dev, generator=gen)
+        uvs16 = torch.randint(-32768, 32768, (nframes, gh // 2, words), dtype=torch.int16, device=dev, generator=gen)
+        ys8, uvs8 = torch.bitwise_right_shift(ys16, 8).to(torch.uint8), torch.bitwise_right_shift(uvs16, 8).to(torch.uint8)
+        tmp_y, tmp_uv = torch.empty_like(ys16[:max(ns)]), torch.empty_like(uvs16[:max(ns)])
+        fr16 = [N.P010(ys16[k].data_ptr(), uvs16[k].data_ptr(), pitch, pitch, gw, gh) for k in range(nframes)]
+        fr8 = [N.NV12(ys8[k].data_ptr(), uvs8[k].data_ptr(), words, words, gw, gh) for k in range(nframes)]
+        rect = ts.letterbox_rect(gw, gh, cw, ch)
+        for fname, fcc, planes, norm, dtype in AREA_FLAVOURS:
+            fp = lambda rt: ts.FrameParameters(width=cw, height=ch, resize_type=rt, pixel_format=fcc, planes_pos=planes, normalization=norm)
+            pa, pb = fp(2).parameters, fp(1).parameters
+            spec = ts.tensor_spec(dtype=T.TORCH[dtype], mean=IMAGENET[0], std=IMAGENET[1]) if dtype else None
+            tdt = T.TORCH[dtype] if dtype else None
+            canvas_bytes = 3 * cw * ch * (T.ESIZE[dtype] if dtype else (4 if norm else 1))
+            d = ts.describe_letterbox_p010_bicubic(fp(2), (gw, gh, pitch), **(dict(dtype=tdt, mean=IMAGENET[0], std=IMAGENET[1]) if dtype else {}))
+            lines += ["", f"## {gw}x{gh} {fname}: kernel={d['kernel']} lds={d['lds']} band={d['band']}",
+                      f"{'n':>3} | " + " | ".join(f"{'(' + k + ') us':>9} {'spread':>19}" for k in "abcd") + f" | {'b / a':>6} {'a / c':>6} {'a / d':>6} {'roof':>6}"]
+            refs = {}
+
+            def reference(f, leg):
+                key = (f, "bc" if leg in "bc" else leg)
+                if key not in refs:
+                    if leg in "ad":
+                        y, uv = ys16[f].cpu().numpy().view(np.uint16), uvs16[f].cpu().numpy().view(np.uint16)
+                        vf = virtual_frame(y, uv, gw, gh, rect, (cw, ch), pad10) if leg == "a" else M.virtual_frame(y, uv, gw, gh, rect, (cw, ch), M.BILINEAR, pad10)
+                        k = M.channels(*vf, fcc)
+                        refs[key] = T.expected(M.quotient(k), 3, IMAGENET, dtype) if dtype else M.stored(k, planes, norm)
+                    else:
+                        q = expected_geo(ys8[f].cpu().numpy(), uvs8[f].cpu().numpy(), gw, rect, (cw, ch), 2, fcc, planes, norm)
+                        refs[key] = T.expected(q, 3, IMAGENET, dtype) if dtype else q.ravel().view(np.uint8)
+                return refs[key]
+
+            for n in ns:
+                sets = max(2, (300 << 20) // (n * canvas_bytes) + 1)
+                pool = [vpp._alloc(pa, cw, ch, n, tdt) for _ in range(sets)]
+                groups = nframes // n
+                arr16 = [(N.P010 * n)(*fr16[g * n:(g + 1) * n]) for g in range(groups)]
+                arr8 = [(N.NV12 * n)(*fr8[g * n:(g + 1) * n]) for g in range(groups)]
+                out_arrs = [(ctypes.c_void_p * n)(*[t[i].data_ptr() for i in range(n)]) for t in pool]
+                ra, rb, sref, ctx = ctypes.byref(pa), ctypes.byref(pb), (ctypes.byref(spec) if dtype else None), vpp._ctx
+
+                def leg_a(k):
+                    if L.tsvpp_convert_letterbox_p010_bicubic(ctx, n, arr16[k % groups], ra, sref, None, pad10[0], pad10[1], pad10[2], out_arrs[k % sets], raw) != 0:
+                        raise RuntimeError("tsvpp_convert_letterbox_p010_bicubic failed")
+
+                def leg_d(k):
+                    if L.tsvpp_convert_letterbox_p010(ctx, n, arr16[k % groups], rb, sref, None, pad10[0], pad10[1], pad10[2], out_arrs[k % sets], raw) != 0:
+                        raise RuntimeError("tsvpp_convert_letterbox_p010 failed")
+
+                def leg_c(k):
+                    if dtype:
+                        sts = L.tsvpp_convert_letterbox_tensor(ctx, n, arr8[k % groups], ra, sref, None, PAD[0], PAD[1], PAD[2], out_arrs[k % sets], raw)
+                    else:
+                        sts = L.tsvpp_convert_letterbox(ctx, n, arr8[k % groups], ra, None, PAD[0], PAD[1], PAD[2], out_arrs[k % sets], raw)
+                    if sts != 0:
+                        raise RuntimeError("the 8-bit BICUBIC letterbox call failed")
+
+                def leg_b(k):
+                    g = k % groups
+                    torch.bitwise_right_shift(ys16[g * n:(g + 1) * n], 8, out=tmp_y[:n])
+                    ys8[g * n:(g + 1) * n].copy_(tmp_y[:n])
+                    torch.bitwise_right_shift(uvs16[g * n:(g + 1) * n], 8, out=tmp_uv[:n])
+                    uvs8[g * n:(g + 1) * n].copy_(tmp_uv[:n])
+                    leg_c(k)
+
+                def parity(leg, last):
+                    got = pool[last % sets]
+                    for i in sorted({0, n - 1}):
+                        if not np.array_equal(T.bits(got[i]), reference((last % groups) * n + i, leg)):
+                            raise SystemExit(f"PARITY FAILURE: leg ({leg}) {gw}x{gh} {fname} n={n} canvas {i}")
+
+                res = {}
+                with torch.cuda.stream(stream):
+                    for leg, fn in (("a", leg_a), ("b", leg_b), ("c", leg_c), ("d", leg_d)):
+                        for t in pool:
+                            t.zero_()
+                        fn(0)
+                        stream.synchronize()
+                        parity(leg, 0)
+                        blocks, last = timed(fn, stream, a.repeats, a.iters, warm=max(5, a.iters // 2))
+                        parity(leg, last)
+                        res[leg] = blocks
+                m = {k: statistics.median(v) for k, v in res.items()}
+                sp = lambda v: f"{min(v):9.2f}..{max(v):<9.2f}"
+                roof = n * (2 * gw * gh * 3 // 2 + canvas_bytes) / (m["a"] * 1e-6) / 8e12
+                lines.append(f"{n:>3} | " + " | ".join(f"{m[k]:9.2f} {sp(res[k])}" for k in "abcd") + f" | {m['b'] / m['a']:6.2f} {m['a'] / m['c']:6.2f} {m['a'] / m['d']:6.2f} {roof:6.1%}")
+                print(lines[-1], flush=True)
+                if n >= 8:
+                    spread = max(res["b"]) - min(res["b"])
+                    verdicts.append((m["b"] - m["a"] > spread, f"{gw}x{gh} {fname}, n = {n}: (b) - (a) = {m['b'] - m['a']:+.2f} us, spread of (b) {spread:.2f} us"))
+                del pool
+                torch.cuda.empty_cache()
+        del ys16, uvs16, ys8, uvs8, tmp_y, tmp_uv
+        torch.cuda.empty_cache()
+    lines += ["", "# parity: (a) against tests/p010_cubic_util.py, (d) against tests/p010_util.py, (b) and (c) against the CPU oracle on the narrowed frames, bit for bit, on the first "
+              "and the last canvas of the first and of the last canvas set a leg wrote", "# expectation ((a) faster than (b) at n = 8 and n = 32 by more than the spread of (b)'s own blocks):"]
+    lines += [f"#   {'met    ' if ok else 'NOT MET'}  {text}" for ok, text in verdicts]
+    lines.append(f"# expectation as a whole: {'met' if all(ok for ok, _ in verdicts) else 'NOT MET'}")
+    lines.append("# a / c and a / d carry no condition.  unmeasured: the kernel's own time from a trace; other band heights")
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+    vpp.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -630,11 +770,14 @@ def main():
     ap.add_argument("--mean", default="0.485,0.456,0.406", help="per stored channel (with --dtype)")
     ap.add_argument("--std", default="0.229,0.224,0.225", help="per stored channel (with --dtype); the library is handed float32(1) / float32(std)")
     ap.add_argument("--area", action="store_true", help="tsvpp_convert_letterbox_area against the loop it replaces and the BILINEAR call; default output profiles/letterbox_area_ab.txt")
+    ap.add_argument("--bicubic", action="store_true", help="with --p010: tsvpp_convert_letterbox_p010_bicubic against narrowing + the 8-bit BICUBIC call; default output profiles/letterbox_p010_bicubic_ab.txt")
     ap.add_argument("--p010", action="store_true", help="tsvpp_convert_letterbox_p010 against torch's narrowing to NV12 + the 8-bit call; default output profiles/letterbox_p010_ab.txt")
     a = ap.parse_args()
     assert a.repeats >= 1 and a.iters >= 1
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "letterbox_p010_area_ab.txt" if a.p010 and a.area else "letterbox_p010_ab.txt" if a.p010 else "letterbox_area_ab.txt" if a.area else "tensor_ab.txt" if a.dtype else "letterbox_ab.txt")
+        a.out = os.path.join(ROOT, "profiles", "letterbox_p010_bicubic_ab.txt" if a.p010 and a.bicubic else "letterbox_p010_area_ab.txt" if a.p010 and a.area else "letterbox_p010_ab.txt" if a.p010 else "letterbox_area_ab.txt" if a.area else "tensor_ab.txt" if a.dtype else "letterbox_ab.txt")
+    if a.p010 and a.bicubic:
+        return p010_bicubic_main(a)
     if a.p010 and a.area:
         return p010_area_main(a)
     if a.p010:
